@@ -1,8 +1,15 @@
 """Headline benchmark: 1 query x 31 rotations x N templates, masked Hamming
 (Template path) with fused min/argmin, on N GPUs (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-per-gpu T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-per-gpu T] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`value`,
+`ms_per_step` = wall time of the K timed steps / K).  --dump-outputs DIR also writes what the
+last timed step returned as DIR/<name>.npy (the inputs are seeded: the same arguments give the
+same outputs on every run).  --full adds the legs that take runs of their own: the CPU
+baseline (`cpu_baseline`), the unprofiled re-timing of sub-millisecond steps and the
+host-slice workloads' profiled pass, resident-call comparison and C++ walk.
 
 `python bench.py --gpus N` with N > 1 and no launcher starts the N ranks itself
 (torch.distributed.run as a child process, before this process touches a GPU)
@@ -68,7 +75,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n-per-gpu", type=int, default=None,
                     help="records per GPU (default 10M; search with 2+ ranks: 12.5M, so 8 ranks are configs[4]'s 100M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each in a run of its own: the CPU "
+                         "baseline leg (cpu_baseline), the unprofiled re-timing of sub-millisecond steps, and for "
+                         "the host-slice workloads the profiled pass behind their kernel times, the resident-call "
+                         "comparison and the C++ walk (default: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64; large outputs as a fixed, seeded sample of rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline leg out")
     ap.add_argument("--reuse-engine", action="store_true",
                     help="build the query engine once instead of once per step (default: per step, in the timed region)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -202,6 +218,40 @@ def check_resolver(shares, denoms):
         d = np.where(den != 0, uneq / den.astype(np.float64), np.inf).min(axis=1)
     idx = int(np.argmin(d))
     return (float(d[idx]), idx) if np.isfinite(d[idx]) else (float("inf"), 2**64 - 1)
+
+
+# ---------------------------------------------------------------------------- --dump-outputs
+
+DUMP_ROWS = 65536  # rows kept of a per-record output: 65536 x 31 f32 = 8 MB, far inside the 64-MB bound
+MATCH_FIELDS = ("distance", "index", "num", "den", "rotation")
+
+
+def match_row(m):
+    """A Match as float64 [distance, index, num, den, rotation] (every field exact in a double but
+    an index of 2^64-1, the no-match marker, which rounds to 2^64)."""
+    return np.array([float(getattr(m, f)) for f in MATCH_FIELDS], np.float64)
+
+
+def dump_rows(n):
+    """The records whose output rows a dump keeps: all of them up to DUMP_ROWS, else a fixed,
+    seeded, sorted sample (the same for every run with the same n)."""
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(n, DUMP_ROWS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(directory, arrays):
+    """Writes {name: array} as DIR/<name>.npy: float64 stays, everything else (u16 rows, record
+    bytes) becomes float32, which holds those values exactly."""
+    d = pathlib.Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        total += a.nbytes
+        np.save(d / f"{name}.npy", a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
 
 
 # ---------------------------------------------------------------------------- CPU baseline
@@ -844,10 +894,30 @@ def run_aux(args, dev):
         m = step()
     dev.synchronize()
     elapsed = time.perf_counter() - t0
+    dump = None
+    if args.dump_outputs:  # what the last timed step returned / wrote, before any further pass
+        if isinstance(m, ih.Match):
+            dump = {"match": match_row(m)}
+        elif separate:
+            rows = dump_rows(n)
+            dump = {"rows": hout[rows], "row_indices": rows.astype(np.float64)}
+        elif args.workload == "load":
+            rows = dump_rows(n)[::64]  # at most 1024 x 3200 record bytes as f32 = 13 MB
+            dump = {"loaded": np.array([float(m)]), "row_indices": rows.astype(np.float64),
+                    "records": np.stack([tdb.read(int(i), 1)[0] for i in rows]).view(np.uint8)}
+        else:  # prepare: the shares and masks written for a sample of the templates
+            # at most 128 templates' P x 12800 u16 as f32 = 6.5 MB x P (fewer templates beyond 6 parties)
+            rows = dump_rows(n)[::512 * -(-P // 6)]
+            dump = {"row_indices": rows.astype(np.float64),
+                    "masks": np.stack([mdb.read(int(i), 1)[0] for i in rows]).view(np.uint8),
+                    **{f"shares_party{j}": np.stack([sdbs[j].read(int(i), 1)[0] for i in rows]) for j in range(P)}}
+    walk_stats = (0, 0.0, 0)
     if separate:
         fc = sorted(first_calls)
         extra["first_call_ms"] = {"median": fc[len(fc) // 2] * 1e3, "max": fc[-1] * 1e3,
                                   "is": "engine creation + the walk's first batch_process call, timed steps"}
+        extra["kernel_times_from"] = "not measured (the timed steps run unprofiled; --full adds a profiled pass)"
+    if separate and args.full:
         dev.reset_stats()
         dev.set_profiling(True)
         for _ in range(args.steps):
@@ -891,7 +961,7 @@ def run_aux(args, dev):
                                     if not shares_wl else "[u16;31]: 62 B per record")}
     dev.set_profiling(False)
     launches, kms, items = walk_stats if separate else dev.kernel_stats(kname)
-    achieved = rec_bytes * items / (kms * 1e-3) / 1e9
+    achieved = rec_bytes * items / (kms * 1e-3) / 1e9 if kms else 0.0
     if separate:
         # host-slice walks: end to end, the records' bytes over the walk's wall time (their windows'
         # kernels overlap on two side streams, so summed kernel times are not a duration)
@@ -917,7 +987,7 @@ def run_aux(args, dev):
         ok = m.index == idx and np.float64(m.distance).view(np.uint64) == np.float64(best).view(np.uint64)
         check = {"expected_index": int(idx), "found_index": int(m.index), "ok": bool(ok)}
     elif args.workload in ("host-shares", "host-masks"):
-        if args.attached:  # the same chunks through the resident calls, for comparison
+        if args.attached and args.full:  # the same chunks through the resident calls, for comparison
             hdev = dev.alloc(chunk * ROT * 2)
             res = {}
             def walk_db(form):
@@ -946,7 +1016,7 @@ def run_aux(args, dev):
                 if args.workload == "host-shares" else check_masks_rows(qt[200:], host[sample]))
         ok = bool((hout[sample] == want).all())
         check = {"sampled_outputs_checked": len(sample), "ok": ok}
-        if file_walk:  # the same walk of the same file from C++, no Python between the calls
+        if file_walk and args.full:  # the same walk of the same file from C++, no Python between the calls
             extra["cxx_walk"] = cxx_walk(shares_wl, n, mpath)
         if mpath is not None:
             del host
@@ -969,11 +1039,13 @@ def run_aux(args, dev):
             ok &= bool((mdb.read(i, 1)[0] == t[200:]).all())
         check = {"sampled_templates_share_identity": len(sample), "ok": bool(ok)}
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args)
         except Exception as ex:  # reported, never fatal
             cpu = {"value": None, "error": str(ex)}
+    if dump is not None:
+        dump_outputs(args.dump_outputs, dump)
     per_unit = ROT if args.workload == "criterion" else 1
     line = {
         "metric": {"resolver": "resolver records/s (share sum + decode + argmin)",
@@ -1032,6 +1104,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("error: --gpus must be >= 1")
+    if not args.dry_run and (args.steps < 1 or args.warmup < 0):
+        raise SystemExit("error: --steps must be >= 1 (the timed steps) and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.single_process:
         sys.exit(launch_ranks(args))
     ranks = Ranks(args)
@@ -1196,10 +1270,10 @@ def main():
             pend = p
         return finish(pend) if pend is not None else m
 
-    # the CPU baseline (rank 0 of a one-GPU run): measured on its own, before any GPU step,
+    # the CPU baseline (--full, rank 0 of a one-GPU run): measured on its own, before any GPU step,
     # on every CPU the process may use (not beside the GPU-driving loop)
     cpu = None
-    if rank == 0 and world_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_gpus == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args)
         except Exception as ex:  # reported, never fatal
@@ -1226,17 +1300,6 @@ def main():
     for d in devs:
         d.set_profiling(False)
     elapsed = ranks.max_over_ranks(elapsed)
-    # participant-sized steps (tens of us): the HIP timing events around every launch are part of
-    # the timed region above, as the roofline needs; the same number of steps is timed once more
-    # without them, which is the wall time a caller sees per call
-    unprofiled_ms = None
-    if elapsed / args.steps < 1e-3:
-        sync_all()
-        t1 = time.perf_counter()
-        run_steps(args.steps)
-        sync_all()
-        unprofiled_ms = ranks.max_over_ranks(time.perf_counter() - t1) / args.steps * 1e3
-
     kname = {"search": "template_search", "batch": "template_batch", "masks": "masks", "shares": "shares"}[args.workload]
     rec_bytes = {"search": BYTES_PER_TEMPLATE,
                  "batch": BYTES_PER_TEMPLATE, "masks": 1600, "shares": 25600}[args.workload]
@@ -1249,6 +1312,9 @@ def main():
         check = ({**found[0], "ok": bool(ok)} if args.workload == "search"
                  else {"planted_queries": found, "query_groups": sorted({f["query"] // 4 for f in found}),
                        "ok": bool(ok)})
+        # the last timed step's result: one merged Match, or one per query of the batch
+        dump = ({"match": match_row(m)} if args.workload == "search"
+                else {"matches": np.stack([match_row(r) for r in results])})
         if args.workload == "batch":
             m = results[plants[0][0]]
     else:  # spot-check 64 outputs
@@ -1260,7 +1326,22 @@ def main():
                 else check_shares_rows(ih.encode(ih.Template.from_array(query)).values, recs))
         ok = bool((full[sample] == want).all())
         check = {"sampled_outputs_checked": 64, "ok": bool(ok)}
+        if args.dump_outputs:  # of the [n][31] rows the last timed step left in HBM
+            rows = dump_rows(n)
+            dump = {"rows": full[rows], "row_indices": (lo + rows).astype(np.float64)}
         del full
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dump)
+    # participant-sized steps (tens of us): the HIP timing events around every launch are part of
+    # the timed region above, as the roofline needs; with --full the same number of steps is timed
+    # once more without them, which is the wall time a caller sees per call
+    unprofiled_ms = None
+    if args.full and elapsed / args.steps < 1e-3:
+        sync_all()
+        t1 = time.perf_counter()
+        run_steps(args.steps)
+        sync_all()
+        unprofiled_ms = ranks.max_over_ranks(time.perf_counter() - t1) / args.steps * 1e3
     # kernel time per launch: averaged over this process's devices (each searches its own shards)
     stats = [d.kernel_stats(kname) for d in devs]
     if sum(s[0] for s in stats) == 0 and args.workload == "batch":  # a 1-3 query batch streams

@@ -89,6 +89,36 @@ def test_plant_sites_inside_database():
     assert bench.plant_sites(400_000, 1)[0] >= 200_000
 
 
+def test_full_is_off_by_default_and_steps_are_checked(monkeypatch):
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit, match="--steps"):
+        bench.main()
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+
+    import bench
+
+    rows = bench.dump_rows(1_000_000)
+    assert len(rows) == bench.DUMP_ROWS == len(set(rows.tolist())) and (rows == bench.dump_rows(1_000_000)).all()
+    assert (bench.dump_rows(5) == np.arange(5)).all()
+    m = bench.ih.Match(0.25, 7, 10, 40, -3, 0)
+    bench.dump_outputs(tmp_path / "o", {"match": bench.match_row(m), "rows": np.arange(62, dtype=np.uint16).reshape(2, 31)})
+    got = np.load(tmp_path / "o" / "match.npy")
+    assert got.dtype == np.float64 and got.tolist() == [0.25, 7.0, 10.0, 40.0, -3.0]
+    got = np.load(tmp_path / "o" / "rows.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 31) and got[1, 30] == 61
+
+
 def test_batch_plants_span_query_groups():
     import bench
 

@@ -71,7 +71,7 @@ for S in "$@"; do
         tail -3 $O/pmc.log ;;
     *)
         A=$(bench_args $S) || { echo "unknown step $S"; exit 2; }
-        timeout -k 10 300 python bench.py $A > $O/$S.log 2>&1 || { echo "$S rc=$?"; tail -3 $O/$S.log; exit 1; }
+        timeout -k 10 300 python bench.py --full $A > $O/$S.log 2>&1 || { echo "$S rc=$?"; tail -3 $O/$S.log; exit 1; }
         grep '^{' $O/$S.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); c=d.get('cpu_baseline') or {}; k=d.get('kernel') or {}; print('$S', '%.4g'%d['value'], d['unit'], 'ms', round(d['ms_per_step'],4), 'kernel_ms', round(k.get('avg_ms') or 0,4), 'frac', round(d['roofline']['frac'],3), 'cpu', c.get('value'), c.get('cores'))" ;;
     esac
 done
