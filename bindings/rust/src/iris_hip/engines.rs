@@ -83,6 +83,58 @@ impl DistanceEngine {
     }
 }
 
+/// `nq` DistanceEngines at once (no reference counterpart; src/lib.rs:33-52 per query): a
+/// participant with several pending queries reads its resident share database once for all of
+/// them.  `out[q]` receives what `DistanceEngine::new(&queries[q])` would write.
+pub struct DistanceBatchEngine {
+    h: Handle,
+    nq: usize,
+}
+
+impl DistanceBatchEngine {
+    pub fn new(queries: &[EncodedBits]) -> Self {
+        Self::new_on(default_device(), queries).unwrap_or_else(|e| panic!("DistanceBatchEngine::new: {e}"))
+    }
+
+    /// 1..=IRIS_DISTANCE_BATCH_MAX queries.
+    pub fn new_on(device: &Device, queries: &[EncodedBits]) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            ffi::iris_distance_batch_engine_new(device.raw(), queries.as_ptr().cast(), queries.len() as u32, &mut raw)
+        })?;
+        Ok(Self { h: Handle { raw, _device: device.clone() }, nq: queries.len() })
+    }
+
+    pub fn nq(&self) -> usize {
+        self.nq
+    }
+
+    /// Records [first, first + n) of a resident share database, n = `out[q].len()` for every q:
+    /// out[q][i][k] = dot_u16(rot(queries[q], k - 15), db[first + i]).
+    pub fn batch_process(&self, out: &mut [Vec<[u16; 31]>], db: &Database, first: u64) -> Result<()> {
+        assert_eq!(out.len(), self.nq);
+        let n = out.first().map_or(0, |o| o.len());
+        assert!(out.iter().all(|o| o.len() == n), "output rows of different lengths");
+        if n == 0 {
+            return Ok(());
+        }
+        // the C call writes one query-major array
+        let mut flat = vec![[0_u16; 31]; self.nq * n];
+        check(unsafe {
+            ffi::iris_distance_batch_process(self.h.raw, db.raw(), first, n as u64, flat.as_mut_ptr().cast())
+        })?;
+        for (q, o) in out.iter_mut().enumerate() {
+            o.copy_from_slice(&flat[q * n..(q + 1) * n]);
+        }
+        Ok(())
+    }
+
+    /// The rows stay on the GPU: `out_device` is a DEVICE array of nq * n * 31 u16 (query-major).
+    pub fn batch_process_device(&self, out_device: *mut u16, db: &Database, first: u64, n: u64) -> Result<()> {
+        check(unsafe { ffi::iris_distance_batch_process_device(self.h.raw, db.raw(), first, n, out_device) })
+    }
+}
+
 /// `MasksEngine` (src/lib.rs:55-80): out[i][k] = dot_bool(rot(query, k - 15), db[i]).
 pub struct MasksEngine {
     h: Handle,

@@ -127,7 +127,7 @@ int iris_device_stream(iris_device_t *dev, void **stream);
 int iris_device_memory(iris_device_t *dev, size_t *free_bytes, size_t *total_bytes);
 /* Kernel timing with HIP events recorded on the device stream around every
  * launch of the named kernel family ("template_search", "template_counts",
- * "masks", "shares", ...).  Disabled by default. */
+ * "masks", "shares", "shares_batch" (items = records x queries), ...).  Disabled by default. */
 int iris_device_set_profiling(iris_device_t *dev, int enabled);
 int iris_device_kernel_stats(iris_device_t *dev, const char *kernel, uint64_t *launches,
                              double *total_ms, uint64_t *items);
@@ -329,6 +329,24 @@ int iris_template_batch_engine_new(iris_device_t *dev, const iris_template_t *qu
                                    iris_engine_t **out);
 int iris_template_batch_search(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                                uint64_t index_base, iris_match_t *out);
+
+/* Batched DistanceEngine (no reference counterpart: the reference builds one DistanceEngine per
+ * query, src/lib.rs:33-52, and a participant with Q pending queries walks its share file Q
+ * times): nq DistanceEngines at once, run against a share database in one pass.  On the TILES
+ * layout every share tile is read once for up to four queries; on LANES the batch runs nq
+ * single-query passes (the layout only selects the kernel family; results are identical).
+ * Destroyed with iris_engine_destroy.  The single-query calls (iris_engine_batch_process*)
+ * refuse a batch engine and these refuse a single-query one (IRIS_E_ARG). */
+#define IRIS_DISTANCE_BATCH_MAX 64
+/* nq DistanceEngines at once: queries = nq x 12800 u16 (EncodedBits), any values */
+int iris_distance_batch_engine_new(iris_device_t *dev, const uint16_t *queries, uint32_t nq, iris_engine_t **out);
+/* out[(q*n + i)*31 + k] = dot_u16(rot(queries[q], k-15), db[first+i])  -- query-major: slab q is exactly
+ * what iris_engine_batch_process of a DistanceEngine(queries[q]) writes (src/lib.rs:42-52).  Host /
+ * device output forms (out: host array, out_device: DEVICE array, of nq*n*31 uint16_t).  n == 0
+ * writes nothing. */
+int iris_distance_batch_process(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n, uint16_t *out);
+int iris_distance_batch_process_device(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                                       uint16_t *out_device);
 
 /* ---------------------------------------------------------------- resolver
  * The resolver's aggregation (src/main.rs:597-621) fused on the GPU: for each

@@ -467,6 +467,30 @@ public:
     }
 };
 
+// nq DistanceEngines at once (iris_distance_batch_engine_new): one pass over a resident share
+// database answers every query; out[q * n + i] is row i of DistanceEngine(queries[q]).
+class DistanceBatchEngine : public detail::Engine {
+public:
+    explicit DistanceBatchEngine(const std::vector<EncodedBits> &queries, Device &dev = Device::default_device())
+        : nq_((uint32_t)queries.size()) {
+        static_assert(sizeof(EncodedBits) == IRIS_BITS * sizeof(uint16_t), "EncodedBits is the reference's 25600-B record");
+        check(iris_distance_batch_engine_new(dev.handle(), queries.empty() ? nullptr : queries[0].v.data(), nq_, &h_));
+    }
+    uint32_t nq() const { return nq_; }
+    // records [first, first + n) of db; out is resized to nq * n rows, query-major
+    void batch_process(std::vector<Rotations> &out, const Database &db, uint64_t first, uint64_t n) const {
+        out.resize((size_t)nq_ * n);
+        check(iris_distance_batch_process(h_, db.handle(), first, n, out.empty() ? nullptr : out[0].data()));
+    }
+    // the rows stay on the GPU: out_device is a device array of nq * n * 31 u16
+    void batch_process_device(uint16_t *out_device, const Database &db, uint64_t first, uint64_t n) const {
+        check(iris_distance_batch_process_device(h_, db.handle(), first, n, out_device));
+    }
+
+private:
+    uint32_t nq_ = 0;
+};
+
 class MasksEngine : public detail::Engine {
 public:
     explicit MasksEngine(const Bits &query, Device &dev = Device::default_device()) {

@@ -1213,6 +1213,7 @@ int iris_engine_batch_process(iris_engine_t *e, const iris_db_t *db, uint64_t fi
     IRIS_KEEP_DEVICE();
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_MASKS || e->kind == IRIS_KIND_SHARES, "batch_process needs a masks or distance engine");
+    ARG(e->nq == 0, "a distance batch engine runs through iris_distance_batch_process");
     ARG(db->k.kind == e->kind, "engine kind does not match the database kind");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     std::lock_guard<std::recursive_mutex> g(e->dev->mu);
@@ -1230,6 +1231,7 @@ int iris_engine_batch_process_device(iris_engine_t *e, const iris_db_t *db, uint
     IRIS_KEEP_DEVICE();
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_MASKS || e->kind == IRIS_KIND_SHARES, "batch_process needs a masks or distance engine");
+    ARG(e->nq == 0, "a distance batch engine runs through iris_distance_batch_process");
     ARG(db->k.kind == e->kind, "engine kind does not match the database kind");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     iris_device *d = e->dev;
@@ -1261,6 +1263,7 @@ int iris_engine_batch_process_host(iris_engine_t *e, const void *records, uint64
     IRIS_KEEP_DEVICE();
     ARG(e, "engine is NULL");
     ARG(e->kind == IRIS_KIND_MASKS || e->kind == IRIS_KIND_SHARES, "batch_process needs a masks or distance engine");
+    ARG(e->nq == 0, "a distance batch engine runs through iris_distance_batch_process");
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
@@ -1708,6 +1711,118 @@ int iris_template_batch_search(iris_engine_t *e, const iris_db_t *db, uint64_t f
     return 0;
 }
 
+// ------------------------------------------------------------------ batched DistanceEngine
+
+// nq DistanceEngines (src/lib.rs:33-40) at once: one single-query engine per query (its LANES table
+// and its TILES fragments, built by the same launch as iris_distance_engine_new's), run together.
+int iris_distance_batch_engine_new(iris_device_t *d, const uint16_t *queries, uint32_t nq, iris_engine_t **out) {
+    IRIS_KEEP_DEVICE();
+    ARG(nq > 0 && nq <= IRIS_DISTANCE_BATCH_MAX, "a distance batch holds 1..IRIS_DISTANCE_BATCH_MAX (64) queries");
+    ARG(d && queries && out, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    iris_engine *e = new (std::nothrow) iris_engine();
+    if (!e) return fail(IRIS_E_NOMEM, "out of host memory");
+    e->dev = d;
+    e->kind = IRIS_KIND_SHARES;
+    e->nq = nq;
+    for (uint32_t i = 0; i < nq; ++i) {
+        iris_engine *c = nullptr;
+        const int rc = engine_from_query(d, IRIS_KIND_SHARES, queries + (size_t)i * IRIS_BITS, IRIS_BITS * 2,
+                                         (size_t)kShareDwords * kSlotTabStride * 4, kShareFragBytes, &c,
+                                         launch_query_shares);
+        if (rc != 0) {
+            engine_free(e);
+            return rc;
+        }
+        e->sub.push_back(c);
+    }
+    device_retain(d);
+    *out = e;
+    return 0;
+}
+
+static int distance_batch_args(iris_engine_t *e, const iris_db_t *db) {
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_SHARES && e->nq > 0, "not a distance batch engine (iris_distance_batch_engine_new)");
+    ARG(db->k.kind == IRIS_KIND_SHARES, "a distance batch engine needs a share database");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    return 0;
+}
+
+// Enqueues the batch over [first, first + n): query q's rows to the device array o + q * n * 31.
+// TILES: the multi-query kernels (iris_shares_batch.hip); LANES: one single-query pass per query.
+// sig (TILES only): the completion word, armed if the call's last kernel signals it.
+static int enqueue_distance_batch(iris_engine *e, const iris_db *db, uint64_t first, uint64_t n, uint16_t *o,
+                                  DoneSignal *sig = nullptr) {
+    iris_device *d = e->dev;
+    const LaunchRange r{first, n};
+    if (sig) sig->armed = false;
+    if (db->k.layout == IRIS_LAYOUT_TILES) {
+        const void *frags[IRIS_DISTANCE_BATCH_MAX];
+        for (uint32_t q = 0; q < e->nq; ++q) frags[q] = e->sub[q]->qfrag;
+        return timed(d, "shares_batch", n * e->nq,
+                     [&] { return launch_shares_batch(d->hooks, d->stream, db->data, frags, e->nq, r, o, sig); });
+    }
+    for (uint32_t q = 0; q < e->nq; ++q)
+        CHK(timed(d, "shares_batch", n,
+                  [&] { return launch_shares(d->stream, db->data, e->sub[q]->qtab, r, o + (uint64_t)q * n * kRot); }));
+    return 0;
+}
+
+int iris_distance_batch_process_device(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                       uint16_t *out_device) {
+    IRIS_KEEP_DEVICE();
+    CHK(distance_batch_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (n == 0) return 0;
+    ARG(out_device, "out is NULL");
+    // as iris_engine_batch_process_device: where the call's last kernel is a participant-sized
+    // single-query one, the call returns on the completion word that kernel writes
+    DoneSignal sig{};
+    if (db->k.layout == IRIS_LAYOUT_TILES) {
+        CHK(ensure_ticket(d));
+        CHK(ensure_host_done(d));
+        sig.ticket = (uint32_t *)d->ticket.p;
+        sig.done = d->host_done;
+        sig.seq = ++d->done_seq;
+        if (sig.seq == 0) sig.seq = ++d->done_seq;  // 0 is the word's initial value
+    }
+    CHK(enqueue_distance_batch(e, db, first, n, out_device, sig.done ? &sig : nullptr));
+    if (!sig.armed) return sync(d);
+    CHK(wait_done(d, sig.seq));
+    if (d->profiling) fold_done(d);
+    return 0;
+}
+
+int iris_distance_batch_process(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint16_t *out) {
+    IRIS_KEEP_DEVICE();
+    CHK(distance_batch_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (n == 0) return 0;
+    ARG(out, "out is NULL");
+    // chunks of records whose nq slabs fit the device's row buffer; slab q of a chunk is copied to
+    // its place in the caller's query-major array
+    const uint64_t ch = std::min<uint64_t>(n, kU16Chunk / e->nq / 32 * 32);  // whole tiles
+    CHK(ensure(d, d->out_a, ch * e->nq * kRot * 2));
+    for (uint64_t done = 0; done < n; done += ch) {
+        const uint64_t m = std::min<uint64_t>(ch, n - done);
+        uint16_t *o = (uint16_t *)d->out_a.p;
+        CHK(enqueue_distance_batch(e, db, first + done, m, o));
+        for (uint32_t q = 0; q < e->nq; ++q)
+            HIPCHK(hipMemcpyAsync(out + ((uint64_t)q * n + done) * kRot, o + (uint64_t)q * m * kRot, m * kRot * 2,
+                                  hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ resolver
 
 static int resolver_finish(iris_device *d, uint32_t np, Partial *res) {
@@ -2129,7 +2244,7 @@ int iris_query_table_sizes(int kind, uint32_t nq, size_t *tab_bytes, size_t *fra
 int iris_engine_query_tables(const iris_engine_t *e, void *tab, size_t tab_bytes, void *frag, size_t frag_bytes) {
     IRIS_KEEP_DEVICE();
     ARG(e, "engine is NULL");
-    ARG(e->sub.empty(), "a streamed batch engine (<= 3 queries) holds one engine per query");
+    ARG(e->sub.empty(), "a streamed template batch (<= 3 queries) or distance batch engine holds one engine per query");
     size_t tb = 0, fb = 0;
     CHK(iris_query_table_sizes(e->kind, e->nq, &tb, &fb));
     ARG(tab_bytes == tb && frag_bytes == fb, "table sizes do not match the engine's layout");

@@ -292,6 +292,11 @@ int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts,
                     double *dist_out, Partial *partials);
 int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,
                        DoneSignal *sig = nullptr);
+// nq DistanceEngine queries in one pass over a TILES share database (iris_shares_batch.hip):
+// qfrags[q] = query q's fragments (as launch_shares_mfma's qfrag), rows of query q at out + q * r.n * 31.
+// sig: as launch_shares_mfma's, armed when the last launch signals.
+int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t nq,
+                        LaunchRange r, uint16_t *out, DoneSignal *sig = nullptr);
 int launch_template_search(void *stream, const void *db, const void *qtab, LaunchRange r, double *dist_out,
                            Partial *partials, uint32_t *n_partials);
 // consumes partials; the winner's idx (range-relative) is offset by idx_base

@@ -64,6 +64,7 @@ _NULL = ctypes.c_void_p()
 COLS, ROWS, BITS, LIMBS, ROTATIONS = 200, 64, 12800, 200, 31
 KIND_MASKS, KIND_SHARES, KIND_TEMPLATES = 1, 2, 3
 LAYOUT_DEFAULT, LAYOUT_LANES, LAYOUT_TILES = 0, 1, 2
+DISTANCE_BATCH_MAX = 64  # IRIS_DISTANCE_BATCH_MAX: queries of a DistanceBatchEngine
 _REC_DTYPE = {KIND_MASKS: (np.uint64, LIMBS), KIND_SHARES: (np.uint16, BITS), KIND_TEMPLATES: (np.uint64, 2 * LIMBS)}
 
 
@@ -161,6 +162,9 @@ def load_library(path=None):
             "iris_template_search": ([P, P, u64, u64, u64, P, ctypes.POINTER(Match)], ctypes.c_int),
             "iris_template_batch_engine_new": ([P, P, ctypes.c_uint32, PP], ctypes.c_int),
             "iris_template_batch_search": ([P, P, u64, u64, u64, ctypes.POINTER(Match)], ctypes.c_int),
+            "iris_distance_batch_engine_new": ([P, P, ctypes.c_uint32, PP], ctypes.c_int),
+            "iris_distance_batch_process": ([P, P, u64, u64, P], ctypes.c_int),
+            "iris_distance_batch_process_device": ([P, P, u64, u64, P], ctypes.c_int),
             "iris_resolver_search": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, P,
                                       ctypes.POINTER(Match)], ctypes.c_int),
             "iris_resolver_search_host": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64,
@@ -236,6 +240,7 @@ def exported_symbols():
         "iris_group_db_shard", "iris_group_db_generate", "iris_group_db_write", "iris_group_db_read",
         "iris_group_db_load_file", "iris_group_template_search", "iris_group_template_search_async",
         "iris_group_pending_wait", "iris_group_template_batch_search",
+        "iris_distance_batch_engine_new", "iris_distance_batch_process", "iris_distance_batch_process_device",
     ]
 
 
@@ -997,6 +1002,44 @@ class TemplateBatchEngine(_Engine):
         _check(load_library().iris_template_batch_search(self.handle, db.handle, int(first), int(n), int(index_base),
                                                          out))
         return list(out)
+
+
+class DistanceBatchEngine(_Engine):
+    """nq DistanceEngines at once (iris_distance_batch_engine_new): one pass over a share database
+    answers every query; out[q] is what DistanceEngine(queries[q]).batch_process writes."""
+
+    kind = KIND_SHARES
+
+    def __init__(self, device, queries):
+        self.device = device
+        q = _records(KIND_SHARES, queries)
+        self.nq = q.shape[0]
+        h = ctypes.c_void_p()
+        _check(load_library().iris_distance_batch_engine_new(device.handle, _ptr(q), self.nq, ctypes.byref(h)))
+        self.handle = h
+
+    def query_tables(self):
+        raise IrisError(-1, "a distance batch engine holds one DistanceEngine's tables per query")
+
+    def batch_process(self, out, db, first=0, n=None):
+        """`db` is a share Database (records [first, first+n)); `out` a C-contiguous [nq, n, 31]
+        uint16 array, filled in place: out[q, i, k] = dot_u16(rot(queries[q], k-15), db[first+i])."""
+        n = (len(db) - first) if n is None else n
+        if (not isinstance(out, np.ndarray) or out.dtype != np.uint16 or not out.flags.c_contiguous or out.ndim != 3
+                or out.shape[0] != self.nq or out.shape[2] != ROTATIONS):
+            raise IrisError(-1, f"out must be a C-contiguous [{self.nq}, n, 31] uint16 array")
+        if out.shape[1] != n:  # assert_eq!(out.len(), db.len()) (src/lib.rs:43), per query
+            raise IrisError(-1, f"assertion `out.len() == db.len()` failed: {out.shape[1]} != {n}")
+        _check(load_library().iris_distance_batch_process(self.handle, db.handle, int(first), int(n), _ptr(out)))
+        return out
+
+    def batch_process_device(self, db, out_device_ptr, first=0, n=None):
+        """Results stay on the GPU: out_device_ptr is a device array of nq*n*31 u16 (query-major)."""
+        n = (len(db) - first) if n is None else n
+        rc = load_library().iris_distance_batch_process_device(self.handle, db.handle, int(first), int(n),
+                                                               int(out_device_ptr))
+        if rc:
+            _check(rc)
 
 
 # ====================================================================== device groups
