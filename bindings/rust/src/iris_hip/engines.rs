@@ -204,6 +204,73 @@ impl MasksEngine {
     }
 }
 
+/// `nq` MasksEngines at once (no reference counterpart; the reference computes denominators and
+/// decodes one query at a time, src/main.rs:506-519 and 597-621): a resolver with several pending
+/// queries reads its resident masks database once for all of them.
+pub struct MasksBatchEngine {
+    h: Handle,
+    nq: usize,
+}
+
+impl MasksBatchEngine {
+    pub fn new(queries: &[Bits]) -> Self {
+        Self::new_on(default_device(), queries).unwrap_or_else(|e| panic!("MasksBatchEngine::new: {e}"))
+    }
+
+    /// 1..=IRIS_MASKS_BATCH_MAX queries.
+    pub fn new_on(device: &Device, queries: &[Bits]) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            ffi::iris_masks_batch_engine_new(device.raw(), queries.as_ptr().cast(), queries.len() as u32, &mut raw)
+        })?;
+        Ok(Self { h: Handle { raw, _device: device.clone() }, nq: queries.len() })
+    }
+
+    pub fn nq(&self) -> usize {
+        self.nq
+    }
+
+    /// Records [first, first + n) of a resident masks database, n = `out[q].len()` for every q:
+    /// out[q][i][k] = dot_bool(rot(queries[q], k - 15), db[first + i]).
+    pub fn batch_process(&self, out: &mut [Vec<[u16; 31]>], db: &Database, first: u64) -> Result<()> {
+        assert_eq!(out.len(), self.nq);
+        let n = out.first().map_or(0, |o| o.len());
+        assert!(out.iter().all(|o| o.len() == n), "output rows of different lengths");
+        if n == 0 {
+            return Ok(());
+        }
+        // the C call writes one query-major array
+        let mut flat = vec![[0_u16; 31]; self.nq * n];
+        check(unsafe { ffi::iris_masks_batch_process(self.h.raw, db.raw(), first, n as u64, flat.as_mut_ptr().cast()) })?;
+        for (q, o) in out.iter_mut().enumerate() {
+            o.copy_from_slice(&flat[q * n..(q + 1) * n]);
+        }
+        Ok(())
+    }
+
+    /// The resolver's step for every query in one pass over masks [first, first + n):
+    /// `shares_device[p]` is participant p's DEVICE array of nq x n x 31 u16, query-major (what
+    /// `DistanceBatchEngine::batch_process_device` wrote over the same records).  One
+    /// (distance, index) per query.
+    pub fn resolve(&self, masks: &Database, first: u64, n: u64, shares_device: &[*const u16]) -> Result<Vec<(f64, usize)>> {
+        let mut m = vec![ffi::IrisMatch::default(); self.nq];
+        check(unsafe {
+            ffi::iris_resolver_batch_search_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                0,
+                ptr::null_mut(),
+                m.as_mut_ptr(),
+            )
+        })?;
+        Ok(m.iter().map(match_to_pair).collect())
+    }
+}
+
 /// `distances` (src/lib.rs:82-87).
 pub fn distances(query: &EncodedBits, entry: &EncodedBits) -> [u16; 31] {
     let mut result = [0_u16; 31];

@@ -40,6 +40,7 @@ pub const IRIS_LAYOUT_TILES: c_int = 2;
 /// Bytes of a device group's RCCL id (`iris_group_unique_id`).
 pub const IRIS_GROUP_ID_BYTES: usize = 128;
 pub const IRIS_DISTANCE_BATCH_MAX: usize = 64;
+pub const IRIS_MASKS_BATCH_MAX: usize = 64;
 pub const IRIS_GROUP_BUS_ID_BYTES: usize = 32;
 
 /// Opaque handles (`iris_device_t`, `iris_db_t`, `iris_engine_t`, `iris_pending_t`).
@@ -267,6 +268,37 @@ extern "C" {
         first: u64,
         n: u64,
         out_device: *mut u16,
+    ) -> c_int;
+    pub fn iris_masks_batch_engine_new(
+        dev: *mut IrisDevice,
+        query_masks: *const u64,
+        nq: u32,
+        out: *mut *mut IrisEngine,
+    ) -> c_int;
+    pub fn iris_masks_batch_process(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        out: *mut u16,
+    ) -> c_int;
+    pub fn iris_masks_batch_process_device(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        out_device: *mut u16,
+    ) -> c_int;
+    pub fn iris_resolver_batch_search_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        dist_out_device: *mut f64,
+        out: *mut IrisMatch,
     ) -> c_int;
 
     // resolver

@@ -127,7 +127,8 @@ int iris_device_stream(iris_device_t *dev, void **stream);
 int iris_device_memory(iris_device_t *dev, size_t *free_bytes, size_t *total_bytes);
 /* Kernel timing with HIP events recorded on the device stream around every
  * launch of the named kernel family ("template_search", "template_counts",
- * "masks", "shares", "shares_batch" (items = records x queries), ...).  Disabled by default. */
+ * "masks", "shares", "shares_batch" (items = records x queries), "masks_batch" and
+ * "masks_batch_resolve" (the same), ...).  Disabled by default. */
 int iris_device_set_profiling(iris_device_t *dev, int enabled);
 int iris_device_kernel_stats(iris_device_t *dev, const char *kernel, uint64_t *launches,
                              double *total_ms, uint64_t *items);
@@ -347,6 +348,34 @@ int iris_distance_batch_engine_new(iris_device_t *dev, const uint16_t *queries, 
 int iris_distance_batch_process(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n, uint16_t *out);
 int iris_distance_batch_process_device(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                                        uint16_t *out_device);
+
+/* Batched MasksEngine and resolver step (no reference counterpart: the reference computes the
+ * denominators and decodes one query at a time, src/main.rs:506-519 and 597-621, so a resolver with
+ * Q pending queries reads its masks Q times): nq MasksEngines at once.  On the TILES layout ranges
+ * past 1024 tiles of 32 records read every mask tile once for up to four queries; smaller ranges
+ * and LANES databases run one single-query pass per query (results are identical).  Destroyed
+ * with iris_engine_destroy.  The single-query calls (iris_engine_batch_process*,
+ * iris_resolver_search_masks*) refuse a masks batch engine and these refuse a single-query or a
+ * distance batch engine (IRIS_E_ARG). */
+#define IRIS_MASKS_BATCH_MAX 64
+/* nq MasksEngines at once: query_masks = nq x 200 u64 (Bits), any values */
+int iris_masks_batch_engine_new(iris_device_t *dev, const uint64_t *query_masks, uint32_t nq, iris_engine_t **out);
+/* out[(q*n + i)*31 + k] = dot_bool(rot(query_masks[q], k-15), db[first+i])  -- query-major: slab q is exactly
+ * what iris_engine_batch_process of a MasksEngine(query_masks[q]) writes (src/lib.rs:69-79).  Host /
+ * device output forms (out: host array, out_device: DEVICE array, of nq*n*31 uint16_t).  n == 0
+ * writes nothing. */
+int iris_masks_batch_process(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n, uint16_t *out);
+int iris_masks_batch_process_device(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                                    uint16_t *out_device);
+/* The fused resolver step (iris_resolver_search_masks, below) for all nq queries in one pass over
+ * masks records [first, first+n): shares_device[p] is a DEVICE array of nq*n*31 uint16_t, query-major
+ * -- exactly what iris_distance_batch_process_device wrote for participant p over the same range
+ * (parts = 1..8).  out[q] (nq matches) is what iris_resolver_search_masks gives for
+ * MasksEngine(query_masks[q]) and slab q of every part.  dist_out_device: NULL, or a DEVICE array of
+ * nq*n doubles (query-major). */
+int iris_resolver_batch_search_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                     const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                     double *dist_out_device, iris_match_t *out);
 
 /* ---------------------------------------------------------------- resolver
  * The resolver's aggregation (src/main.rs:597-621) fused on the GPU: for each

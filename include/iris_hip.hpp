@@ -528,6 +528,40 @@ public:
     }
 };
 
+// nq MasksEngines at once (iris_masks_batch_engine_new): one pass over a resident masks database
+// answers every query; out[q * n + i] is row i of MasksEngine(queries[q]).
+class MasksBatchEngine : public detail::Engine {
+public:
+    explicit MasksBatchEngine(const std::vector<Bits> &queries, Device &dev = Device::default_device())
+        : nq_((uint32_t)queries.size()) {
+        static_assert(sizeof(Bits) == IRIS_LIMBS * sizeof(uint64_t), "Bits is the reference's 1600-B record");
+        check(iris_masks_batch_engine_new(dev.handle(), queries.empty() ? nullptr : queries[0].limbs.data(), nq_, &h_));
+    }
+    uint32_t nq() const { return nq_; }
+    // records [first, first + n) of db; out is resized to nq * n rows, query-major
+    void batch_process(std::vector<Rotations> &out, const Database &db, uint64_t first, uint64_t n) const {
+        out.resize((size_t)nq_ * n);
+        check(iris_masks_batch_process(h_, db.handle(), first, n, out.empty() ? nullptr : out[0].data()));
+    }
+    // the rows stay on the GPU: out_device is a device array of nq * n * 31 u16
+    void batch_process_device(uint16_t *out_device, const Database &db, uint64_t first, uint64_t n) const {
+        check(iris_masks_batch_process_device(h_, db.handle(), first, n, out_device));
+    }
+    // The resolver step for every query in one pass over the masks: shares_device[p] is participant
+    // p's device array of nq * n * 31 u16, query-major (DistanceBatchEngine::batch_process_device's
+    // output over the same records); one Match per query.
+    std::vector<Match> resolve(const Database &db, const std::vector<const uint16_t *> &shares_device, uint64_t first,
+                               uint64_t n, uint64_t index_base = 0, double *dist_out_device = nullptr) const {
+        std::vector<Match> m(nq_);
+        check(iris_resolver_batch_search_masks(h_, db.handle(), first, n, shares_device.data(),
+                                               (uint32_t)shares_device.size(), index_base, dist_out_device, m.data()));
+        return m;
+    }
+
+private:
+    uint32_t nq_ = 0;
+};
+
 // An enqueued search (TemplateEngine::search_async): wait() once for its Match;
 // destroying it unwaited waits and discards the result.
 class PendingSearch {

@@ -1213,7 +1213,7 @@ int iris_engine_batch_process(iris_engine_t *e, const iris_db_t *db, uint64_t fi
     IRIS_KEEP_DEVICE();
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_MASKS || e->kind == IRIS_KIND_SHARES, "batch_process needs a masks or distance engine");
-    ARG(e->nq == 0, "a distance batch engine runs through iris_distance_batch_process");
+    ARG(e->nq == 0, "a batch engine runs through iris_distance_batch_process / iris_masks_batch_process");
     ARG(db->k.kind == e->kind, "engine kind does not match the database kind");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     std::lock_guard<std::recursive_mutex> g(e->dev->mu);
@@ -1231,7 +1231,7 @@ int iris_engine_batch_process_device(iris_engine_t *e, const iris_db_t *db, uint
     IRIS_KEEP_DEVICE();
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_MASKS || e->kind == IRIS_KIND_SHARES, "batch_process needs a masks or distance engine");
-    ARG(e->nq == 0, "a distance batch engine runs through iris_distance_batch_process");
+    ARG(e->nq == 0, "a batch engine runs through iris_distance_batch_process / iris_masks_batch_process");
     ARG(db->k.kind == e->kind, "engine kind does not match the database kind");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     iris_device *d = e->dev;
@@ -1263,7 +1263,7 @@ int iris_engine_batch_process_host(iris_engine_t *e, const void *records, uint64
     IRIS_KEEP_DEVICE();
     ARG(e, "engine is NULL");
     ARG(e->kind == IRIS_KIND_MASKS || e->kind == IRIS_KIND_SHARES, "batch_process needs a masks or distance engine");
-    ARG(e->nq == 0, "a distance batch engine runs through iris_distance_batch_process");
+    ARG(e->nq == 0, "a batch engine runs through iris_distance_batch_process / iris_masks_batch_process");
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
@@ -1823,6 +1823,184 @@ int iris_distance_batch_process(iris_engine_t *e, const iris_db_t *db, uint64_t 
     return 0;
 }
 
+// ------------------------------------------------------------------ batched MasksEngine
+
+// nq MasksEngines (src/lib.rs:55-67) at once: one single-query engine per query (its LANES table and
+// its TILES fragments, built by the same launch as iris_masks_engine_new's), run together.
+int iris_masks_batch_engine_new(iris_device_t *d, const uint64_t *query_masks, uint32_t nq, iris_engine_t **out) {
+    IRIS_KEEP_DEVICE();
+    ARG(nq > 0 && nq <= IRIS_MASKS_BATCH_MAX, "a masks batch holds 1..IRIS_MASKS_BATCH_MAX (64) queries");
+    ARG(d && query_masks && out, "NULL argument");
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    iris_engine *e = new (std::nothrow) iris_engine();
+    if (!e) return fail(IRIS_E_NOMEM, "out of host memory");
+    e->dev = d;
+    e->kind = IRIS_KIND_MASKS;
+    e->nq = nq;
+    for (uint32_t i = 0; i < nq; ++i) {
+        iris_engine *c = nullptr;
+        const int rc = engine_from_host_query(d, IRIS_KIND_MASKS, query_masks + (size_t)i * IRIS_LIMBS,
+                                              (size_t)kPlaneDwords * kSlotTabStride * 4, kMaskFragBytes, &c,
+                                              launch_query_masks);
+        if (rc != 0) {
+            engine_free(e);
+            return rc;
+        }
+        e->sub.push_back(c);
+    }
+    device_retain(d);
+    *out = e;
+    return 0;
+}
+
+static int masks_batch_args(iris_engine_t *e, const iris_db_t *db) {
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_MASKS && e->nq > 0, "not a masks batch engine (iris_masks_batch_engine_new)");
+    ARG(db->k.kind == IRIS_KIND_MASKS, "a masks batch engine needs a masks database");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    return 0;
+}
+
+// Enqueues the batch over [first, first + n): query q's rows to the device array o + q * n * 31.
+// TILES ranges the batch kernel runs (masks_batch_runs): groups of kMasksBatchG queries per pass
+// ("masks_batch"), two or three left-over queries a pass of their own, a single one the single-query
+// kernel ("masks").  Other TILES ranges and LANES: one single-query pass per query ("masks").
+static int enqueue_masks_batch(iris_engine *e, const iris_db *db, uint64_t first, uint64_t n, uint16_t *o) {
+    iris_device *d = e->dev;
+    const LaunchRange r{first, n};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const bool batch = tiles && masks_batch_runs(d->hooks, r);
+    const uint64_t slab = n * (uint64_t)kRot;
+    for (uint32_t q0 = 0; q0 < e->nq;) {
+        const uint32_t m = batch ? std::min<uint32_t>(e->nq - q0, kMasksBatchG) : 1;
+        if (m == 1) {
+            CHK(enqueue_u16_engine(e->sub[q0], db, first, n, o + q0 * slab));
+        } else {
+            const void *frags[kMasksBatchG];
+            for (uint32_t s = 0; s < m; ++s) frags[s] = e->sub[q0 + s]->qfrag;
+            CHK(timed(d, "masks_batch", n * m, [&] {
+                return launch_masks_batch(d->hooks, d->stream, db->data, frags, m, r, o + q0 * slab, nullptr);
+            }));
+        }
+        q0 += m;
+    }
+    return 0;
+}
+
+int iris_masks_batch_process_device(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                    uint16_t *out_device) {
+    IRIS_KEEP_DEVICE();
+    CHK(masks_batch_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (n == 0) return 0;
+    ARG(out_device, "out is NULL");
+    CHK(enqueue_masks_batch(e, db, first, n, out_device));
+    return sync(d);
+}
+
+int iris_masks_batch_process(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint16_t *out) {
+    IRIS_KEEP_DEVICE();
+    CHK(masks_batch_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (n == 0) return 0;
+    ARG(out, "out is NULL");
+    // as iris_distance_batch_process: chunks of records whose nq slabs fit the device's row buffer
+    const uint64_t ch = std::min<uint64_t>(n, kU16Chunk / e->nq / 32 * 32);  // whole tiles
+    CHK(ensure(d, d->out_a, ch * e->nq * kRot * 2));
+    for (uint64_t done = 0; done < n; done += ch) {
+        const uint64_t m = std::min<uint64_t>(ch, n - done);
+        uint16_t *o = (uint16_t *)d->out_a.p;
+        CHK(enqueue_masks_batch(e, db, first + done, m, o));
+        for (uint32_t q = 0; q < e->nq; ++q)
+            HIPCHK(hipMemcpyAsync(out + ((uint64_t)q * n + done) * kRot, o + (uint64_t)q * m * kRot, m * kRot * 2,
+                                  hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+    }
+    return 0;
+}
+
+// The fused resolver step (iris_resolver_search_masks) for every query of a masks batch engine in
+// one pass over the masks: shares_device[p] holds nq slabs of n rows (what
+// iris_distance_batch_process_device wrote for participant p).  Every query's partials get a run
+// of their own, each run is reduced into its slot of the pinned result, and the call waits once.
+int iris_resolver_batch_search_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                     const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                     double *dist_out_device, iris_match_t *out) {
+    IRIS_KEEP_DEVICE();
+    ARG(out, "NULL argument");
+    CHK(masks_batch_args(e, db));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(n == 0 || shares_device, "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    if (n == 0) {
+        for (uint32_t q = 0; q < nq; ++q) match_from(Partial{}, false, index_base, &out[q]);
+        return 0;
+    }
+    const LaunchRange r{first, n};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const bool batch = tiles && masks_batch_runs(d->hooks, r);
+    const uint64_t slab = n * (uint64_t)kRot;
+    // partials: one run of `stride` per query (LANES: the resolver kernel's)
+    const uint32_t stride = !tiles ? resolver_partials(n)
+                                   : std::max(masks_resolve_partials(d->hooks, r), batch ? masks_batch_partials(d->hooks, r) : 0u);
+    CHK(ensure(d, d->partials, (size_t)nq * stride * sizeof(Partial)));
+    CHK(ensure_host_result(d, (size_t)nq * sizeof(Partial)));
+    if (!tiles) CHK(ensure(d, d->out_a, n * kRot * 2));
+    Partial *parts_dev = (Partial *)d->partials.p, *res = (Partial *)d->host_result;
+    auto reduce = [&](uint32_t q, uint32_t np) {
+        return timed(d, "reduce", np, [&] { return launch_reduce(d->stream, parts_dev + (size_t)q * stride, np, res + q); });
+    };
+    for (uint32_t q0 = 0; q0 < nq;) {
+        const uint32_t m = batch ? std::min<uint32_t>(nq - q0, kMasksBatchG) : 1;
+        if (m > 1) {
+            const void *frags[kMasksBatchG];
+            for (uint32_t s = 0; s < m; ++s) frags[s] = e->sub[q0 + s]->qfrag;
+            const MasksBatchResolve rs{shares_device, parts, q0, dist_out_device, parts_dev + (size_t)q0 * stride, stride};
+            uint32_t np = 0;
+            CHK(timed(d, "masks_batch_resolve", n * m, [&] {
+                return launch_masks_batch(d->hooks, d->stream, db->data, frags, m, r, nullptr, &rs, &np);
+            }));
+            for (uint32_t s = 0; s < m; ++s) CHK(reduce(q0 + s, np));
+            q0 += m;
+            continue;
+        }
+        // one query through the single-query forms, on its slab of every part
+        const uint16_t *sl[8];
+        for (uint32_t p = 0; p < parts; ++p) sl[p] = shares_device[p] + q0 * slab;
+        double *dist = dist_out_device ? dist_out_device + (uint64_t)q0 * n : nullptr;
+        Partial *pq = parts_dev + (size_t)q0 * stride;
+        iris_engine *c = e->sub[q0];
+        if (tiles) {
+            CHK(timed(d, "masks_resolve", n, [&] {
+                return launch_masks_resolve(d->hooks, d->stream, db->data, c->qfrag, r, sl, parts, dist, pq);
+            }));
+            CHK(reduce(q0, masks_resolve_partials(d->hooks, r)));
+        } else {
+            CHK(timed(d, "masks", n, [&] { return launch_masks(d->stream, db->data, c->qtab, r, (uint16_t *)d->out_a.p); }));
+            CHK(timed(d, "resolver", n, [&] {
+                return launch_resolver(d->stream, sl, parts, (const uint16_t *)d->out_a.p, n, dist, pq);
+            }));
+            CHK(reduce(q0, resolver_partials(n)));
+        }
+        q0 += 1;
+    }
+    CHK(sync(d));
+    for (uint32_t q = 0; q < nq; ++q) match_from(res[q], true, index_base, &out[q]);
+    return 0;
+}
+
 // ------------------------------------------------------------------ resolver
 
 static int resolver_finish(iris_device *d, uint32_t np, Partial *res) {
@@ -1869,6 +2047,7 @@ int iris_resolver_search_masks(iris_engine_t *e, const iris_db_t *db, uint64_t f
     ARG(e && db && out, "NULL argument");
     ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
     ARG(e->kind == IRIS_KIND_MASKS && db->k.kind == IRIS_KIND_MASKS, "needs a masks engine and a masks database");
+    ARG(e->nq == 0, "a masks batch engine runs through iris_resolver_batch_search_masks");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     ARG(n == 0 || shares_device, "NULL argument");
     for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
@@ -1915,6 +2094,7 @@ int iris_resolver_search_masks_host(iris_engine_t *e, const iris_db_t *db, uint6
     ARG(e && db && out, "NULL argument");
     ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
     ARG(e->kind == IRIS_KIND_MASKS && db->k.kind == IRIS_KIND_MASKS, "needs a masks engine and a masks database");
+    ARG(e->nq == 0, "a masks batch engine runs through iris_resolver_batch_search_masks");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     ARG(n == 0 || shares, "NULL argument");
     for (uint32_t p = 0; n && p < parts; ++p) ARG(shares[p], "NULL share array");
@@ -2244,7 +2424,7 @@ int iris_query_table_sizes(int kind, uint32_t nq, size_t *tab_bytes, size_t *fra
 int iris_engine_query_tables(const iris_engine_t *e, void *tab, size_t tab_bytes, void *frag, size_t frag_bytes) {
     IRIS_KEEP_DEVICE();
     ARG(e, "engine is NULL");
-    ARG(e->sub.empty(), "a streamed template batch (<= 3 queries) or distance batch engine holds one engine per query");
+    ARG(e->sub.empty(), "a streamed template batch (<= 3 queries), distance batch or masks batch engine holds one engine per query");
     size_t tb = 0, fb = 0;
     CHK(iris_query_table_sizes(e->kind, e->nq, &tb, &fb));
     ARG(tab_bytes == tb && frag_bytes == fb, "table sizes do not match the engine's layout");

@@ -297,6 +297,24 @@ int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void 
 // sig: as launch_shares_mfma's, armed when the last launch signals.
 int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t nq,
                         LaunchRange r, uint16_t *out, DoneSignal *sig = nullptr);
+// Several MasksEngine queries in one pass over a TILES masks database (iris_masks_batch.hip).
+constexpr int kMasksBatchG = 4;  // queries per pass
+// The fused resolver step of a pass: shares[p] = participant p's query-major device array (nq slabs of
+// r.n * 31 u16), q0 = the pass's first query (its slab), dist_out = NULL or nq * r.n doubles
+// (query-major); query q0 + s writes masks_batch_partials() partials at partials + s * stride.
+struct MasksBatchResolve {
+    const uint16_t *const *shares;
+    uint32_t parts;
+    uint32_t q0;
+    double *dist_out;
+    Partial *partials;
+    uint32_t stride;
+};
+bool masks_batch_runs(const Hooks &h, LaunchRange r);  // whether a range runs the batch kernel (else single-query launches)
+uint32_t masks_batch_partials(const Hooks &h, LaunchRange r);  // upper bound of a query's partials
+// m = 2..kMasksBatchG queries; rs == NULL: rows of query s to out + s * r.n * 31; *np: partials written per query
+int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
+                       uint16_t *out, const MasksBatchResolve *rs, uint32_t *np = nullptr);
 int launch_template_search(void *stream, const void *db, const void *qtab, LaunchRange r, double *dist_out,
                            Partial *partials, uint32_t *n_partials);
 // consumes partials; the winner's idx (range-relative) is offset by idx_base

@@ -1,0 +1,369 @@
+// iris_masks_batch.hip — several MasksEngine queries in one pass over a TILES masks database.
+//
+// MasksEngine::batch_process (src/lib.rs:69-79) for G queries at once: out[q][t][k] =
+// popcount(rot_k(qm_q) & m_t), with the fp4 arithmetic of masks_mfma_kernel (iris_engines_mfma.hip):
+// one v_mfma_scale_f32_32x32x64_f8f6f4 per 64-bit chunk, 32 rotation rows x 32 masks, 200 chunks,
+// every intermediate an exact integer <= 12 800 in f32.  A single-query pass is bound by the 1600 B
+// it reads per record while the matrix cores idle; here a wave expands each 16-B load of a mask
+// tile into the four B operands once and issues them against the A operands of G queries, so G
+// queries cost one read of the database.  The resolve form decodes, per query, the participants'
+// summed share rows of that query's slab against the denominators still in the accumulators
+// (the resolver step of src/main.rs:510-519 + 597-621) and keeps one running best per query.
+//
+// The query side: each wave reads the G queries' compact words (16 B per lane, step and query)
+// from L2, as masks_mfma_kernel<MASKS_RESOLVE> does for its one query; a query's fragments are
+// 51 KB, so G of them do not fit in LDS beside the output staging.  (Sharing each step's words among
+// the workgroup's waves through a two-slot LDS ring, one barrier per step, measured slower: 6.31
+// against 6.06 ms for 4 queries over 10M masks, profiles/r08_masks_batch.txt.)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "iris_device.hpp"
+
+namespace iris {
+
+namespace {
+
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTile = 32;
+constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
+
+enum { BATCH_OUT = 0, BATCH_RESOLVE = 1 };
+
+__device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
+    const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ uint4 load16(const uint4 *p) {
+    const u32x4 v = *(const u32x4 *)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ v16f mfma_fp4(const v8i &a, const v8i &b, const v16f &c) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 127, 0, 127);
+}
+
+// the A operand of a compact query word and the B operand of a mask tile dword (kMaskFragUint4,
+// kMaskTileUint4 in iris_internal.hpp): the expansions of masks_mfma_kernel
+__device__ __forceinline__ v8i mask_a(uint32_t w) {
+    return v8i{(int)(w & 0x44444444u), (int)(w & 0x22222222u), (int)(w & 0x11111111u), (int)((w >> 3) & 0x11111111u),
+               0, 0, 0, 0};
+}
+__device__ __forceinline__ v8i mask_b(uint32_t x) {
+    return v8i{(int)(x & 0x11111111u), (int)(x & 0x22222222u), (int)(x & 0x44444444u), (int)((x >> 1) & 0x44444444u),
+               0, 0, 0, 0};
+}
+
+__device__ __forceinline__ uint32_t dword_of(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
+
+// The G query slots of one launch.  Slots valid .. G-1 repeat slot 0's fragments and are never
+// stored or resolved.
+template <int G>
+struct MaskBatchArgs {
+    const uint4 *frag[G];
+    int valid;
+    // BATCH_OUT: the slot's [n][31] u16 slab
+    uint16_t *out[G];
+    // BATCH_RESOLVE: the participants' query-major arrays; slot g's slab starts slab[g] elements in
+    const uint16_t *shares[8];
+    uint64_t slab[G];
+    double *dist[G];        // the slot's n doubles, or all NULL
+    Partial *partials[G];   // the slot's run of gridDim.x partials
+    uint32_t parts;
+    uint32_t aligned;       // bit g: slab g of every part starts 16-B aligned
+};
+
+}  // namespace
+
+// Persistent, the shape of masks_mfma_kernel: each wave walks the tile groups wave, wave + nwaves, ...
+// of T tiles as one flat stream of (group, step) K-steps through register stages, so the next
+// group's loads are in flight while the current group's G x T tiles are written out.
+template <int G, int T, int MODE>
+__global__ void __launch_bounds__(256, 2)
+    masks_batch_kernel(const uint4 *__restrict__ db, MaskBatchArgs<G> a, uint64_t tile0, uint64_t ntiles, uint64_t first,
+                       uint64_t end) {
+    __shared__ __attribute__((aligned(16))) uint16_t sh_out[kWaveSlots][1024];
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaveSlots + (threadIdx.x >> 6));
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWaveSlots;
+    const uint64_t ngroups = (ntiles + T - 1) / T;
+    if (MODE != BATCH_RESOLVE && wave >= ngroups) return;
+    const uint32_t total = wave < ngroups ? (uint32_t)((ngroups - wave + nwaves - 1) / nwaves) * kSteps : 0;
+    uint16_t *lds = sh_out[threadIdx.x >> 6];
+    Partial best[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) best[g] = partial_none();
+
+    v16f acc[G][T];
+    auto zero = [&] {
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[g][t][i] = 0.f;
+    };
+    // resolver epilogue of one tile (records t0 .. t0+31 of the database) for slot g: resolve_tile of
+    // masks_mfma_kernel, with the slot's slab of every share array; alignment is the slab's own
+    auto resolve_tile = [&](int g, uint64_t t0, bool tv, const v16f &den, Partial &bq) {
+        const bool full = tv && t0 >= first && t0 + 32 <= end && ((t0 - first) & 7) == 0 && ((a.aligned >> g) & 1u);
+        const uint64_t s0 = a.slab[g];
+        const uint64_t e0 = s0 + (t0 - first) * kRot;  // first share element of the tile (when full)
+        if (full) {  // wave-uniform: 124 16-B words per share array
+            typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+            for (int i = lane; i < 32 * kRot / 8; i += 64) {
+                u16x8 v = *(const u16x8 *)(a.shares[0] + e0 + 8 * i);
+                for (uint32_t p = 1; p < a.parts; ++p) v += *(const u16x8 *)(a.shares[p] + e0 + 8 * i);
+                *(u16x8 *)&lds[8 * i] = v;
+            }
+        } else {
+            for (int i = lane; i < 32 * kRot; i += 64) {
+                const uint64_t tg = t0 + (uint64_t)(i / kRot);
+                uint16_t v = 0;
+                if (tv && tg >= first && tg < end) {
+                    const uint64_t e = s0 + (tg - first) * kRot + (uint64_t)(i % kRot);
+                    for (uint32_t p = 0; p < a.parts; ++p) v = (uint16_t)(v + a.shares[p][e]);
+                }
+                lds[i] = v;
+            }
+        }
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed
+        __builtin_amdgcn_wave_barrier();
+        const int h = lane >> 5;
+        uint32_t bn, bd;
+        int br;
+        best_rotation(lane, [&](int r, uint32_t &u, uint32_t &d) {
+            const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
+            d = (uint32_t)den[r] & 0xFFFFu;  // the MasksEngine output value (u16)
+            u = k < kRot ? (uint32_t)((uint16_t)(d - lds[(lane & 31) * kRot + k]) >> 1) : 0;  // src/lib.rs:104
+        }, bn, bd, br);
+        const uint64_t tg = t0 + (lane & 31);
+        const bool valid = tv && tg >= first && tg < end;
+        if (valid && a.dist[g] && h == 0) a.dist[g][tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
+        Partial c;
+        c.num = bn;
+        c.den = valid ? bd : 0;
+        c.rot = br;
+        c.pad = 0;
+        c.idx = tg - first;
+        if (partial_better_dev(c, bq)) bq = c;
+        __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+    };
+    if (total) {
+        zero();
+        // the mask tiles (HBM) are loaded two steps ahead through three register stages, the query
+        // words (L2) one step ahead through two: 16 G registers fewer than three stages of both
+        struct StageD {
+            uint4 d[T];
+        };
+        struct StageW {
+            uint4 w[G];
+        };
+        auto load_d = [&](StageD &st, uint32_t s) {
+            s = s < total ? s : total - 1;
+            const uint32_t j = s / kSteps, c = s - j * kSteps;
+            const uint64_t tw = (wave + (uint64_t)j * nwaves) * T;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const uint64_t rel = (tw + t < ntiles) ? tw + t : ntiles - 1;
+                st.d[t] = nt_load16(db + (tile0 + rel) * (uint64_t)kMaskTileUint4 + c * 64 + lane);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto load_w = [&](StageW &st, uint32_t s) {
+            s = s < total ? s : total - 1;
+            const uint32_t c = s % kSteps;
+#pragma unroll
+            for (int g = 0; g < G; ++g) st.w[g] = load16(a.frag[g] + c * 64 + lane);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto compute = [&](const StageD &sd, const StageW &st, uint32_t s) {
+            if (s >= total) return;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                // the tile dwords' B operands, expanded once for the G queries
+                v8i b[T];
+#pragma unroll
+                for (int t = 0; t < T; ++t) b[t] = mask_b(dword_of(sd.d[t], c));
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const v8i av = mask_a(dword_of(st.w[g], c));
+#pragma unroll
+                    for (int t = 0; t < T; ++t) acc[g][t] = mfma_fp4(av, b[t], acc[g][t]);
+                }
+            }
+            const uint32_t j = s / kSteps;
+            if (s - j * kSteps == kSteps - 1) {  // group j done: write its rows / resolve it, per slot
+                const uint64_t tw = (wave + (uint64_t)j * nwaves) * T;
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    if (g < a.valid) {  // wave-uniform
+#pragma unroll
+                        for (int t = 0; t < T; ++t) {
+                            if constexpr (MODE == BATCH_OUT) {
+                                store_tile_rows(a.out[g], lds, (tile0 + tw + t) * kTile, first, end, tw + t < ntiles, lane,
+                                                [&](int r) { return (uint16_t)(uint32_t)acc[g][t][r]; });
+                                __builtin_amdgcn_wave_barrier();  // the LDS rows are read before the next tile's
+                            } else {
+                                resolve_tile(g, (tile0 + tw + t) * kTile, tw + t < ntiles, acc[g][t], best[g]);
+                            }
+                        }
+                    }
+                }
+                zero();
+            }
+        };
+        // step s: the query words of step s + 1 are requested first, then the tiles of step s + 2, so
+        // the wait for step s + 1's operands (vmcnt counts in order) leaves the tile loads in flight
+        StageD d0, d1, d2;
+        StageW w0, w1;
+        auto step = [&](const StageD &dcur, StageD &dfree, const StageW &wcur, StageW &wfree, uint32_t s) {
+            load_w(wfree, s + 1);
+            load_d(dfree, s + 2);
+            compute(dcur, wcur, s);
+        };
+        load_d(d0, 0);
+        load_d(d1, 1);
+        load_w(w0, 0);
+#pragma unroll 1
+        for (uint32_t s = 0; s < total; s += 6) {  // three tile stages x two query stages
+            step(d0, d2, w0, w1, s);
+            step(d1, d0, w1, w0, s + 1);
+            step(d2, d1, w0, w1, s + 2);
+            step(d0, d2, w1, w0, s + 3);
+            step(d1, d0, w0, w1, s + 4);
+            step(d2, d1, w1, w0, s + 5);
+        }
+    }
+    if constexpr (MODE == BATCH_RESOLVE) {
+        __shared__ Partial sh_best[G][kWaveSlots];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const Partial o = partial_shfl_xor(best[g], off);
+                if (partial_better_dev(o, best[g])) best[g] = o;
+            }
+            if (lane == 0) sh_best[g][threadIdx.x >> 6] = best[g];
+        }
+        __syncthreads();
+        if (threadIdx.x < G && (int)threadIdx.x < a.valid) {
+            const int g = threadIdx.x;
+            Partial b = sh_best[g][0];
+            for (int w = 1; w < kWaveSlots; ++w)
+                if (partial_better_dev(sh_best[g][w], b)) b = sh_best[g][w];
+            Partial *dst = a.partials[0];
+#pragma unroll
+            for (int i = 1; i < G; ++i)
+                if (g == i) dst = a.partials[i];
+            dst[blockIdx.x] = b;
+        }
+    }
+}
+
+namespace {
+
+// Tiles per wave, G x T = 8 (128 accumulators): 2 for four queries, 4 for two, or 1 where that
+// would leave fewer waves than the chip holds at two workgroups per CU (the rule of the
+// single-query kernels' tiles_per_wave); IRIS_TILES_PER_WAVE pins either for tests.  Measured on
+// one box, interleaved, 10M masks: two queries 3.60 ms at 4 tiles against 3.83 at 2 (resolve
+// form 4.17 against 4.42); the resolve form of four queries 7.40 ms at 2 tiles against 8.65 at 1.
+// VGPRs (no scratch in any instantiation): rows form 98 / 242 for two queries at 1 / 4 tiles,
+// 164 / 234 for four at 1 / 2; resolve form 122 / 256 and 192 / 256.
+template <int G>
+constexpr int batch_big_tiles() { return G == 2 ? 4 : 2; }
+constexpr uint64_t kMasksBatchSplitTiles = 1024;  // = kMasksSplitTiles (iris_engines_mfma.hip)
+
+int batch_tiles_per_wave(const Hooks &h, uint64_t ntiles, int big) {
+    if (h.tiles_per_wave) return h.tiles_per_wave == 1 ? 1 : big;
+    return ntiles / big < (uint64_t)resident_blocks(2) * kWaveSlots ? 1 : big;
+}
+
+struct BatchTiles {
+    uint64_t tile0, ntiles;
+    int tpw;
+    uint32_t grid;
+};
+
+// grid = min(ceil(ceil(ntiles / tpw) / 4), 2 workgroups per CU): past 2 x CUs x 4 x tpw tiles a wave
+// walks more than one tile group
+BatchTiles batch_tiles(const Hooks &h, LaunchRange r, int big) {
+    BatchTiles t;
+    t.tile0 = r.first / kTile;
+    t.ntiles = (r.first + r.n + kTile - 1) / kTile - t.tile0;
+    t.tpw = batch_tiles_per_wave(h, t.ntiles, big);
+    const uint64_t waves = (t.ntiles + t.tpw - 1) / t.tpw;
+    t.grid = (uint32_t)std::min<uint64_t>((waves + kWaveSlots - 1) / kWaveSlots, resident_blocks(2));
+    return t;
+}
+
+template <int G, int MODE>
+int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const BatchTiles &t, LaunchRange r) {
+    auto kern = t.tpw == 1 ? masks_batch_kernel<G, 1, MODE> : masks_batch_kernel<G, batch_big_tiles<G>(), MODE>;
+    hipLaunchKernelGGL(kern, dim3(t.grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)db, a, t.tile0, t.ntiles,
+                       r.first, r.first + r.n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <int G>
+int launch_slots(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
+                 uint16_t *out, const MasksBatchResolve *rs, uint32_t *np) {
+    const BatchTiles t = batch_tiles(h, r, batch_big_tiles<G>());
+    if (np) *np = t.grid;
+    const uint64_t slab = r.n * (uint64_t)kRot;
+    MaskBatchArgs<G> a{};
+    a.valid = (int)m;
+    for (uint32_t g = 0; g < (uint32_t)G; ++g) {
+        const uint32_t s = g < m ? g : 0;
+        a.frag[g] = (const uint4 *)qfrags[s];
+        if (!rs) {
+            a.out[g] = out + s * slab;
+            continue;
+        }
+        a.slab[g] = (rs->q0 + s) * slab;
+        a.dist[g] = rs->dist_out ? rs->dist_out + (rs->q0 + s) * r.n : nullptr;
+        a.partials[g] = rs->partials + (uint64_t)s * rs->stride;
+        bool al = true;
+        for (uint32_t p = 0; p < rs->parts; ++p) al &= ((uintptr_t)(rs->shares[p] + a.slab[g]) & 15) == 0;
+        a.aligned |= (al ? 1u : 0u) << g;
+    }
+    if (!rs) return launch_group<G, BATCH_OUT>(stream, db, a, t, r);
+    a.parts = rs->parts;
+    for (uint32_t p = 0; p < rs->parts; ++p) a.shares[p] = rs->shares[p];
+    return launch_group<G, BATCH_RESOLVE>(stream, db, a, t, r);
+}
+
+}  // namespace
+
+// Ranges the batch kernel runs: those past the single-query kernels' K-split threshold (kMasksSplitTiles;
+// the resolver's 20 000-record chunk is 625).  Below it a batch runs one single-query launch per
+// query through the K-split and fused resolve kernels: no K-split batch form is shipped.
+bool masks_batch_runs(const Hooks &h, LaunchRange r) {
+    if (r.n == 0) return false;
+    const uint64_t ntiles = (r.first + r.n + kTile - 1) / kTile - r.first / kTile;
+    return ntiles > kMasksBatchSplitTiles || h.tiles_per_wave != 0;  // the hook pins the batch kernel for tests
+}
+
+// the most partials per query a pass over r writes (the grid at one tile per wave)
+uint32_t masks_batch_partials(const Hooks &h, LaunchRange r) { return r.n ? batch_tiles(h, r, 1).grid : 0; }
+
+// m = 2 .. kMasksBatchG queries (qfrags[s]: a MasksEngine's compact fragments) over [r.first, r.first +
+// r.n) of a TILES masks database in one pass; two queries run the two-slot kernel, three the
+// four-slot one with an unused slot.  rs == NULL: query s's rows go to out + s * r.n * 31; otherwise
+// the fused resolver step, see MasksBatchResolve; *np = the partials each query's run then holds.
+int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
+                       uint16_t *out, const MasksBatchResolve *rs, uint32_t *np) {
+    if (np) *np = 0;
+    if (r.n == 0) return 0;
+    if (m < 2 || m > (uint32_t)kMasksBatchG) return -1;
+    if (rs && (rs->parts == 0 || rs->parts > 8)) return -1;
+    if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, out, rs, np);
+    return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, out, rs, np);
+}
+
+}  // namespace iris

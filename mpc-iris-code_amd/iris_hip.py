@@ -65,6 +65,7 @@ COLS, ROWS, BITS, LIMBS, ROTATIONS = 200, 64, 12800, 200, 31
 KIND_MASKS, KIND_SHARES, KIND_TEMPLATES = 1, 2, 3
 LAYOUT_DEFAULT, LAYOUT_LANES, LAYOUT_TILES = 0, 1, 2
 DISTANCE_BATCH_MAX = 64  # IRIS_DISTANCE_BATCH_MAX: queries of a DistanceBatchEngine
+MASKS_BATCH_MAX = 64  # IRIS_MASKS_BATCH_MAX: queries of a MasksBatchEngine
 _REC_DTYPE = {KIND_MASKS: (np.uint64, LIMBS), KIND_SHARES: (np.uint16, BITS), KIND_TEMPLATES: (np.uint64, 2 * LIMBS)}
 
 
@@ -165,6 +166,11 @@ def load_library(path=None):
             "iris_distance_batch_engine_new": ([P, P, ctypes.c_uint32, PP], ctypes.c_int),
             "iris_distance_batch_process": ([P, P, u64, u64, P], ctypes.c_int),
             "iris_distance_batch_process_device": ([P, P, u64, u64, P], ctypes.c_int),
+            "iris_masks_batch_engine_new": ([P, P, ctypes.c_uint32, PP], ctypes.c_int),
+            "iris_masks_batch_process": ([P, P, u64, u64, P], ctypes.c_int),
+            "iris_masks_batch_process_device": ([P, P, u64, u64, P], ctypes.c_int),
+            "iris_resolver_batch_search_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, P, ctypes.POINTER(Match)],
+                                                 ctypes.c_int),
             "iris_resolver_search": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, P,
                                       ctypes.POINTER(Match)], ctypes.c_int),
             "iris_resolver_search_host": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64,
@@ -241,6 +247,8 @@ def exported_symbols():
         "iris_group_db_load_file", "iris_group_template_search", "iris_group_template_search_async",
         "iris_group_pending_wait", "iris_group_template_batch_search",
         "iris_distance_batch_engine_new", "iris_distance_batch_process", "iris_distance_batch_process_device",
+        "iris_masks_batch_engine_new", "iris_masks_batch_process", "iris_masks_batch_process_device",
+        "iris_resolver_batch_search_masks",
     ]
 
 
@@ -1040,6 +1048,59 @@ class DistanceBatchEngine(_Engine):
                                                                int(out_device_ptr))
         if rc:
             _check(rc)
+
+
+class MasksBatchEngine(_Engine):
+    """nq MasksEngines at once (iris_masks_batch_engine_new): one pass over a masks database answers
+    every query; out[q] is what MasksEngine(masks[q]).batch_process writes, and resolve() is the
+    resolver step of every query against the participants' DistanceBatchEngine outputs."""
+
+    kind = KIND_MASKS
+
+    def __init__(self, device, masks):
+        self.device = device
+        q = _records(KIND_MASKS, masks)
+        self.nq = q.shape[0]
+        h = ctypes.c_void_p()
+        _check(load_library().iris_masks_batch_engine_new(device.handle, _ptr(q), self.nq, ctypes.byref(h)))
+        self.handle = h
+
+    def query_tables(self):
+        raise IrisError(-1, "a masks batch engine holds one MasksEngine's tables per query")
+
+    def batch_process(self, out, db, first=0, n=None):
+        """`db` is a masks Database (records [first, first+n)); `out` a C-contiguous [nq, n, 31]
+        uint16 array, filled in place: out[q, i, k] = dot_bool(rot(masks[q], k-15), db[first+i])."""
+        n = (len(db) - first) if n is None else n
+        if (not isinstance(out, np.ndarray) or out.dtype != np.uint16 or not out.flags.c_contiguous or out.ndim != 3
+                or out.shape[0] != self.nq or out.shape[2] != ROTATIONS):
+            raise IrisError(-1, f"out must be a C-contiguous [{self.nq}, n, 31] uint16 array")
+        if out.shape[1] != n:  # assert_eq!(out.len(), db.len()) (src/lib.rs:70), per query
+            raise IrisError(-1, f"assertion `out.len() == db.len()` failed: {out.shape[1]} != {n}")
+        _check(load_library().iris_masks_batch_process(self.handle, db.handle, int(first), int(n), _ptr(out)))
+        return out
+
+    def batch_process_device(self, db, out_device_ptr, first=0, n=None):
+        """Results stay on the GPU: out_device_ptr is a device array of nq*n*31 u16 (query-major)."""
+        n = (len(db) - first) if n is None else n
+        rc = load_library().iris_masks_batch_process_device(self.handle, db.handle, int(first), int(n),
+                                                            int(out_device_ptr))
+        if rc:
+            _check(rc)
+
+    def resolve(self, db, shares_device_ptrs, first=0, n=None, index_base=0, dist_out=None):
+        """The resolver step of every query in one pass over masks records [first, first+n):
+        shares_device_ptrs[p] is participant p's device array of nq*n*31 u16, query-major (what
+        DistanceBatchEngine.batch_process_device wrote over the same records); dist_out: None or
+        a device array of nq*n doubles (query-major).  -> list of nq Match."""
+        n = (len(db) - first) if n is None else n
+        ptrs = [int(p) for p in shares_device_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        out = (Match * self.nq)()
+        _check(load_library().iris_resolver_batch_search_masks(self.handle, db.handle, int(first), int(n), arr,
+                                                               len(ptrs), int(index_base),
+                                                               ctypes.c_void_p(dist_out or 0), out))
+        return list(out)
 
 
 # ====================================================================== device groups
