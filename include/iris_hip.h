@@ -128,7 +128,10 @@ int iris_device_memory(iris_device_t *dev, size_t *free_bytes, size_t *total_byt
 /* Kernel timing with HIP events recorded on the device stream around every
  * launch of the named kernel family ("template_search", "template_counts",
  * "masks", "shares", "shares_batch" (items = records x queries), "masks_batch" and
- * "masks_batch_resolve" (the same), ...).  Disabled by default. */
+ * "masks_batch_resolve" (the same), ...).  Disabled by default.  Beside the
+ * timed "shares_batch" entry of a call on a TILES database, "shares_batch_large",
+ * "shares_batch_split" and "shares_batch_single" count the passes it ran in each
+ * kernel form (launches = passes, items = their rows, no time of their own). */
 int iris_device_set_profiling(iris_device_t *dev, int enabled);
 int iris_device_kernel_stats(iris_device_t *dev, const char *kernel, uint64_t *launches,
                              double *total_ms, uint64_t *items);

@@ -1761,8 +1761,24 @@ static int enqueue_distance_batch(iris_engine *e, const iris_db *db, uint64_t fi
     if (db->k.layout == IRIS_LAYOUT_TILES) {
         const void *frags[IRIS_DISTANCE_BATCH_MAX];
         for (uint32_t q = 0; q < e->nq; ++q) frags[q] = e->sub[q]->qfrag;
-        return timed(d, "shares_batch", n * e->nq,
-                     [&] { return launch_shares_batch(d->hooks, d->stream, db->data, frags, e->nq, r, o, sig); });
+        SharesBatchForms forms;
+        CHK(timed(d, "shares_batch", n * e->nq, [&] {
+            return launch_shares_batch(d->hooks, d->stream, db->data, frags, e->nq, r, o, sig, &forms);
+        }));
+        if (d->profiling) {
+            // which kernel forms the call ran: launches = passes, items = their rows, no time of
+            // their own (the whole call is timed as "shares_batch")
+            auto count = [&](const char *name, uint32_t passes, uint32_t queries) {
+                if (!passes) return;
+                KStat &s = d->stats[name];
+                s.launches += passes;
+                s.items += n * queries;
+            };
+            count("shares_batch_large", forms.large, forms.large_queries);
+            count("shares_batch_split", forms.split, forms.split_queries);
+            count("shares_batch_single", forms.single, forms.single);
+        }
+        return 0;
     }
     for (uint32_t q = 0; q < e->nq; ++q)
         CHK(timed(d, "shares_batch", n,

@@ -295,8 +295,14 @@ int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void 
 // nq DistanceEngine queries in one pass over a TILES share database (iris_shares_batch.hip):
 // qfrags[q] = query q's fragments (as launch_shares_mfma's qfrag), rows of query q at out + q * r.n * 31.
 // sig: as launch_shares_mfma's, armed when the last launch signals.
+// forms (optional): the passes the call launched and the queries they held, by kernel form.
+struct SharesBatchForms {
+    uint32_t large = 0, large_queries = 0;    // shares_batch_kernel (passes of 2..4 queries)
+    uint32_t split = 0, split_queries = 0;    // shares_batch_split_kernel (full groups)
+    uint32_t single = 0;                      // launch_shares_mfma, one query each
+};
 int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t nq,
-                        LaunchRange r, uint16_t *out, DoneSignal *sig = nullptr);
+                        LaunchRange r, uint16_t *out, DoneSignal *sig = nullptr, SharesBatchForms *forms = nullptr);
 // Several MasksEngine queries in one pass over a TILES masks database (iris_masks_batch.hip).
 constexpr int kMasksBatchG = 4;  // queries per pass
 // The fused resolver step of a pass: shares[p] = participant p's query-major device array (nq slabs of

@@ -326,6 +326,8 @@ constexpr int kBatchSplitKS = 2;
 // threshold (kSharesSplitTiles): the large form starts one workgroup per 4 T = 4 tiles, at most two
 // rounds of its 2 workgroups per CU below it.  (T = 2 at one wave per SIMD, 256 accumulators in
 // AGPRs: the register allocator spilled ~315 VGPRs with 150 unused, so T = 1.)
+// IRIS_TILES_PER_WAVE (a test hook) pins the large form on ranges of any size, as it pins the
+// single-query and masks kernels' variants: T is 1, so both of its values select the same kernel.
 constexpr uint64_t kSharesBatchSplitTiles = 4096;
 
 // nq queries (qfrags[q]: a DistanceEngine's fragments) over [r.first, r.first + r.n) of a TILES share
@@ -336,19 +338,22 @@ constexpr uint64_t kSharesBatchSplitTiles = 4096;
 // left-over queries run single-query passes, so no nq is slower than the calls it replaces.
 // sig (optional): the completion word of a blocking device-output call, handed to the last launch
 // when that is a single-query launch that signals (launches of one stream run in order).
+// forms (optional): the passes launched, by kernel form.
 int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t nq,
-                        LaunchRange r, uint16_t *out, DoneSignal *sig) {
+                        LaunchRange r, uint16_t *out, DoneSignal *sig, SharesBatchForms *forms) {
     if (sig) sig->armed = false;
+    if (forms) *forms = SharesBatchForms{};
     if (r.n == 0 || nq == 0) return 0;
     const uint64_t t0 = r.first / kTile;
     const uint64_t ntiles = (r.first + r.n + kTile - 1) / kTile - t0;
     const uint64_t slab = r.n * (uint64_t)kRot;
-    const bool split = ntiles <= kSharesBatchSplitTiles;
+    const bool split = ntiles <= kSharesBatchSplitTiles && !h.tiles_per_wave;  // the hook pins the large form for tests
     for (uint32_t q0 = 0; q0 < nq;) {
         const uint32_t m = nq - q0 < (uint32_t)kBatchG ? nq - q0 : (uint32_t)kBatchG;
         if (m == 1 || (split && m < (uint32_t)kBatchG)) {
             const bool last = q0 + 1 == nq;
             if (launch_shares_mfma(h, stream, db, qfrags[q0], r, out + q0 * slab, last ? sig : nullptr) != 0) return -1;
+            if (forms) forms->single += 1;
             q0 += 1;
             continue;
         }
@@ -369,6 +374,10 @@ int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void
                                (const uint4 *)db, qs, t0, ntiles, r.first, r.first + r.n);
         }
         if (hipGetLastError() != hipSuccess) return -1;
+        if (forms) {
+            (split ? forms->split : forms->large) += 1;
+            (split ? forms->split_queries : forms->large_queries) += m;
+        }
         q0 += m;
     }
     return 0;
