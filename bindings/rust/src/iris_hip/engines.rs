@@ -21,6 +21,26 @@ use std::ptr;
 use super::{check, default_device, ffi, match_to_pair, Database, Device, Record, Result, ShardedDatabase};
 use crate::{Bits, EncodedBits, Template};
 
+/// Runs one `iris_*_matches` call: `call(out, cap, count)`.  `cap = None` returns every match (room
+/// for 1024 first, then once more with room for the reported count); `Some(0)` only counts.
+/// -> (the matches of lowest index as `(distance, index)`, ascending; the total count).
+fn collect_matches(
+    cap: Option<u64>,
+    mut call: impl FnMut(*mut ffi::IrisMatch, u64, *mut u64) -> i32,
+) -> Result<(Vec<(f64, usize)>, u64)> {
+    let mut room = cap.unwrap_or(1024);
+    let mut count = 0u64;
+    let mut buf = vec![ffi::IrisMatch::default(); room as usize];
+    check(call(if room == 0 { ptr::null_mut() } else { buf.as_mut_ptr() }, room, &mut count))?;
+    if cap.is_none() && count > room {
+        room = count;
+        buf = vec![ffi::IrisMatch::default(); room as usize];
+        check(call(buf.as_mut_ptr(), room, &mut count))?;
+    }
+    buf.truncate(count.min(room) as usize);
+    Ok((buf.iter().map(match_to_pair).collect(), count))
+}
+
 /// An engine handle plus the device it lives on (kept alive by the clone).
 struct Handle {
     raw: *mut ffi::IrisEngine,
@@ -178,6 +198,35 @@ impl MasksEngine {
             )
         })?;
         Ok(match_to_pair(&m))
+    }
+
+    /// Every record of that step whose decoded distance is below `threshold`
+    /// (iris_resolver_matches_masks; the threshold has no reference counterpart): indices are the
+    /// rows within the range.  -> (matches in ascending index order, total count).
+    pub fn matches(
+        &self,
+        masks: &Database,
+        first: u64,
+        n: u64,
+        shares_device: &[*const u16],
+        threshold: f64,
+        cap: Option<u64>,
+    ) -> Result<(Vec<(f64, usize)>, u64)> {
+        collect_matches(cap, |out, room, count| unsafe {
+            ffi::iris_resolver_matches_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                0,
+                threshold,
+                out,
+                room,
+                count,
+            )
+        })
     }
 
     /// The same step with the participants' replies still in host memory (`shares[p]` holds the
@@ -350,6 +399,23 @@ impl TemplateEngine {
             ffi::iris_template_search(self.h.raw, db.raw(), first, n, index_base, ptr::null_mut(), &mut m)
         })?;
         Ok(match_to_pair(&m))
+    }
+
+    /// Every record of [first, first + n) whose distance is below `threshold`, in one database
+    /// pass (iris_template_matches; the threshold has no reference counterpart); indices are
+    /// `index_base + first + i`.  -> (matches in ascending index order, total count).
+    pub fn matches(
+        &self,
+        db: &Database,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        cap: Option<u64>,
+    ) -> Result<(Vec<(f64, usize)>, u64)> {
+        collect_matches(cap, |out, room, count| unsafe {
+            ffi::iris_template_matches(self.h.raw, db.raw(), first, n, index_base, threshold, out, room, count)
+        })
     }
 
     /// Enqueues the search and returns at once (the engine may be dropped before the

@@ -323,6 +323,43 @@ extern "C" {
         dist_out_device: *mut f64,
         out: *mut IrisMatch,
     ) -> c_int;
+    // threshold matching: every record below a distance (no reference counterpart for the threshold)
+    pub fn iris_template_matches(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        out: *mut IrisMatch,
+        cap: u64,
+        count: *mut u64,
+    ) -> c_int;
+    pub fn iris_resolver_matches(
+        dev: *mut IrisDevice,
+        shares_device: *const *const u16,
+        parts: u32,
+        denoms_device: *const u16,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        out: *mut IrisMatch,
+        cap: u64,
+        count: *mut u64,
+    ) -> c_int;
+    pub fn iris_resolver_matches_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        threshold: f64,
+        out: *mut IrisMatch,
+        cap: u64,
+        count: *mut u64,
+    ) -> c_int;
     pub fn iris_resolver_search_masks_host(
         engine: *mut IrisEngine,
         masks_db: *const IrisDb,

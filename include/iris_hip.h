@@ -414,6 +414,51 @@ int iris_resolver_search_masks_host(iris_engine_t *engine, const iris_db_t *mask
 int iris_resolver_search_host(iris_device_t *dev, const uint16_t *const *shares, uint32_t parts,
                               const uint16_t *denoms, uint64_t n, uint64_t index_base, iris_match_t *out);
 
+/* ------------------------------------------------------ threshold matching
+ * Every record under a distance, in one database pass -- what a uniqueness check or an
+ * identification asks for.  The reference keeps only the single best record: its loops
+ * (src/template.rs:43-47 per record, src/main.rs:616-621 over records) fold a minimum, and the
+ * calls below generalise those loops from "the minimum" to "all below a threshold".  The
+ * threshold itself has no reference counterpart.
+ *
+ * A record matches iff distance < threshold, where distance is the f64 the sibling search call
+ * (iris_template_search, iris_resolver_search, iris_resolver_search_masks) would report if that
+ * record were the only one in the range: (double)num / (double)den of its best rotation (exact
+ * fraction minimum, lowest rotation on ties; decode_distance of the wrapping share sum,
+ * src/lib.rs:97-107, for the resolver forms).  The decision is that f64 comparison, bit for bit.
+ * A record without a valid rotation (every den == 0, distance +inf) never matches, not even for
+ * threshold = +inf.  threshold: any f64 but NaN (IRIS_E_ARG); <= 0 matches nothing, +inf every
+ * record with a valid rotation.
+ *
+ * out: host array of cap iris_match_t; *count (required) receives the number of matches in the
+ * range, which may exceed cap.  out receives the min(*count, cap) matches of lowest index, in
+ * ascending index order, each filled as the sibling search would (reserved = 0); entries past them
+ * are left untouched.  cap == 0 with out == NULL counts only.  n == 0 gives *count = 0.  The
+ * result is deterministic: identical calls return identical bytes.  Argument, engine-kind and
+ * range checks and locking are the sibling search's; a batch engine is refused.
+ *
+ * The library keeps a per-device match buffer (never more than n records) and does not guess its
+ * size: a pass that reports more matches than the buffer holds is run once more with the buffer
+ * grown to the reported count.
+ *
+ * Out of scope: the batch engines (template, distance and masks batch), the host-array forms
+ * (*_host), the asynchronous pipeline, and device groups (a variable-length exchange). */
+/* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
+ * index_base + first + i. */
+int iris_template_matches(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                          uint64_t index_base, double threshold,
+                          iris_match_t *out, uint64_t cap, uint64_t *count);
+/* iris_resolver_search's sibling (src/main.rs:597-621; the per-row minimum over rotations is
+ * decode_distance's, the template.rs:43-47 fold): DEVICE arrays of n*31 uint16_t; indices are index_base + i. */
+int iris_resolver_matches(iris_device_t *dev, const uint16_t *const *shares_device, uint32_t parts,
+                          const uint16_t *denoms_device, uint64_t n, uint64_t index_base, double threshold,
+                          iris_match_t *out, uint64_t cap, uint64_t *count);
+/* iris_resolver_search_masks' sibling (src/main.rs:510-519 + 597-621; rotations folded as in
+ * src/template.rs:43-47): indices are index_base + i, i the row within the range. */
+int iris_resolver_matches_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                double threshold, iris_match_t *out, uint64_t cap, uint64_t *count);
+
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):
  *   dot_bool(&[u64;200], &[u64;200]) -> u16   src/arch/generic.rs:4-9

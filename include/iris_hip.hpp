@@ -27,6 +27,7 @@
 #ifndef IRIS_HIP_HPP
 #define IRIS_HIP_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -50,6 +51,14 @@ constexpr std::size_t ROTATIONS = IRIS_ROTATIONS;    // 31 = -15..=15
 using Rotations = std::array<uint16_t, ROTATIONS>;   // [u16; 31]
 using Match = iris_match_t;
 
+// Result of a threshold-match call (iris_*_matches): the matches of lowest index in ascending index
+// order (all of them unless a cap was given) and the total number of matches in the range.
+struct Matches {
+    std::vector<Match> list;
+    uint64_t count = 0;
+};
+constexpr uint64_t kAllMatches = UINT64_MAX;  // cap: return every match
+
 class Error : public std::runtime_error {
 public:
     Error(int code, const std::string &msg) : std::runtime_error("iris_hip error " + std::to_string(code) + ": " + msg), code(code) {}
@@ -61,6 +70,26 @@ inline void check(int rc) {
 }
 
 // ------------------------------------------------------------------ device
+
+namespace detail {
+// call(out, cap, &count) -> rc.  cap = kAllMatches: room for 1024 first, then once more with room for
+// the reported count; cap = 0 only counts.
+template <class F>
+inline Matches collect_matches(uint64_t cap, F call) {
+    Matches m;
+    const bool all = cap == kAllMatches;
+    if (all) cap = 1024;
+    m.list.resize(cap);
+    check(call(cap ? m.list.data() : nullptr, cap, &m.count));
+    if (all && m.count > cap) {
+        cap = m.count;
+        m.list.resize(cap);
+        check(call(m.list.data(), cap, &m.count));
+    }
+    m.list.resize(std::min<uint64_t>(cap, m.count));
+    return m;
+}
+}  // namespace detail
 
 class Device {
 public:
@@ -512,6 +541,16 @@ public:
                                          index_base, nullptr, &m));
         return m;
     }
+    // Every record of that resolver step whose decoded distance is below `threshold`
+    // (iris_resolver_matches_masks; the threshold has no reference counterpart); indices are
+    // index_base + row.
+    Matches matches(const Database &db, const std::vector<const uint16_t *> &shares_device, double threshold,
+                    uint64_t first, uint64_t n, uint64_t index_base = 0, uint64_t cap = kAllMatches) const {
+        return detail::collect_matches(cap, [&](Match *out, uint64_t c, uint64_t *count) {
+            return iris_resolver_matches_masks(h_, db.handle(), first, n, shares_device.data(),
+                                               (uint32_t)shares_device.size(), index_base, threshold, out, c, count);
+        });
+    }
     // The same with the participants' outputs in host memory (the rows as they arrive): summed on
     // the host, the sum uploaded (iris_resolver_search_masks_host).
     Match resolve_host(const Database &db, const std::vector<const std::vector<Rotations> *> &shares, uint64_t first,
@@ -605,6 +644,14 @@ public:
         check(iris_template_search(h_, db.handle(), first, n, index_base, nullptr, &m));
         return m;
     }
+    // Every record whose distance is below `threshold`, in one database pass (iris_template_matches;
+    // the threshold has no reference counterpart); indices are index_base + first + i.
+    Matches matches(const Database &db, double threshold, uint64_t first, uint64_t n, uint64_t index_base = 0,
+                    uint64_t cap = kAllMatches) const {
+        return detail::collect_matches(cap, [&](Match *out, uint64_t c, uint64_t *count) {
+            return iris_template_matches(h_, db.handle(), first, n, index_base, threshold, out, c, count);
+        });
+    }
     // pipelined form: returns once the search is enqueued (the engine may be destroyed before the wait)
     PendingSearch search_async(const Database &db, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
         iris_pending_t *p = nullptr;
@@ -671,6 +718,17 @@ inline Match resolver_search(const std::vector<std::vector<Rotations>> &shares, 
 }
 
 // `prepare` (src/main.rs:333-361) on the device: shares of encode(templates[first..first+n))
+// Device-array form of the resolver's threshold matching (iris_resolver_matches): shares_device[p]
+// and denoms_device are device arrays of n * 31 u16; indices are index_base + row.
+inline Matches resolver_matches(Device &dev, const std::vector<const uint16_t *> &shares_device,
+                                const uint16_t *denoms_device, uint64_t n, double threshold, uint64_t index_base = 0,
+                                uint64_t cap = kAllMatches) {
+    return detail::collect_matches(cap, [&](Match *out, uint64_t c, uint64_t *count) {
+        return iris_resolver_matches(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
+                                     index_base, threshold, out, c, count);
+    });
+}
+
 inline void prepare_shares(const Database &templates, uint64_t first, uint64_t n, const std::array<uint8_t, 32> &key,
                            const std::vector<Database *> &shares, Database *masks = nullptr, uint64_t nonce = 0,
                            uint64_t index_base = 0, uint32_t rounds = 12) {

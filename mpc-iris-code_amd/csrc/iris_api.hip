@@ -651,7 +651,8 @@ void device_teardown(iris_device *d) {
         (void)hipSetDevice(d->ordinal);
         resident_drop_all(d);
         (void)hipStreamSynchronize(d->stream);
-        for (DevBuf *b : {&d->partials, &d->result, &d->staging, &d->out_a, &d->out_b, &d->ticket, &d->tempdb})
+        for (DevBuf *b : {&d->partials, &d->result, &d->staging, &d->out_a, &d->out_b, &d->ticket, &d->tempdb,
+                          &d->matches, &d->match_count})
             if (b->p) (void)hipFree(b->p);
         side_sync(d);
         for (int b = 0; b < 2; ++b) {
@@ -2094,6 +2095,135 @@ int iris_resolver_search_masks(iris_engine_t *e, const iris_db_t *db, uint64_t f
     }
     match_from(res, n > 0, index_base, out);
     return 0;
+}
+
+// ------------------------------------------------------------------ threshold matching
+
+// Records the first pass has room for when the caller's cap asks for fewer: a threshold that
+// matters matches a handful of records, so this covers every sparse list in one pass (24 KB).
+constexpr uint64_t kMatchFirstRoom = 1024;
+
+static int matches_args(double threshold, const iris_match_t *out, uint64_t cap, const uint64_t *count) {
+    ARG(threshold == threshold, "threshold is NaN");
+    ARG(count, "count is NULL");
+    ARG(cap == 0 || out, "out is NULL with cap > 0");
+    return 0;
+}
+
+// One threshold-match call over n records: `launch` enqueues the pass that appends every hit to the
+// sink it is given.  The counter is zeroed on the stream before each launch and always counts, so
+// a pass whose hits did not fit reports how many there are: the buffer grows to exactly that (at
+// most n records) and the pass runs once more.  The records are then sorted by index -- the append
+// order depends on which wave adds first -- and the min(count, cap) lowest become iris_match_t as
+// match_from fills them (idx + base).  cap == 0 needs no record, so never a second pass.
+static int matches_run(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
+                       uint64_t *count, const char *name, const std::function<int(const MatchSink &)> &launch) {
+    *count = 0;
+    if (n == 0) return 0;
+    CHK(ensure(d, d->match_count, sizeof(uint64_t)));
+    CHK(ensure_host_result(d, sizeof(uint64_t)));
+    uint64_t room = 0;
+    if (cap) {
+        room = std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom));
+        room = std::max<uint64_t>(room, std::min<uint64_t>(n, d->matches.cap / sizeof(Partial)));  // grown earlier
+    }
+    uint64_t total = 0;
+    for (int pass = 0;; ++pass) {
+        CHK(ensure(d, d->matches, room * sizeof(Partial)));
+        const MatchSink ms{(Partial *)d->matches.p, room, (uint64_t *)d->match_count.p, threshold};
+        HIPCHK(hipMemsetAsync(d->match_count.p, 0, sizeof(uint64_t), d->stream));
+        CHK(timed(d, name, n, [&] { return launch(ms); }));
+        HIPCHK(hipMemcpyAsync(d->host_result, d->match_count.p, sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+        memcpy(&total, d->host_result, sizeof(uint64_t));
+        if (total > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+        if (cap == 0 || total <= room) break;
+        if (pass == 1) return fail(IRIS_E_HIP, "match pass counts differ between two runs");
+        room = total;
+    }
+    *count = total;
+    const uint64_t take = std::min(total, cap);
+    if (take == 0) return 0;
+    std::vector<Partial> recs;
+    try {
+        recs.resize(total);
+    } catch (const std::bad_alloc &) {
+        return fail(IRIS_E_NOMEM, "out of host memory");
+    }
+    HIPCHK(hipMemcpyAsync(recs.data(), d->matches.p, total * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
+    CHK(sync(d));
+    const auto by_index = [](const Partial &a, const Partial &b) { return a.idx < b.idx; };
+    if (take < total) std::nth_element(recs.begin(), recs.begin() + take, recs.end(), by_index);
+    std::sort(recs.begin(), recs.begin() + take, by_index);
+    for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[i]);
+    return 0;
+}
+
+// iris_template_search's threshold sibling (header: "threshold matching")
+int iris_template_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                          double threshold, iris_match_t *out, uint64_t cap, uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, count));  // the value arguments first: refused whatever the handles
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    return matches_run(d, n, index_base + first, threshold, out, cap, count, "template_match", [&](const MatchSink &ms) {
+        return db->k.layout == IRIS_LAYOUT_TILES
+                   ? launch_template_mfma_match(d->hooks, d->stream, db->data, e->qfrag, r, ms)
+                   : launch_template_match(d->stream, db->data, e->qtab, r, ms);
+    });
+}
+
+// iris_resolver_search's threshold sibling
+int iris_resolver_matches(iris_device_t *d, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms,
+                          uint64_t n, uint64_t index_base, double threshold, iris_match_t *out, uint64_t cap,
+                          uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(d, "NULL argument");
+    ARG(n == 0 || (shares && denoms), "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares[p], "NULL share array");
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
+        return launch_resolver_match(d->stream, shares, parts, denoms, n, ms);
+    });
+}
+
+// iris_resolver_search_masks' threshold sibling: TILES runs the fused masks_mfma_kernel<MASKS_MATCH>;
+// LANES the masks kernel into a workspace and then the resolver match kernel.
+int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                double threshold, iris_match_t *out, uint64_t cap, uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_MASKS && db->k.kind == IRIS_KIND_MASKS, "needs a masks engine and a masks database");
+    ARG(e->nq == 0, "a masks batch engine has no threshold-match form");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    ARG(n == 0 || shares_device, "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    if (db->k.layout == IRIS_LAYOUT_TILES)
+        return matches_run(d, n, index_base, threshold, out, cap, count, "masks_match", [&](const MatchSink &ms) {
+            return launch_masks_match(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, ms);
+        });
+    if (n) {
+        CHK(ensure(d, d->out_a, n * kRot * 2));
+        CHK(timed(d, "masks", n, [&] { return launch_masks(d->stream, db->data, e->qtab, r, (uint16_t *)d->out_a.p); }));
+    }
+    return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
+        return launch_resolver_match(d->stream, shares_device, parts, (const uint16_t *)d->out_a.p, n, ms);
+    });
 }
 
 // The resolver step from host share arrays and the resident masks database (src/main.rs:510-519 +

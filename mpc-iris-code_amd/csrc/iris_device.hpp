@@ -223,6 +223,51 @@ __device__ __forceinline__ Partial partial_none() {
     return p;
 }
 
+// Threshold matching (MatchSink, iris_internal.hpp).  The decision is the f64 comparison the
+// caller would make on the search's own distance: one IEEE division per record, den = 0
+// (distance +inf) never matches, not even under threshold = +inf.
+__device__ __forceinline__ bool match_hit(const MatchSink &m, bool valid, uint32_t num, uint32_t den) {
+    return valid && den != 0 && (double)num / (double)den < m.threshold;
+}
+
+// Appends a wave's hits of T record groups (one candidate per lane and group; every lane of the
+// wave calls this): a ballot per group finds them, lane 0 reserves the wave's slots with ONE
+// agent-scope relaxed atomic add (none when the wave has no hit), and each hit whose slot lies
+// inside the buffer stores its record.  Slot order depends on which wave adds first; the host
+// sorts by index.
+template <int T>
+__device__ __forceinline__ void append_matches(const MatchSink &m, int lane, const bool (&hit)[T],
+                                               const uint32_t (&num)[T], const uint32_t (&den)[T], const int (&rot)[T],
+                                               const uint64_t (&idx)[T]) {
+    uint64_t mask[T];
+    uint32_t total = 0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        mask[t] = __ballot(hit[t]);
+        total += (uint32_t)__popcll(mask[t]);
+    }
+    if (total == 0) return;  // wave-uniform
+    uint64_t base = 0;
+    if (lane == 0) base = __hip_atomic_fetch_add(m.count, (uint64_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    const uint64_t below = (1ull << lane) - 1;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const uint64_t slot = base + (uint64_t)__popcll(mask[t] & below);
+        if (hit[t] && slot < m.cap) {
+            Partial p;
+            p.num = num[t];
+            p.den = den[t];
+            p.rot = rot[t];
+            p.pad = 0;
+            p.idx = idx[t];
+            m.buf[slot] = p;
+        }
+        base += (uint64_t)__popcll(mask[t]);
+    }
+}
+
 // Last-workgroup reduction (a search's partials reduce without a second launch).  Thread 0
 // publishes this workgroup's partial with agent-scope atomic stores (sc1: written through
 // past the XCD's L2, coherent across the XCDs without an L2 writeback / invalidate -- a full

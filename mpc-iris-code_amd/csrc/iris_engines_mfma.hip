@@ -35,8 +35,10 @@ constexpr int kTile = 32;
 // costs registers: 5.1 vs 2.7 ms)
 constexpr int kMasksTiles = 7;
 constexpr int kResolveTiles = 4;
+// MASKS_RESOLVE (1) and MASKS_MATCH (3) share the resolver step's shape
+constexpr bool masks_resolving(int mode) { return mode == 1 || mode == 3; }
 template <int MODE>
-constexpr int masks_tiles() { return MODE != 1 ? kMasksTiles : kResolveTiles; }
+constexpr int masks_tiles() { return !masks_resolving(MODE) ? kMasksTiles : kResolveTiles; }
 constexpr int kMasksBlocksPerCu = 2;  // persistent grid: workgroups per CU
 // MasksEngine stages the compact query (51 KB) in LDS per workgroup (two workgroups per CU); the
 // fused resolver (4 tiles per wave, 168 VGPRs) runs three workgroups per CU with the query read
@@ -45,7 +47,7 @@ constexpr int kMasksBlocksPerCu = 2;  // persistent grid: workgroups per CU
 // (2.90-3.01 vs 2.93-3.00 ms).
 constexpr int kResolveBlocksPerCu = 3;
 template <int MODE>
-constexpr int masks_blocks_per_cu() { return MODE != 1 ? kMasksBlocksPerCu : kResolveBlocksPerCu; }
+constexpr int masks_blocks_per_cu() { return !masks_resolving(MODE) ? kMasksBlocksPerCu : kResolveBlocksPerCu; }
 constexpr int kSharesTiles = 2;
 
 __device__ __forceinline__ uint4 nt_load(const uint4 *p) {
@@ -94,10 +96,13 @@ struct MaskResolve {
     bool aligned;  // every share array 16-B aligned
     double *dist_out;
     Partial *partials;
+    MatchSink match;  // MASKS_MATCH
 };
 
 // MASKS_PACKED: the [u16;31] rows in the read-ahead's packed form (store_tile_packed, iris_device.hpp)
-enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2 };
+// MASKS_MATCH: MASKS_RESOLVE's staging and decode; in place of the running best, the records below
+// rs.match.threshold are appended to rs.match (iris_resolver_matches_masks)
+enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3 };
 
 // Persistent: each wave walks the tile groups wave, wave + nwaves, ... as one
 // flat stream of (group, step) K-steps, so the loads of the next group are in
@@ -117,7 +122,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
                       uint64_t first, uint64_t end, uint16_t *__restrict__ out, MaskResolve rs) {
     constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
     const uint4 *sq = qfrag;  // the query's compact fragments: in LDS, or read from L2
-    if constexpr (MODE != MASKS_RESOLVE) {
+    if constexpr (!masks_resolving(MODE)) {
         __shared__ uint4 sq_lds[kMaskFragUint4];
         for (int i = threadIdx.x; i < (int)kMaskFragUint4; i += blockDim.x) sq_lds[i] = qfrag[i];
         __syncthreads();
@@ -129,7 +134,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
     const uint64_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaveSlots + (threadIdx.x >> 6));
     const uint64_t nwaves = (uint64_t)gridDim.x * kWaveSlots;
     const uint64_t ngroups = (ntiles + T - 1) / T;
-    if (MODE != MASKS_RESOLVE && wave >= ngroups) return;
+    if (!masks_resolving(MODE) && wave >= ngroups) return;
     const uint32_t total = wave < ngroups ? (uint32_t)((ngroups - wave + nwaves - 1) / nwaves) * kSteps : 0;
     uint16_t *lds = sh_out[threadIdx.x >> 6];
     Partial best = partial_none();
@@ -176,6 +181,15 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
         }, bn, bd, br);
         const uint64_t tg = t0 + (lane & 31);
         const bool valid = tv && tg >= first && tg < end;
+        if constexpr (MODE == MASKS_MATCH) {
+            const bool hit[1] = {match_hit(rs.match, valid && h == 0, bn, bd)};
+            const uint32_t hn[1] = {bn}, hd[1] = {bd};
+            const int hr[1] = {br};
+            const uint64_t hi[1] = {tg - first};
+            append_matches<1>(rs.match, lane, hit, hn, hd, hr, hi);
+            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+            return;
+        }
         if (valid && rs.dist_out && h == 0) rs.dist_out[tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
         Partial c;
         c.num = bn;
@@ -383,6 +397,29 @@ int launch_masks_resolve(const Hooks &h, void *stream, const void *db, const voi
     rs.dist_out = dist_out;
     rs.partials = partials;
     auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_RESOLVE, 1> : masks_mfma_kernel<MASKS_RESOLVE>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, rs);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// launch_masks_resolve's dispatch and grid with the MASKS_MATCH epilogue
+int launch_masks_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                       const uint16_t *const *shares, uint32_t parts, const MatchSink &ms) {
+    if (r.n == 0) return 0;
+    if (parts == 0 || parts > 8) return -1;
+    const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles);
+    const Tiles t = tiles_of(r, tpw);
+    const uint64_t grid = masks_resolve_partials(h, r);
+    MaskResolve rs{};
+    rs.aligned = true;
+    for (uint32_t p = 0; p < parts; ++p) {
+        rs.shares[p] = shares[p];
+        rs.aligned &= ((uintptr_t)shares[p] & 15) == 0;
+    }
+    rs.parts = parts;
+    rs.match = ms;
+    auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_MATCH, 1> : masks_mfma_kernel<MASKS_MATCH>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
                        (uint16_t *)nullptr, rs);

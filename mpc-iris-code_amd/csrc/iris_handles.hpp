@@ -102,6 +102,9 @@ struct iris_device {
     std::vector<hipEvent_t> event_pool;
     DevBuf partials, result, staging, out_a, out_b;
     DevBuf tempdb;  // the host-slice calls' transient database (TempDb, iris_api.hip)
+    // threshold matching (iris_*_matches): the hits' records and the 8-byte counter a pass appends
+    // through (iris::MatchSink); the counter is zeroed on the stream before every launch
+    DevBuf matches, match_count;
     // zeroed device word of the fused (last-workgroup) search reduce; searches on the stream
     // are serialised, and each launch leaves it zeroed
     DevBuf ticket;

@@ -148,6 +148,17 @@ struct Partial {
     uint64_t idx;   // template index relative to the searched range start
 };
 
+// Where a threshold-match pass appends its hits (iris_*_matches): every record whose best
+// fraction num / den, divided in f64, is below `threshold` takes the next slot of `count` and,
+// if that slot is inside `cap`, stores one Partial {num, den, rot, idx = range-relative index}
+// at buf[slot].  The counter always counts, so a short buffer still yields the exact total.
+struct MatchSink {
+    Partial *buf;
+    uint64_t cap;      // records buf holds
+    uint64_t *count;   // device counter, zeroed on the stream before the launch
+    double threshold;  // never NaN (the API refuses it)
+};
+
 // ---------------------------------------------------------------- generator
 // Counter-based synthetic data: limb = splitmix64 output number
 // ctr+1 of the stream keyed by (seed, stream).  Templates: stream 0, pattern
@@ -279,6 +290,15 @@ uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r);
 int launch_masks_resolve(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
                          const uint16_t *const *shares, uint32_t parts, double *dist_out, Partial *partials);
 uint32_t resolver_partials(uint64_t n);
+// Threshold-match passes (iris_*_matches): the sibling search's streaming loop and dispatch, with
+// the MatchSink append as epilogue (ms.count zeroed on the stream by the caller).
+int launch_template_mfma_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                               const MatchSink &ms);
+int launch_template_match(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ms);
+int launch_resolver_match(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                          const MatchSink &ms);
+int launch_masks_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                       const uint16_t *const *shares, uint32_t parts, const MatchSink &ms);
 struct BatchGeometry {
     uint64_t tile0, ntiles;
     uint32_t nqg, G;  // query groups, workgroups per query group

@@ -21,7 +21,7 @@
 // popcount sums nor hoist the 62 temporaries (it spills otherwise).
 #include <hip/hip_runtime.h>
 
-#include "iris_internal.hpp"
+#include "iris_device.hpp"
 
 namespace iris {
 
@@ -114,14 +114,15 @@ __device__ __forceinline__ Partial wave_best(Partial c) {
 
 // ------------------------------------------------------------------ template kernel
 
-enum { MODE_COUNTS = 0, MODE_SEARCH = 1 };
+// MODE_MATCH: the records below ms.threshold are appended to ms (iris_template_matches)
+enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2 };
 
 // Each wave: one 64-record block.  Workgroup: 4 waves.
 template <int MODE>
 __global__ void __launch_bounds__(256, 5)
     template_kernel(const uint4 *__restrict__ db, const uint32_t *__restrict__ qtab, uint64_t blk0, uint64_t nblk,
                     uint64_t first, uint64_t end, uint16_t *__restrict__ num_out, uint16_t *__restrict__ den_out,
-                    double *__restrict__ dist_out, Partial *__restrict__ partials) {
+                    double *__restrict__ dist_out, Partial *__restrict__ partials, MatchSink ms) {
     const int lane = threadIdx.x & 63;
     const int wslot = threadIdx.x >> 6;
     const uint64_t wave = (uint64_t)blockIdx.x * kWaveSlots + wslot;
@@ -186,6 +187,14 @@ __global__ void __launch_bounds__(256, 5)
             }
         }
         if (!valid) c.den = 0;
+        if constexpr (MODE == MODE_MATCH) {
+            const bool hit[1] = {match_hit(ms, valid, c.num, c.den)};
+            const uint32_t hn[1] = {c.num}, hd[1] = {c.den};
+            const int hr[1] = {c.rot};
+            const uint64_t hi[1] = {o};
+            append_matches<1>(ms, lane, hit, hn, hd, hr, hi);
+            return;
+        }
         if (valid && dist_out) dist_out[o] = c.den ? (double)c.num / (double)c.den : __builtin_inf();
 
         c = wave_best(c);
@@ -493,7 +502,7 @@ int launch_template_counts(void *stream, const void *db, const void *qtab, Launc
     const BlockRange b = block_range(r);
     hipLaunchKernelGGL(template_kernel<MODE_COUNTS>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n, num_out,
-                       den_out, (double *)nullptr, (Partial *)nullptr);
+                       den_out, (double *)nullptr, (Partial *)nullptr, MatchSink{});
     return check_launch();
 }
 
@@ -504,7 +513,16 @@ int launch_template_search(void *stream, const void *db, const void *qtab, Launc
     if (r.n == 0) return 0;
     hipLaunchKernelGGL(template_kernel<MODE_SEARCH>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials);
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials, MatchSink{});
+    return check_launch();
+}
+
+int launch_template_match(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ms) {
+    if (r.n == 0) return 0;
+    const BlockRange b = block_range(r);
+    hipLaunchKernelGGL(template_kernel<MODE_MATCH>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, ms);
     return check_launch();
 }
 

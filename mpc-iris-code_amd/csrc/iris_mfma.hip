@@ -73,7 +73,9 @@ __device__ __forceinline__ uint4 stream_load(const uint4 *p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-enum { MF_COUNTS = 0, MF_SEARCH = 1 };
+// MF_MATCH: every record of the range whose best rotation's f64 distance is below ms.threshold
+// is appended to ms (iris_template_matches); no partials, no reduce
+enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2 };
 
 // KS > 1 (small ranges, T = kSplitT): the KS waves of a tile group split K -- wave w computes
 // chunk groups [w' * 100 / KS, +100 / KS) of tiles T * (blockIdx.x * (4 / KS) + w / KS) + t (w' = w % KS)
@@ -86,7 +88,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     template_mfma_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, uint64_t tile0,
                          uint64_t ntiles, uint64_t first, uint64_t end, uint16_t *__restrict__ num_out,
                          uint16_t *__restrict__ den_out, double *__restrict__ dist_out,
-                         Partial *__restrict__ partials, FusedFinish fin) {
+                         Partial *__restrict__ partials, FusedFinish fin, MatchSink ms) {
     constexpr int W = kWaveSlots;
     static_assert(KS == 1 || (W % KS == 0 && kPlaneGroups % KS == 0), "K-split geometry");
     const int lane = threadIdx.x & 63;
@@ -202,6 +204,11 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     // k = (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 0..15.
     const int h = lane >> 5;
     Partial best = partial_none();
+    // MF_MATCH: the tiles' candidates (half 0 of the wave votes: both halves hold the record's best)
+    bool hit[T];
+    uint32_t hn[T], hd[T];
+    int hr[T];
+    uint64_t hi[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const uint64_t t0 = (tile0 + tw + t) * kTileRecs;  // global index of the tile's first template
@@ -225,6 +232,14 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                 dd = (uint32_t)den[t][r];
                 nn = (uint32_t)(((int)dd - (int)s[t][r]) >> 1);  // num = (den - S) / 2
             }, bn, bd, br);
+            if constexpr (MODE == MF_MATCH) {
+                hit[t] = match_hit(ms, valid && h == 0, bn, bd);
+                hn[t] = bn;
+                hd[t] = bd;
+                hr[t] = br;
+                hi[t] = o;
+                continue;
+            }
             if (valid && dist_out && h == 0) dist_out[o] = bd ? (double)bn / (double)bd : __builtin_inf();
             Partial c;
             c.num = bn;
@@ -235,6 +250,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
             if (partial_better_dev(c, best)) best = c;
         }
     }
+    if constexpr (MODE == MF_MATCH) append_matches<T>(ms, lane, hit, hn, hd, hr, hi);
     if constexpr (MODE == MF_SEARCH) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
@@ -555,7 +571,7 @@ int launch_template_mfma_counts(const Hooks &h, void *stream, const void *db, co
                 : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_COUNTS, 1> : template_mfma_kernel<MF_COUNTS>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, num_out,
-                       den_out, (double *)nullptr, (Partial *)nullptr, FusedFinish{});
+                       den_out, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, MatchSink{});
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -573,7 +589,21 @@ int launch_template_mfma_search(const Hooks &h, void *stream, const void *db, co
                          : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_SEARCH, 1> : template_mfma_kernel<MF_SEARCH>);
     hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials, fin ? *fin : FusedFinish{});
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials, fin ? *fin : FusedFinish{},
+                       MatchSink{});
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the search's dispatch (K-split form on small ranges, else one or four tiles per wave), MF_MATCH epilogue
+int launch_template_mfma_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                               const MatchSink &ms) {
+    if (r.n == 0) return 0;
+    const TileRange t = tile_range(h, r);
+    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_MATCH, kSplitT, 4>
+                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_MATCH, 1> : template_mfma_kernel<MF_MATCH>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, ms);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -49,9 +49,12 @@ __device__ __forceinline__ u16x8 load_word(const uint16_t *__restrict__ src, uin
 constexpr int kWords = kWaveRows * kRot * 2 / 16;  // 248
 constexpr int kSlots = (kWords + 63) / 64;         // 4
 
+// MATCH (iris_resolver_matches): the load and sum path is the search's; after the per-row decode
+// the rows below ms.threshold are appended to ms (idx = row) instead of the argmin.
+template <bool MATCH = false>
 __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uint16_t *__restrict__ denoms,
                                                        uint64_t n, double *__restrict__ dist_out,
-                                                       Partial *__restrict__ partials) {
+                                                       Partial *__restrict__ partials, MatchSink ms) {
     __shared__ __attribute__((aligned(16))) uint16_t sh_num[kWaveSlots][kWaveRows * kRot + 8];
     __shared__ __attribute__((aligned(16))) uint16_t sh_den[kWaveSlots][kWaveRows * kRot + 8];
     __shared__ Partial sh_best[kWaveSlots];
@@ -106,6 +109,14 @@ __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uin
         }
         if (dist_out) dist_out[row0 + lane] = c.den ? (double)c.num / (double)c.den : __builtin_inf();
     }
+    if constexpr (MATCH) {
+        const bool hit[1] = {match_hit(ms, (uint64_t)lane < rows, c.num, c.den)};
+        const uint32_t hn[1] = {c.num}, hd[1] = {c.den};
+        const int hr[1] = {c.rot};
+        const uint64_t hi[1] = {c.idx};
+        append_matches<1>(ms, lane, hit, hn, hd, hr, hi);
+        return;
+    }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const Partial o = partial_shfl_xor(c, off);
@@ -132,8 +143,20 @@ int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts,
     ResolverArgs a{};
     for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
     a.parts = parts;
-    hipLaunchKernelGGL(resolver_kernel, dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a, denoms, n,
-                       dist_out, partials);
+    hipLaunchKernelGGL(resolver_kernel<false>, dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a, denoms, n,
+                       dist_out, partials, MatchSink{});
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_resolver_match(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                          const MatchSink &ms) {
+    if (n == 0) return 0;
+    if (parts == 0 || parts > (uint32_t)kMaxParts) return -1;
+    ResolverArgs a{};
+    for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
+    a.parts = parts;
+    hipLaunchKernelGGL(resolver_kernel<true>, dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a, denoms, n,
+                       (double *)nullptr, (Partial *)nullptr, ms);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -182,6 +182,12 @@ def load_library(path=None):
             "iris_encode": ([P, P], ctypes.c_int),
             "iris_decode_distance": ([P, P, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
             "iris_match_merge": ([ctypes.POINTER(Match), u64, ctypes.POINTER(Match)], ctypes.c_int),
+            "iris_template_matches": ([P, P, u64, u64, u64, ctypes.c_double, ctypes.POINTER(Match), u64,
+                                       ctypes.POINTER(u64)], ctypes.c_int),
+            "iris_resolver_matches": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.c_double,
+                                       ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
+            "iris_resolver_matches_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_double,
+                                             ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
                                         ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
             "iris_engine_query_tables": ([P, P, ctypes.c_size_t, P, ctypes.c_size_t], ctypes.c_int),
@@ -249,6 +255,7 @@ def exported_symbols():
         "iris_distance_batch_engine_new", "iris_distance_batch_process", "iris_distance_batch_process_device",
         "iris_masks_batch_engine_new", "iris_masks_batch_process", "iris_masks_batch_process_device",
         "iris_resolver_batch_search_masks",
+        "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
     ]
 
 
@@ -322,6 +329,32 @@ def _c(a, dtype):
 
 
 # ====================================================================== value types
+
+
+def _collect_matches(call, cap, out, owner=None):
+    """Runs one iris_*_matches call -> (list[Match], count).  call(out_ptr, cap, count_ref) -> rc.
+    out: a (Match * cap) ctypes array filled in place (entries past the matches stay untouched), or
+    None.  cap=None asks for every match: a first call with room for 1024 -- or for a quarter more
+    than `owner`'s last such call reported, so a caller with a steady list length makes one call --
+    and one more with room for the reported count if there are more; cap=0 with out=None only counts."""
+    count = ctypes.c_uint64()
+    if out is not None:
+        cap = len(out) if cap is None else int(cap)
+        if cap > len(out):
+            raise IrisError(-1, "cap exceeds len(out)")
+        _check(call(out, cap, ctypes.byref(count)))
+        return [out[i] for i in range(min(cap, count.value))], count.value
+    want_all = cap is None
+    cap = max(1024, getattr(owner, "_match_room", 0)) if want_all else int(cap)
+    buf = (Match * cap)() if cap else None
+    _check(call(buf, cap, ctypes.byref(count)))
+    if want_all and count.value > cap:
+        cap = count.value
+        buf = (Match * cap)()
+        _check(call(buf, cap, ctypes.byref(count)))
+    if want_all and owner is not None:
+        owner._match_room = min(count.value + count.value // 4, 1 << 22)
+    return [buf[i] for i in range(min(cap, count.value))], count.value
 
 
 class Bits:
@@ -903,6 +936,38 @@ class MasksEngine(_Engine):
                 dev.free(p)
 
 
+    def matches(self, db, shares, threshold, first=0, n=None, index_base=0, cap=None, out=None):
+        """Every record of the resolver step whose decoded distance is below `threshold`
+        (iris_resolver_matches_masks; the threshold has no reference counterpart): shares = the
+        participants' [n,31] u16 outputs, host arrays (uploaded for the call) or device pointers.
+        Indices are index_base + row.  -> (list[Match] in ascending index order, count); cap / out
+        as in TemplateEngine.matches."""
+        if n is None:
+            n = len(db) - int(first)
+        dev = self.device
+        tmp = []
+        try:
+            ptrs = []
+            for a in shares:
+                if isinstance(a, int):
+                    ptrs.append(a)
+                    continue
+                a = _c(a, np.uint16)
+                if a.shape != (n, ROTATIONS):
+                    raise IrisError(-1, "shares must be [n, 31] uint16")
+                p = dev.alloc(max(a.nbytes, 16))
+                tmp.append(p)
+                dev.h2d(p, a)
+                ptrs.append(p)
+            arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+            f = load_library().iris_resolver_matches_masks
+            return _collect_matches(lambda o, c, cnt: f(self.handle, db.handle, int(first), int(n), arr, len(ptrs),
+                                                        int(index_base), float(threshold), o, c, cnt), cap, out, self)
+        finally:
+            for p in tmp:
+                dev.free(p)
+
+
 class DistanceEngine(_Engine):
     """DistanceEngine (src/lib.rs:28-53): out[k] = dot_u16(rot(query, k-15), entry)."""
 
@@ -967,6 +1032,18 @@ class TemplateEngine(_Engine):
         if rc:
             _check(rc)
         return m
+
+
+    def matches(self, db, threshold, first=0, n=None, index_base=0, cap=None, out=None):
+        """Every record whose distance is below `threshold`, in one database pass
+        (iris_template_matches; the threshold has no reference counterpart) -> (list[Match] in
+        ascending index order, count).  cap=None returns them all; with a cap the list holds the
+        min(count, cap) lowest indices and count is still the total; cap=0 only counts.  out: a
+        (Match * cap) ctypes array to fill in place."""
+        n = (len(db) - first) if n is None else n
+        f = load_library().iris_template_matches
+        return _collect_matches(lambda o, c, cnt: f(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                    float(threshold), o, c, cnt), cap, out, self)
 
 
 class PendingSearch:
@@ -1351,6 +1428,16 @@ def resolver_search_device(device, share_ptrs, denoms_ptr, n, index_base=0, dist
                                                int(index_base), ctypes.c_void_p(dist_out_device or 0),
                                                ctypes.byref(m)))
     return m
+
+
+def resolver_matches(device, share_ptrs, denoms_ptr, n, threshold, index_base=0, cap=None, out=None):
+    """Every row of the resolver's aggregation whose decoded distance is below `threshold`
+    (iris_resolver_matches; device arrays of n*31 u16; indices are index_base + row) ->
+    (list[Match] in ascending index order, count); cap / out as in TemplateEngine.matches."""
+    ptrs = (ctypes.c_void_p * len(share_ptrs))(*share_ptrs)
+    f = load_library().iris_resolver_matches
+    return _collect_matches(lambda o, c, cnt: f(device.handle, ptrs, len(share_ptrs), ctypes.c_void_p(denoms_ptr), int(n),
+                                                int(index_base), float(threshold), o, c, cnt), cap, out, device)
 
 
 # ====================================================================== arch plugin
