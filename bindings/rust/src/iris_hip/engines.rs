@@ -318,6 +318,57 @@ impl MasksBatchEngine {
         })?;
         Ok(m.iter().map(match_to_pair).collect())
     }
+
+    /// Every query's records of that step whose decoded distance is below `threshold`, in one
+    /// pass over the masks (iris_resolver_batch_matches_masks; the threshold has no reference
+    /// counterpart): entry q is what `MasksEngine::matches` gives for query q on slab q of every
+    /// part -- (matches in ascending index order, total count).  `cap` is per query; None asks
+    /// for every match (room for 1024 a query first, then once more for the longest list).
+    pub fn batch_matches(
+        &self,
+        masks: &Database,
+        first: u64,
+        n: u64,
+        shares_device: &[*const u16],
+        threshold: f64,
+        cap: Option<u64>,
+    ) -> Result<Vec<(Vec<(f64, usize)>, u64)>> {
+        let mut room = cap.unwrap_or(1024);
+        let mut counts = vec![0u64; self.nq];
+        let mut pass = 0;
+        let buf = loop {
+            let mut buf = vec![ffi::IrisMatch::default(); self.nq * room as usize];
+            check(unsafe {
+                ffi::iris_resolver_batch_matches_masks(
+                    self.h.raw,
+                    masks.raw(),
+                    first,
+                    n,
+                    shares_device.as_ptr(),
+                    shares_device.len() as u32,
+                    0,
+                    threshold,
+                    if room == 0 { ptr::null_mut() } else { buf.as_mut_ptr() },
+                    room,
+                    counts.as_mut_ptr(),
+                )
+            })?;
+            let longest = counts.iter().copied().max().unwrap_or(0);
+            if cap.is_some() || pass == 1 || longest <= room {
+                break buf;
+            }
+            room = longest;
+            pass += 1;
+        };
+        Ok(counts
+            .iter()
+            .enumerate()
+            .map(|(q, &c)| {
+                let list = &buf[q * room as usize..q * room as usize + c.min(room) as usize];
+                (list.iter().map(match_to_pair).collect(), c)
+            })
+            .collect())
+    }
 }
 
 /// `distances` (src/lib.rs:82-87).

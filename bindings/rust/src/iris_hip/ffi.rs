@@ -360,6 +360,19 @@ extern "C" {
         cap: u64,
         count: *mut u64,
     ) -> c_int;
+    pub fn iris_resolver_batch_matches_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        threshold: f64,
+        out: *mut IrisMatch,
+        cap: u64,
+        counts: *mut u64,
+    ) -> c_int;
     pub fn iris_resolver_search_masks_host(
         engine: *mut IrisEngine,
         masks_db: *const IrisDb,

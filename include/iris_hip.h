@@ -435,13 +435,15 @@ int iris_resolver_search_host(iris_device_t *dev, const uint16_t *const *shares,
  * ascending index order, each filled as the sibling search would (reserved = 0); entries past them
  * are left untouched.  cap == 0 with out == NULL counts only.  n == 0 gives *count = 0.  The
  * result is deterministic: identical calls return identical bytes.  Argument, engine-kind and
- * range checks and locking are the sibling search's; a batch engine is refused.
+ * range checks and locking are the sibling search's; a batch engine is refused (a masks batch
+ * engine has a form of its own, iris_resolver_batch_matches_masks below).
  *
  * The library keeps a per-device match buffer (never more than n records) and does not guess its
  * size: a pass that reports more matches than the buffer holds is run once more with the buffer
  * grown to the reported count.
  *
- * Out of scope: the batch engines (template, distance and masks batch), the host-array forms
+ * Out of scope: of the batch engines, the template and the distance batch engine (the masks batch
+ * engine, where the resolver decides, has iris_resolver_batch_matches_masks); the host-array forms
  * (*_host), the asynchronous pipeline, and device groups (a variable-length exchange). */
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
  * index_base + first + i. */
@@ -458,6 +460,34 @@ int iris_resolver_matches(iris_device_t *dev, const uint16_t *const *shares_devi
 int iris_resolver_matches_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
                                 const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
                                 double threshold, iris_match_t *out, uint64_t cap, uint64_t *count);
+/* iris_resolver_batch_search_masks' sibling, for a masks batch engine (iris_masks_batch_engine_new,
+ * nq = 1..64): the threshold lists of all nq queries in one pass over masks records
+ * [first, first+n) (src/main.rs:510-519 + 597-621 per query; rotations folded as in
+ * src/template.rs:43-47).  The inputs are iris_resolver_batch_search_masks': shares_device[p] is
+ * participant p's query-major DEVICE array of nq*n*31 uint16_t (parts = 1..8).  One threshold for
+ * the whole batch.
+ *
+ * counts (required): host array of nq uint64_t; counts[q] is the exact number of matches of query
+ * q in the range and may exceed cap.  out: host array of nq*cap iris_match_t, query-major;
+ * out[q*cap + j], j < min(counts[q], cap), are query q's matches of lowest index in ascending index
+ * order, each filled as iris_resolver_matches_masks fills it (index = index_base + row within the
+ * range, reserved = 0); entries past a query's list are left untouched.  cap == 0 with out == NULL
+ * counts only.  n == 0 sets every count to 0.
+ *
+ * Contract: query q's list and count are byte for byte what iris_resolver_matches_masks returns
+ * for MasksEngine(query_masks[q]) with slab q of every part.  The decision is the same f64
+ * comparison: a record whose every denominator is 0 never matches, not even under +inf;
+ * threshold <= 0 matches nothing; NaN is refused (IRIS_E_ARG).  Identical calls return identical
+ * bytes.  The value arguments (threshold, out / cap, counts, parts) are checked before the
+ * handles; engine, database and range checks are iris_resolver_batch_search_masks'.
+ *
+ * On TILES ranges the batch kernel runs (past 1024 tiles) the masks are read once per group of up
+ * to four queries; a query whose list does not fit its share of the device's match buffer has only
+ * its own group (elsewhere: the query alone) run once more, so no query reads the masks more than
+ * twice and the buffer never holds more than one group's records. */
+int iris_resolver_batch_matches_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                      const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                      double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

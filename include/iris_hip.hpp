@@ -596,6 +596,34 @@ public:
                                                (uint32_t)shares_device.size(), index_base, dist_out_device, m.data()));
         return m;
     }
+    // Every query's records of that step whose decoded distance is below `threshold`, in one pass
+    // over the masks (iris_resolver_batch_matches_masks; the threshold has no reference
+    // counterpart): result[q] is what MasksEngine(queries[q]).matches gives on slab q of every part;
+    // indices are index_base + row.  cap is per query; kAllMatches: room for 1024 a query first,
+    // then once more with room for the longest reported list.
+    std::vector<Matches> matches(const Database &db, const std::vector<const uint16_t *> &shares_device, uint64_t first,
+                                 uint64_t n, double threshold, uint64_t index_base = 0, uint64_t cap = kAllMatches) const {
+        const bool all = cap == kAllMatches;
+        if (all) cap = 1024;
+        std::vector<Match> flat;
+        std::vector<uint64_t> counts(nq_);
+        for (int pass = 0;; ++pass) {
+            flat.resize((size_t)nq_ * cap);
+            check(iris_resolver_batch_matches_masks(h_, db.handle(), first, n, shares_device.data(),
+                                                    (uint32_t)shares_device.size(), index_base, threshold,
+                                                    cap ? flat.data() : nullptr, cap, counts.data()));
+            const uint64_t longest = counts.empty() ? 0 : *std::max_element(counts.begin(), counts.end());
+            if (!all || pass || longest <= cap) break;
+            cap = longest;
+        }
+        std::vector<Matches> res(nq_);
+        for (uint32_t q = 0; q < nq_; ++q) {
+            res[q].count = counts[q];
+            const Match *src = flat.data() + (size_t)q * cap;
+            res[q].list.assign(src, src + std::min(counts[q], cap));
+        }
+        return res;
+    }
 
 private:
     uint32_t nq_ = 0;

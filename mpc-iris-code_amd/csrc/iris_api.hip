@@ -2110,53 +2110,103 @@ static int matches_args(double threshold, const iris_match_t *out, uint64_t cap,
     return 0;
 }
 
-// One threshold-match call over n records: `launch` enqueues the pass that appends every hit to the
-// sink it is given.  The counter is zeroed on the stream before each launch and always counts, so
-// a pass whose hits did not fit reports how many there are: the buffer grows to exactly that (at
-// most n records) and the pass runs once more.  The records are then sorted by index -- the append
-// order depends on which wave adds first -- and the min(count, cap) lowest become iris_match_t as
-// match_from fills them (idx + base).  cap == 0 needs no record, so never a second pass.
-static int matches_run(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
-                       uint64_t *count, const char *name, const std::function<int(const MatchSink &)> &launch) {
-    *count = 0;
+// One launch unit of a threshold-match call: queries q0 .. q0 + m - 1, whose hits one pass appends.
+// launch(sinks) enqueues that pass (timed under its own names); sinks[s] is query q0 + s's.
+struct MatchUnit {
+    uint32_t q0, m;
+    std::function<int(const MatchSink *)> launch;
+};
+
+// One threshold-match call of nq queries over n records each.  Every query has a counter of its
+// own (all zeroed on the stream before the first launch) and a region of `room` records of the
+// device's match buffer; every unit's first pass is enqueued before the one wait.  The counters
+// always count, so a query whose hits did not fit reports how many there are: its unit -- that
+// unit alone -- runs once more, its regions grown to exactly the reported counts (at most n
+// records a query), one unit at a time, its records copied back before the next unit runs.  A
+// query's records are then sorted by index -- the append order depends on which wave adds first --
+// and the min(count, cap) lowest become iris_match_t at out + q * cap as match_from fills them
+// (idx + base).  cap == 0 needs no record, so never a second pass.  reuse_grown (the single-query
+// calls): a buffer an earlier call grew is used in full by the first pass.
+static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
+                             uint64_t *counts, uint32_t nq, bool reuse_grown, const std::vector<MatchUnit> &units) {
+    for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
     if (n == 0) return 0;
-    CHK(ensure(d, d->match_count, sizeof(uint64_t)));
-    CHK(ensure_host_result(d, sizeof(uint64_t)));
+    CHK(ensure(d, d->match_count, nq * sizeof(uint64_t)));
+    CHK(ensure_host_result(d, nq * sizeof(uint64_t)));
     uint64_t room = 0;
     if (cap) {
         room = std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom));
-        room = std::max<uint64_t>(room, std::min<uint64_t>(n, d->matches.cap / sizeof(Partial)));  // grown earlier
+        if (reuse_grown) room = std::max<uint64_t>(room, std::min<uint64_t>(n, d->matches.cap / sizeof(Partial)));
     }
-    uint64_t total = 0;
-    for (int pass = 0;; ++pass) {
-        CHK(ensure(d, d->matches, room * sizeof(Partial)));
-        const MatchSink ms{(Partial *)d->matches.p, room, (uint64_t *)d->match_count.p, threshold};
-        HIPCHK(hipMemsetAsync(d->match_count.p, 0, sizeof(uint64_t), d->stream));
-        CHK(timed(d, name, n, [&] { return launch(ms); }));
-        HIPCHK(hipMemcpyAsync(d->host_result, d->match_count.p, sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
-        CHK(sync(d));
-        memcpy(&total, d->host_result, sizeof(uint64_t));
-        if (total > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
-        if (cap == 0 || total <= room) break;
-        if (pass == 1) return fail(IRIS_E_HIP, "match pass counts differ between two runs");
-        room = total;
+    CHK(ensure(d, d->matches, nq * room * sizeof(Partial)));
+    uint64_t *cnt = (uint64_t *)d->match_count.p;
+    HIPCHK(hipMemsetAsync(cnt, 0, nq * sizeof(uint64_t), d->stream));
+    MatchSink sinks[kMasksBatchG];
+    for (const MatchUnit &u : units) {
+        for (uint32_t s = 0; s < u.m; ++s)
+            sinks[s] = MatchSink{(Partial *)d->matches.p + (u.q0 + s) * room, room, cnt + u.q0 + s, threshold};
+        CHK(u.launch(sinks));
     }
-    *count = total;
-    const uint64_t take = std::min(total, cap);
-    if (take == 0) return 0;
-    std::vector<Partial> recs;
-    try {
-        recs.resize(total);
-    } catch (const std::bad_alloc &) {
-        return fail(IRIS_E_NOMEM, "out of host memory");
-    }
-    HIPCHK(hipMemcpyAsync(recs.data(), d->matches.p, total * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
     CHK(sync(d));
-    const auto by_index = [](const Partial &a, const Partial &b) { return a.idx < b.idx; };
-    if (take < total) std::nth_element(recs.begin(), recs.begin() + take, recs.end(), by_index);
-    std::sort(recs.begin(), recs.begin() + take, by_index);
-    for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[i]);
+    uint64_t total[IRIS_MASKS_BATCH_MAX];
+    memcpy(total, d->host_result, nq * sizeof(uint64_t));
+    for (uint32_t q = 0; q < nq; ++q)
+        if (total[q] > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+    // query q's total[q] records at src -> counts[q] and its list
+    std::vector<Partial> recs;
+    auto finish = [&](uint32_t q, const Partial *src) -> int {
+        counts[q] = total[q];
+        const uint64_t take = std::min(total[q], cap);
+        if (take == 0) return 0;
+        try {
+            recs.resize(total[q]);
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        HIPCHK(hipMemcpyAsync(recs.data(), src, total[q] * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+        const auto by_index = [](const Partial &a, const Partial &b) { return a.idx < b.idx; };
+        if (take < total[q]) std::nth_element(recs.begin(), recs.begin() + take, recs.end(), by_index);
+        std::sort(recs.begin(), recs.begin() + take, by_index);
+        for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[q * cap + i]);
+        return 0;
+    };
+    auto overflows = [&](const MatchUnit &u) {
+        for (uint32_t s = 0; cap && s < u.m; ++s)
+            if (total[u.q0 + s] > room) return true;
+        return false;
+    };
+    // the units whose lists fit first: a rerun below may replace the buffer their records are in
+    for (const MatchUnit &u : units) {
+        if (overflows(u)) continue;
+        for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + (u.q0 + s) * room));
+    }
+    for (const MatchUnit &u : units) {
+        if (!overflows(u)) continue;
+        uint64_t off[kMasksBatchG + 1] = {0};
+        for (uint32_t s = 0; s < u.m; ++s) off[s + 1] = off[s] + total[u.q0 + s];
+        CHK(ensure(d, d->matches, off[u.m] * sizeof(Partial)));
+        for (uint32_t s = 0; s < u.m; ++s)
+            sinks[s] = MatchSink{(Partial *)d->matches.p + off[s], total[u.q0 + s], cnt + u.q0 + s, threshold};
+        HIPCHK(hipMemsetAsync(cnt + u.q0, 0, u.m * sizeof(uint64_t), d->stream));
+        CHK(u.launch(sinks));
+        HIPCHK(hipMemcpyAsync(d->host_result, cnt + u.q0, u.m * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+        if (memcmp(d->host_result, total + u.q0, u.m * sizeof(uint64_t)) != 0)
+            return fail(IRIS_E_HIP, "match pass counts differ between two runs");
+        for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + off[s]));
+    }
     return 0;
+}
+
+// The single-query calls: one unit of one query, `launch` timed as `name`.
+static int matches_run(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
+                       uint64_t *count, const char *name, const std::function<int(const MatchSink &)> &launch) {
+    const std::vector<MatchUnit> unit{MatchUnit{0, 1, [&](const MatchSink *ms) {
+        return timed(d, name, n, [&] { return launch(ms[0]); });
+    }}};
+    return matches_run_units(d, n, base, threshold, out, cap, count, 1, true, unit);
 }
 
 // iris_template_search's threshold sibling (header: "threshold matching")
@@ -2204,7 +2254,7 @@ int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t 
     ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_MASKS && db->k.kind == IRIS_KIND_MASKS, "needs a masks engine and a masks database");
-    ARG(e->nq == 0, "a masks batch engine has no threshold-match form");
+    ARG(e->nq == 0, "a masks batch engine runs through iris_resolver_batch_matches_masks");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     ARG(n == 0 || shares_device, "NULL argument");
     for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
@@ -2224,6 +2274,63 @@ int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t 
     return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
         return launch_resolver_match(d->stream, shares_device, parts, (const uint16_t *)d->out_a.p, n, ms);
     });
+}
+
+// iris_resolver_batch_search_masks' threshold sibling, and that call's dispatch: TILES ranges the
+// batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass of
+// masks_batch_kernel<BATCH_MATCH> ("masks_batch_match") appending to the group's sinks, a single
+// left-over query one launch_masks_match; other TILES ranges one launch_masks_match per query; LANES
+// the masks kernel into the workspace and the resolver match kernel per query.  A launch unit -- a
+// group or a single query -- is what matches_run_units runs again when one of its lists overflows.
+int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                      const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                      double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, counts));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(masks_batch_args(e, db));
+    ARG(n == 0 || shares_device, "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    const LaunchRange r{first, n};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const bool batch = tiles && masks_batch_runs(d->hooks, r);
+    const uint64_t slab = n * (uint64_t)kRot;
+    if (n && !tiles) CHK(ensure(d, d->out_a, n * kRot * 2));
+    std::vector<MatchUnit> units;
+    for (uint32_t q0 = 0; n && q0 < nq;) {
+        const uint32_t m = batch ? std::min<uint32_t>(nq - q0, kMasksBatchG) : 1;
+        if (m > 1) {
+            units.push_back(MatchUnit{q0, m, [=](const MatchSink *ms) {
+                const void *frags[kMasksBatchG];
+                for (uint32_t s = 0; s < m; ++s) frags[s] = e->sub[q0 + s]->qfrag;
+                return timed(d, "masks_batch_match", n * m, [&] {
+                    return launch_masks_batch_match(d->hooks, d->stream, db->data, frags, m, r, shares_device, parts, q0, ms);
+                });
+            }});
+        } else {
+            // one query through the single-query forms, on its slab of every part
+            units.push_back(MatchUnit{q0, 1, [=](const MatchSink *ms) {
+                const uint16_t *sl[8];
+                for (uint32_t p = 0; p < parts; ++p) sl[p] = shares_device[p] + q0 * slab;
+                const iris_engine *c = e->sub[q0];
+                if (tiles)
+                    return timed(d, "masks_match", n, [&] {
+                        return launch_masks_match(d->hooks, d->stream, db->data, c->qfrag, r, sl, parts, ms[0]);
+                    });
+                CHK(timed(d, "masks", n, [&] { return launch_masks(d->stream, db->data, c->qtab, r, (uint16_t *)d->out_a.p); }));
+                return timed(d, "resolver_match", n, [&] {
+                    return launch_resolver_match(d->stream, sl, parts, (const uint16_t *)d->out_a.p, n, ms[0]);
+                });
+            }});
+        }
+        q0 += m;
+    }
+    return matches_run_units(d, n, index_base, threshold, out, cap, counts, nq, false, units);
 }
 
 // The resolver step from host share arrays and the resident masks database (src/main.rs:510-519 +

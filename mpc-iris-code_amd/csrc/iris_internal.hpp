@@ -341,6 +341,11 @@ uint32_t masks_batch_partials(const Hooks &h, LaunchRange r);  // upper bound of
 // m = 2..kMasksBatchG queries; rs == NULL: rows of query s to out + s * r.n * 31; *np: partials written per query
 int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
                        uint16_t *out, const MasksBatchResolve *rs, uint32_t *np = nullptr);
+// the threshold-match form of that pass: query s reads slab q0 + s of every part and appends to sinks[s]
+// (m sinks, each with its own buffer region and counter; counters zeroed on the stream by the caller)
+int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                             LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0,
+                             const MatchSink *sinks);
 int launch_template_search(void *stream, const void *db, const void *qtab, LaunchRange r, double *dist_out,
                            Partial *partials, uint32_t *n_partials);
 // consumes partials; the winner's idx (range-relative) is offset by idx_base

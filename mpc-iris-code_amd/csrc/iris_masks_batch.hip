@@ -9,6 +9,8 @@
 // queries cost one read of the database.  The resolve form decodes, per query, the participants'
 // summed share rows of that query's slab against the denominators still in the accumulators
 // (the resolver step of src/main.rs:510-519 + 597-621) and keeps one running best per query.
+// The match form decodes the same way and, in place of the running best, appends every record
+// below the threshold to the query's own MatchSink (iris_resolver_batch_matches_masks).
 //
 // The query side: each wave reads the G queries' compact words (16 B per lane, step and query)
 // from L2, as masks_mfma_kernel<MASKS_RESOLVE> does for its one query; a query's fragments are
@@ -32,7 +34,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTile = 32;
 constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
 
-enum { BATCH_OUT = 0, BATCH_RESOLVE = 1 };
+enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2 };
 
 __device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
     const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
@@ -69,13 +71,15 @@ struct MaskBatchArgs {
     int valid;
     // BATCH_OUT: the slot's [n][31] u16 slab
     uint16_t *out[G];
-    // BATCH_RESOLVE: the participants' query-major arrays; slot g's slab starts slab[g] elements in
+    // BATCH_RESOLVE, BATCH_MATCH: the participants' query-major arrays; slot g's slab starts slab[g]
+    // elements in
     const uint16_t *shares[8];
     uint64_t slab[G];
-    double *dist[G];        // the slot's n doubles, or all NULL
-    Partial *partials[G];   // the slot's run of gridDim.x partials
+    double *dist[G];        // BATCH_RESOLVE: the slot's n doubles, or all NULL
+    Partial *partials[G];   // BATCH_RESOLVE: the slot's run of gridDim.x partials
     uint32_t parts;
     uint32_t aligned;       // bit g: slab g of every part starts 16-B aligned
+    MatchSink match[G];     // BATCH_MATCH: the slot's own records, room, counter and threshold
 };
 
 }  // namespace
@@ -83,6 +87,9 @@ struct MaskBatchArgs {
 // Persistent, the shape of masks_mfma_kernel: each wave walks the tile groups wave, wave + nwaves, ...
 // of T tiles as one flat stream of (group, step) K-steps through register stages, so the next
 // group's loads are in flight while the current group's G x T tiles are written out.
+// BATCH_MATCH: BATCH_RESOLVE's staging and decode; each tile's records below a.match[g].threshold
+// are appended to a.match[g] (one atomic per wave, tile and slot with a hit) -- no running best,
+// no partials, nothing after the loop.
 template <int G, int T, int MODE>
 __global__ void __launch_bounds__(256, 2)
     masks_batch_kernel(const uint4 *__restrict__ db, MaskBatchArgs<G> a, uint64_t tile0, uint64_t ntiles, uint64_t first,
@@ -144,6 +151,15 @@ __global__ void __launch_bounds__(256, 2)
         }, bn, bd, br);
         const uint64_t tg = t0 + (lane & 31);
         const bool valid = tv && tg >= first && tg < end;
+        if constexpr (MODE == BATCH_MATCH) {
+            const bool hit[1] = {match_hit(a.match[g], valid && h == 0, bn, bd)};
+            const uint32_t hn[1] = {bn}, hd[1] = {bd};
+            const int hr[1] = {br};
+            const uint64_t hi[1] = {tg - first};
+            append_matches<1>(a.match[g], lane, hit, hn, hd, hr, hi);
+            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+            return;
+        }
         if (valid && a.dist[g] && h == 0) a.dist[g][tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
         Partial c;
         c.num = bn;
@@ -274,7 +290,8 @@ namespace {
 // one box, interleaved, 10M masks: two queries 3.60 ms at 4 tiles against 3.83 at 2 (resolve
 // form 4.17 against 4.42); the resolve form of four queries 7.40 ms at 2 tiles against 8.65 at 1.
 // VGPRs (no scratch in any instantiation): rows form 98 / 242 for two queries at 1 / 4 tiles,
-// 164 / 234 for four at 1 / 2; resolve form 122 / 256 and 192 / 256.
+// 164 / 234 for four at 1 / 2; resolve form 122 / 256 and 192 / 256; match form 110 / 245 and
+// 169 / 233 (it keeps no running best: profiles/r10_masks_batch_matches.txt).
 template <int G>
 constexpr int batch_big_tiles() { return G == 2 ? 4 : 2; }
 constexpr uint64_t kMasksBatchSplitTiles = 1024;  // = kMasksSplitTiles (iris_engines_mfma.hip)
@@ -312,7 +329,7 @@ int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const 
 
 template <int G>
 int launch_slots(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
-                 uint16_t *out, const MasksBatchResolve *rs, uint32_t *np) {
+                 uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks = nullptr) {
     const BatchTiles t = batch_tiles(h, r, batch_big_tiles<G>());
     if (np) *np = t.grid;
     const uint64_t slab = r.n * (uint64_t)kRot;
@@ -326,8 +343,12 @@ int launch_slots(const Hooks &h, void *stream, const void *db, const void *const
             continue;
         }
         a.slab[g] = (rs->q0 + s) * slab;
-        a.dist[g] = rs->dist_out ? rs->dist_out + (rs->q0 + s) * r.n : nullptr;
-        a.partials[g] = rs->partials + (uint64_t)s * rs->stride;
+        if (sinks) {
+            a.match[g] = sinks[s];
+        } else {
+            a.dist[g] = rs->dist_out ? rs->dist_out + (rs->q0 + s) * r.n : nullptr;
+            a.partials[g] = rs->partials + (uint64_t)s * rs->stride;
+        }
         bool al = true;
         for (uint32_t p = 0; p < rs->parts; ++p) al &= ((uintptr_t)(rs->shares[p] + a.slab[g]) & 15) == 0;
         a.aligned |= (al ? 1u : 0u) << g;
@@ -335,6 +356,7 @@ int launch_slots(const Hooks &h, void *stream, const void *db, const void *const
     if (!rs) return launch_group<G, BATCH_OUT>(stream, db, a, t, r);
     a.parts = rs->parts;
     for (uint32_t p = 0; p < rs->parts; ++p) a.shares[p] = rs->shares[p];
+    if (sinks) return launch_group<G, BATCH_MATCH>(stream, db, a, t, r);
     return launch_group<G, BATCH_RESOLVE>(stream, db, a, t, r);
 }
 
@@ -364,6 +386,19 @@ int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void 
     if (rs && (rs->parts == 0 || rs->parts > 8)) return -1;
     if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, out, rs, np);
     return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, out, rs, np);
+}
+
+// The threshold-match form of the same pass (launch_masks_batch's slots, tiles per wave and grid):
+// query s decodes slab q0 + s of every part and appends its records below sinks[s].threshold to
+// sinks[s]; the counters are zeroed on the stream by the caller.
+int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                             LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0,
+                             const MatchSink *sinks) {
+    if (r.n == 0) return 0;
+    if (m < 2 || m > (uint32_t)kMasksBatchG || parts == 0 || parts > 8 || !sinks) return -1;
+    const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
+    if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
+    return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
 }
 
 }  // namespace iris

@@ -188,6 +188,8 @@ def load_library(path=None):
                                        ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
             "iris_resolver_matches_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_double,
                                              ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
+            "iris_resolver_batch_matches_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_double,
+                                                   ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
                                         ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
             "iris_engine_query_tables": ([P, P, ctypes.c_size_t, P, ctypes.c_size_t], ctypes.c_int),
@@ -256,6 +258,7 @@ def exported_symbols():
         "iris_masks_batch_engine_new", "iris_masks_batch_process", "iris_masks_batch_process_device",
         "iris_resolver_batch_search_masks",
         "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
+        "iris_resolver_batch_matches_masks",
     ]
 
 
@@ -1178,6 +1181,42 @@ class MasksBatchEngine(_Engine):
                                                                len(ptrs), int(index_base),
                                                                ctypes.c_void_p(dist_out or 0), out))
         return list(out)
+
+    def matches(self, db, shares_device_ptrs, threshold, first=0, n=None, index_base=0, cap=None, out=None):
+        """Every query's records of that resolver step whose decoded distance is below `threshold`,
+        in one pass over the masks (iris_resolver_batch_matches_masks; the threshold has no
+        reference counterpart): shares_device_ptrs as in resolve().  -> (lists, counts): lists[q]
+        is the list[Match] MasksEngine(masks[q]).matches gives on slab q of every part (ascending
+        index, index_base + row), counts[q] its exact total.  cap is per query: None asks for every
+        match (room for 1024 a query, then once more with room for the longest reported list); 0
+        with out=None only counts.  out: a (Match * (nq * cap)) ctypes array filled in place,
+        query-major (entries past a query's list stay untouched); cap defaults to len(out) // nq."""
+        n = (len(db) - first) if n is None else n
+        ptrs = [int(p) for p in shares_device_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        counts = (ctypes.c_uint64 * self.nq)()
+        f = load_library().iris_resolver_batch_matches_masks
+
+        def call(buf, room):
+            _check(f(self.handle, db.handle, int(first), int(n), arr, len(ptrs), int(index_base), float(threshold),
+                     buf, room, counts))
+
+        want_all = out is None and cap is None
+        if out is not None:
+            cap = len(out) // self.nq if cap is None else int(cap)
+            if self.nq * cap > len(out):
+                raise IrisError(-1, "nq * cap exceeds len(out)")
+            buf = out
+        else:
+            cap = 1024 if want_all else int(cap)
+            buf = (Match * (self.nq * cap))() if cap else None
+        call(buf, cap)
+        if want_all and max(counts) > cap:
+            cap = max(counts)
+            buf = (Match * (self.nq * cap))()
+            call(buf, cap)
+        totals = [int(c) for c in counts]
+        return [[buf[q * cap + j] for j in range(min(cap, totals[q]))] for q in range(self.nq)], totals
 
 
 # ====================================================================== device groups
