@@ -478,6 +478,91 @@ impl TemplateEngine {
     }
 }
 
+/// Many query Templates against one resident Template database in one pass (no reference
+/// counterpart; the reference folds one query at a time, src/template.rs:43-47 and
+/// src/main.rs:616-621): a deduplication run or a plaintext identification service with many
+/// probes reads the enrolled database once for all of them.
+pub struct TemplateBatchEngine {
+    h: Handle,
+    nq: usize,
+}
+
+impl TemplateBatchEngine {
+    pub fn new(queries: &[Template]) -> Self {
+        Self::new_on(default_device(), queries).unwrap_or_else(|e| panic!("TemplateBatchEngine::new: {e}"))
+    }
+
+    /// At least one query; more than 3 need a database in the TILES layout.
+    pub fn new_on(device: &Device, queries: &[Template]) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            ffi::iris_template_batch_engine_new(device.raw(), queries.as_ptr().cast(), queries.len() as u32, &mut raw)
+        })?;
+        Ok(Self { h: Handle { raw, _device: device.clone() }, nq: queries.len() })
+    }
+
+    pub fn nq(&self) -> usize {
+        self.nq
+    }
+
+    /// Every query's (min distance, index) over records [first, first + n); indices are
+    /// `index_base + first + i`.
+    pub fn batch_search(&self, db: &Database, first: u64, n: u64, index_base: u64) -> Result<Vec<(f64, usize)>> {
+        let mut m = vec![ffi::IrisMatch::default(); self.nq];
+        check(unsafe { ffi::iris_template_batch_search(self.h.raw, db.raw(), first, n, index_base, m.as_mut_ptr()) })?;
+        Ok(m.iter().map(match_to_pair).collect())
+    }
+
+    /// Every query's records of [first, first + n) whose distance is below `threshold`, in one
+    /// pass over the templates (iris_template_batch_matches; the threshold has no reference
+    /// counterpart): entry q is what `TemplateEngine::matches` gives for query q -- (matches in
+    /// ascending index order, total count).  `cap` is per query; None asks for every match (room
+    /// for at most 1024 a query first, 64 at 1024 queries, then once more for the longest list).
+    pub fn batch_matches(
+        &self,
+        db: &Database,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        cap: Option<u64>,
+    ) -> Result<Vec<(Vec<(f64, usize)>, u64)>> {
+        let mut room = cap.unwrap_or((65536 / self.nq.max(1) as u64).clamp(16, 1024));
+        let mut counts = vec![0u64; self.nq];
+        let mut pass = 0;
+        let buf = loop {
+            let mut buf = vec![ffi::IrisMatch::default(); self.nq * room as usize];
+            check(unsafe {
+                ffi::iris_template_batch_matches(
+                    self.h.raw,
+                    db.raw(),
+                    first,
+                    n,
+                    index_base,
+                    threshold,
+                    if room == 0 { ptr::null_mut() } else { buf.as_mut_ptr() },
+                    room,
+                    counts.as_mut_ptr(),
+                )
+            })?;
+            let longest = counts.iter().copied().max().unwrap_or(0);
+            if cap.is_some() || pass == 1 || longest <= room {
+                break buf;
+            }
+            room = longest;
+            pass += 1;
+        };
+        Ok(counts
+            .iter()
+            .enumerate()
+            .map(|(q, &c)| {
+                let list = &buf[q * room as usize..q * room as usize + c.min(room) as usize];
+                (list.iter().map(match_to_pair).collect(), c)
+            })
+            .collect())
+    }
+}
+
 #[cfg(test)]
 mod tests {
     //! The reference's engine semantics against plain host loops (wrapping u16 MACs and

@@ -373,6 +373,17 @@ extern "C" {
         cap: u64,
         counts: *mut u64,
     ) -> c_int;
+    pub fn iris_template_batch_matches(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        out: *mut IrisMatch,
+        cap: u64,
+        counts: *mut u64,
+    ) -> c_int;
     pub fn iris_resolver_search_masks_host(
         engine: *mut IrisEngine,
         masks_db: *const IrisDb,

@@ -436,15 +436,18 @@ int iris_resolver_search_host(iris_device_t *dev, const uint16_t *const *shares,
  * are left untouched.  cap == 0 with out == NULL counts only.  n == 0 gives *count = 0.  The
  * result is deterministic: identical calls return identical bytes.  Argument, engine-kind and
  * range checks and locking are the sibling search's; a batch engine is refused (a masks batch
- * engine has a form of its own, iris_resolver_batch_matches_masks below).
+ * engine and a template batch engine have forms of their own, iris_resolver_batch_matches_masks
+ * and iris_template_batch_matches below).
  *
  * The library keeps a per-device match buffer (never more than n records) and does not guess its
  * size: a pass that reports more matches than the buffer holds is run once more with the buffer
  * grown to the reported count.
  *
- * Out of scope: of the batch engines, the template and the distance batch engine (the masks batch
- * engine, where the resolver decides, has iris_resolver_batch_matches_masks); the host-array forms
- * (*_host), the asynchronous pipeline, and device groups (a variable-length exchange). */
+ * Out of scope: of the batch engines, the distance batch engine (its rows are shares, no
+ * distances; the masks batch engine has iris_resolver_batch_matches_masks and the template batch
+ * engine iris_template_batch_matches, both below); the host-array forms (*_host), the
+ * asynchronous pipeline, and device groups (a variable-length exchange;
+ * iris_group_template_batch_search's sibling included). */
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
  * index_base + first + i. */
 int iris_template_matches(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
@@ -488,6 +491,35 @@ int iris_resolver_matches_masks(iris_engine_t *engine, const iris_db_t *masks_db
 int iris_resolver_batch_matches_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
                                       const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
                                       double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts);
+/* iris_template_batch_search's sibling, for a template batch engine (iris_template_batch_engine_new,
+ * any nq it accepts): the threshold lists of all nq queries in one pass over template records
+ * [first, first+n) (src/template.rs:43-47 per record, src/main.rs:616-621 over records, per
+ * query) -- many probes against one enrolled database, as a deduplication run asks.  One threshold
+ * for the whole batch.
+ *
+ * counts (required): host array of nq uint64_t; counts[q] is the exact number of matches of query
+ * q in the range and may exceed cap.  out: host array of nq*cap iris_match_t, query-major;
+ * out[q*cap + j], j < min(counts[q], cap), are query q's matches of lowest index in ascending index
+ * order, each filled as iris_template_matches fills it (index = index_base + first + i,
+ * reserved = 0); entries past a query's list are left untouched.  cap == 0 with out == NULL counts
+ * only.  n == 0 sets every count to 0.
+ *
+ * Contract: query q's list and count are byte for byte what iris_template_matches returns for
+ * TemplateEngine(queries[q]) over the same range, index_base and threshold.  The decision is the
+ * same f64 comparison on the best rotation (exact fraction, lowest rotation on ties): a record
+ * without a valid rotation never matches, not even under +inf; threshold <= 0 matches nothing; NaN
+ * is refused (IRIS_E_ARG).  Identical calls return identical bytes.  The value arguments
+ * (threshold, out / cap, counts) are checked before the handles; engine, database, layout and
+ * range checks are iris_template_batch_search's (more than 3 queries need a TILES database).
+ *
+ * More than 3 queries run one pass of the batched GEMM for all of them.  The first pass gives
+ * every query room for min(n, max(1024, min(cap, 256 MiB / (24 nq)))) records of the device's match
+ * buffer; a query whose list is longer has only its aligned block of 4 queries run once more, one
+ * block at a time, so no query is computed more than twice and the buffer holds at most the first
+ * pass's regions or one block's records.  Up to 3 queries run one single-query match pass each. */
+int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                                uint64_t index_base, double threshold,
+                                iris_match_t *out, uint64_t cap, uint64_t *counts);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

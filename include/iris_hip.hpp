@@ -699,6 +699,53 @@ public:
     }
 };
 
+// Many query Templates against one template database in one pass (iris_template_batch_engine_new):
+// many probes against one enrolled database.  More than 3 queries need a TILES database.
+class TemplateBatchEngine : public detail::Engine {
+public:
+    explicit TemplateBatchEngine(const std::vector<Template> &queries, Device &dev = Device::default_device())
+        : nq_((uint32_t)queries.size()) {
+        check(iris_template_batch_engine_new(dev.handle(), queries.empty() ? nullptr : queries[0].c(), nq_, &h_));
+    }
+    uint32_t nq() const { return nq_; }
+    // every query's minimum over records [first, first + n); indices are index_base + first + i
+    std::vector<Match> search(const Database &db, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        std::vector<Match> m(nq_);
+        check(iris_template_batch_search(h_, db.handle(), first, n, index_base, m.data()));
+        return m;
+    }
+    // Every query's records whose distance is below `threshold`, in one pass over the templates
+    // (iris_template_batch_matches; the threshold has no reference counterpart): result[q] is what
+    // TemplateEngine(queries[q]).matches gives over the same range; indices are index_base + first + i.
+    // cap is per query; kAllMatches: room for at most 1024 a query first (64 at 1024 queries), then
+    // once more with room for the longest reported list.
+    std::vector<Matches> matches(const Database &db, double threshold, uint64_t first, uint64_t n, uint64_t index_base = 0,
+                                 uint64_t cap = kAllMatches) const {
+        const bool all = cap == kAllMatches;
+        if (all) cap = std::min<uint64_t>(1024, std::max<uint64_t>(16, 65536 / std::max<uint32_t>(nq_, 1)));
+        std::vector<Match> flat;
+        std::vector<uint64_t> counts(nq_);
+        for (int pass = 0;; ++pass) {
+            flat.resize((size_t)nq_ * cap);
+            check(iris_template_batch_matches(h_, db.handle(), first, n, index_base, threshold, cap ? flat.data() : nullptr,
+                                              cap, counts.data()));
+            const uint64_t longest = counts.empty() ? 0 : *std::max_element(counts.begin(), counts.end());
+            if (!all || pass || longest <= cap) break;
+            cap = longest;
+        }
+        std::vector<Matches> res(nq_);
+        for (uint32_t q = 0; q < nq_; ++q) {
+            res[q].count = counts[q];
+            const Match *src = flat.data() + (size_t)q * cap;
+            res[q].list.assign(src, src + std::min(counts[q], cap));
+        }
+        return res;
+    }
+
+private:
+    uint32_t nq_ = 0;
+};
+
 // distances / denominators (src/lib.rs:82-94): single-entry wrappers
 inline Rotations distances(const EncodedBits &query, const EncodedBits &entry) {
     std::vector<Rotations> out(1);

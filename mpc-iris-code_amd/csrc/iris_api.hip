@@ -652,7 +652,7 @@ void device_teardown(iris_device *d) {
         resident_drop_all(d);
         (void)hipStreamSynchronize(d->stream);
         for (DevBuf *b : {&d->partials, &d->result, &d->staging, &d->out_a, &d->out_b, &d->ticket, &d->tempdb,
-                          &d->matches, &d->match_count})
+                          &d->matches, &d->match_count, &d->match_sinks})
             if (b->p) (void)hipFree(b->p);
         side_sync(d);
         for (int b = 0; b < 2; ++b) {
@@ -2111,46 +2111,74 @@ static int matches_args(double threshold, const iris_match_t *out, uint64_t cap,
 }
 
 // One launch unit of a threshold-match call: queries q0 .. q0 + m - 1, whose hits one pass appends.
-// launch(sinks) enqueues that pass (timed under its own names); sinks[s] is query q0 + s's.
+// launch(sinks) enqueues that pass (timed under its own names); sinks[s] is query q0 + s's.  A pass
+// whose kernel takes more sinks than the unit has queries (the template batch GEMM's padding
+// queries) asks for `pad` more after them: cap 0, no buffer, a zeroed counter of their own.
 struct MatchUnit {
     uint32_t q0, m;
+    std::function<int(const MatchSink *)> launch;
+    uint32_t pad = 0;
+};
+
+// A first pass that one launch runs for all queries at once (the template batch GEMM), the units
+// then being only what runs again: launch(sinks) takes nqp sinks, the queries' and the padding
+// queries' after them.
+struct MatchWhole {
+    uint32_t nqp;
     std::function<int(const MatchSink *)> launch;
 };
 
 // One threshold-match call of nq queries over n records each.  Every query has a counter of its
 // own (all zeroed on the stream before the first launch) and a region of `room` records of the
-// device's match buffer; every unit's first pass is enqueued before the one wait.  The counters
-// always count, so a query whose hits did not fit reports how many there are: its unit -- that
-// unit alone -- runs once more, its regions grown to exactly the reported counts (at most n
-// records a query), one unit at a time, its records copied back before the next unit runs.  A
-// query's records are then sorted by index -- the append order depends on which wave adds first --
-// and the min(count, cap) lowest become iris_match_t at out + q * cap as match_from fills them
-// (idx + base).  cap == 0 needs no record, so never a second pass.  reuse_grown (the single-query
-// calls): a buffer an earlier call grew is used in full by the first pass.
+// device's match buffer; the first pass -- `whole`, or else every unit's -- is enqueued before the
+// one wait.  The counters always count, so a query whose hits did not fit reports how many there
+// are: its unit -- that unit alone -- runs once more, its regions grown to exactly the reported
+// counts (at most n records a query), one unit at a time, its records copied back before the next
+// unit runs.  A query's records are then sorted by index -- the append order depends on which wave
+// adds first -- and the min(count, cap) lowest become iris_match_t at out + q * cap as match_from
+// fills them (idx + base).  cap == 0 needs no record, so never a second pass.  reuse_grown (the
+// single-query calls): a buffer an earlier call grew is used in full by the first pass.  budget
+// (0: none): the bytes all first-pass regions may take together, while a query keeps room for
+// kMatchFirstRoom records -- a large cap times many queries asks for no more.
 static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
-                             uint64_t *counts, uint32_t nq, bool reuse_grown, const std::vector<MatchUnit> &units) {
+                             uint64_t *counts, uint32_t nq, bool reuse_grown, const std::vector<MatchUnit> &units,
+                             const MatchWhole *whole = nullptr, uint64_t budget = 0) {
     for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
     if (n == 0) return 0;
-    CHK(ensure(d, d->match_count, nq * sizeof(uint64_t)));
+    uint32_t nc = whole ? std::max(nq, whole->nqp) : nq;  // counters and first-pass sinks
+    for (const MatchUnit &u : units) nc = std::max(nc, u.q0 + u.m + u.pad);
+    CHK(ensure(d, d->match_count, nc * sizeof(uint64_t)));
     CHK(ensure_host_result(d, nq * sizeof(uint64_t)));
     uint64_t room = 0;
     if (cap) {
-        room = std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom));
+        uint64_t want = cap;
+        if (budget) want = std::min<uint64_t>(want, budget / (sizeof(Partial) * nq));
+        room = std::min<uint64_t>(n, std::max<uint64_t>(want, kMatchFirstRoom));
         if (reuse_grown) room = std::max<uint64_t>(room, std::min<uint64_t>(n, d->matches.cap / sizeof(Partial)));
     }
     CHK(ensure(d, d->matches, nq * room * sizeof(Partial)));
     uint64_t *cnt = (uint64_t *)d->match_count.p;
-    HIPCHK(hipMemsetAsync(cnt, 0, nq * sizeof(uint64_t), d->stream));
-    MatchSink sinks[kMasksBatchG];
-    for (const MatchUnit &u : units) {
-        for (uint32_t s = 0; s < u.m; ++s)
-            sinks[s] = MatchSink{(Partial *)d->matches.p + (u.q0 + s) * room, room, cnt + u.q0 + s, threshold};
-        CHK(u.launch(sinks));
+    HIPCHK(hipMemsetAsync(cnt, 0, nc * sizeof(uint64_t), d->stream));
+    std::vector<MatchSink> sinks;  // by query; a unit's own during its rerun
+    std::vector<uint64_t> total, off;
+    try {
+        sinks.resize(nc);
+        total.resize(nq);
+        off.reserve(kMasksBatchG + 1);
+    } catch (const std::bad_alloc &) {
+        return fail(IRIS_E_NOMEM, "out of host memory");
+    }
+    for (uint32_t q = 0; q < nc; ++q)
+        sinks[q] = q < nq ? MatchSink{(Partial *)d->matches.p + q * room, room, cnt + q, threshold}
+                          : MatchSink{nullptr, 0, cnt + q, threshold};
+    if (whole) {
+        CHK(whole->launch(sinks.data()));
+    } else {
+        for (const MatchUnit &u : units) CHK(u.launch(sinks.data() + u.q0));
     }
     HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
     CHK(sync(d));
-    uint64_t total[IRIS_MASKS_BATCH_MAX];
-    memcpy(total, d->host_result, nq * sizeof(uint64_t));
+    memcpy(total.data(), d->host_result, nq * sizeof(uint64_t));
     for (uint32_t q = 0; q < nq; ++q)
         if (total[q] > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
     // query q's total[q] records at src -> counts[q] and its list
@@ -2184,16 +2212,17 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
     }
     for (const MatchUnit &u : units) {
         if (!overflows(u)) continue;
-        uint64_t off[kMasksBatchG + 1] = {0};
+        off.assign(u.m + 1, 0);
         for (uint32_t s = 0; s < u.m; ++s) off[s + 1] = off[s] + total[u.q0 + s];
         CHK(ensure(d, d->matches, off[u.m] * sizeof(Partial)));
-        for (uint32_t s = 0; s < u.m; ++s)
-            sinks[s] = MatchSink{(Partial *)d->matches.p + off[s], total[u.q0 + s], cnt + u.q0 + s, threshold};
+        for (uint32_t s = 0; s < u.m + u.pad; ++s)
+            sinks[s] = s < u.m ? MatchSink{(Partial *)d->matches.p + off[s], total[u.q0 + s], cnt + u.q0 + s, threshold}
+                               : MatchSink{nullptr, 0, cnt + u.q0 + s, threshold};
         HIPCHK(hipMemsetAsync(cnt + u.q0, 0, u.m * sizeof(uint64_t), d->stream));
-        CHK(u.launch(sinks));
+        CHK(u.launch(sinks.data()));
         HIPCHK(hipMemcpyAsync(d->host_result, cnt + u.q0, u.m * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
         CHK(sync(d));
-        if (memcmp(d->host_result, total + u.q0, u.m * sizeof(uint64_t)) != 0)
+        if (memcmp(d->host_result, total.data() + u.q0, u.m * sizeof(uint64_t)) != 0)
             return fail(IRIS_E_HIP, "match pass counts differ between two runs");
         for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + off[s]));
     }
@@ -2331,6 +2360,81 @@ int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uin
         q0 += m;
     }
     return matches_run_units(d, n, index_base, threshold, out, cap, counts, nq, false, units);
+}
+
+// The bytes the first pass of iris_template_batch_matches gives all queries' regions together (a
+// design constant): 1024 queries with a large cap then ask for 256 MiB, not for
+// cap x 1024 records.
+constexpr uint64_t kBatchMatchBudget = 256ull << 20;
+
+// iris_template_batch_search's threshold sibling, and that call's checks and dispatch.  Engines of
+// up to kBatchStreamMax queries: one single-query match pass per query ("template_match"), all
+// enqueued before the one wait.  The GEMM: one launch of batch_lds_kernel<..., MATCH>
+// ("template_batch_match") over all query groups, every query appending to its own sink of the
+// device array d->match_sinks; what runs again when a list overflows is the aligned block of
+// batch_query_group() queries, independent of the kernel shape, launched on its own query tiles.
+int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                                double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, counts));  // the value arguments first: refused whatever the handles
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
+    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
+    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
+        "batched search of more than 3 queries needs a template database in the TILES layout");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    const LaunchRange r{first, n};
+    const uint64_t base = index_base + first;
+    std::vector<MatchUnit> units;
+    if (!e->sub.empty()) {
+        for (uint32_t q = 0; n && q < nq; ++q) {
+            const iris_engine *c = e->sub[q];
+            units.push_back(MatchUnit{q, 1, [=](const MatchSink *ms) {
+                return timed(d, "template_match", n, [&] {
+                    return db->k.layout == IRIS_LAYOUT_TILES
+                               ? launch_template_mfma_match(d->hooks, d->stream, db->data, c->qfrag, r, ms[0])
+                               : launch_template_match(d->stream, db->data, c->qtab, r, ms[0]);
+                });
+            }});
+        }
+        return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, nullptr, kBatchMatchBudget);
+    }
+    const uint32_t bq = batch_query_group();
+    const uint32_t nqp = (nq + bq - 1) / bq * bq;  // the engine's padded queries (zero tiles)
+    const size_t tile_bytes = (size_t)16 * kPlaneGroups * 64;
+    // the sinks cross to the device from pinned memory, so the copy is a plain asynchronous one on
+    // the stream: the device's pinned result words past the nq counts the call reads back
+    const size_t stage_off = (nq * sizeof(uint64_t) + 63) / 64 * 64;
+    if (n) {
+        CHK(ensure(d, d->match_sinks, nqp * sizeof(MatchSink)));
+        CHK(ensure_host_result(d, stage_off + nqp * sizeof(MatchSink)));
+    }
+    const MatchSink *dsinks = (const MatchSink *)d->match_sinks.p;
+    // the sinks of queries q0 .. q0 + m - 1 and of the padding queries that fill their last block
+    // (host) -> their places in the device array, then the pass over those queries' tiles; every
+    // pass but the first follows a wait, so the staged sinks are never overwritten in flight
+    auto pass = [=](uint32_t q0, uint32_t m, const MatchSink *ms) -> int {
+        const uint32_t mp = (m + bq - 1) / bq * bq;
+        MatchSink *stage = (MatchSink *)((char *)d->host_result + stage_off) + q0;
+        memcpy(stage, ms, mp * sizeof(MatchSink));
+        HIPCHK(hipMemcpyAsync((void *)(dsinks + q0), stage, mp * sizeof(MatchSink), hipMemcpyHostToDevice, d->stream));
+        const BatchGeometry geo = batch_geometry(d->hooks, r, m);
+        return timed(d, "template_batch_match", n * m, [&] {
+            return launch_batch_match(d->hooks, d->stream, db->data, (const char *)e->qfrag + q0 * tile_bytes, r, geo,
+                                      dsinks + q0);
+        });
+    };
+    for (uint32_t q0 = 0; n && q0 < nq; q0 += bq) {
+        const uint32_t m = std::min(bq, nq - q0);
+        units.push_back(MatchUnit{q0, m, [=](const MatchSink *ms) { return pass(q0, m, ms); }, bq - m});
+    }
+    const MatchWhole whole{nqp, [=](const MatchSink *ms) { return pass(0, nq, ms); }};
+    return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, &whole, kBatchMatchBudget);
 }
 
 // The resolver step from host share arrays and the resident masks database (src/main.rs:510-519 +

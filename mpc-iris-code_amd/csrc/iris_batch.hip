@@ -11,9 +11,13 @@
 // and all query groups walk the same N-groups at once, so a template tile is
 // fetched from HBM about once per XCD and re-read from L2 by the other query
 // groups.  Per query the kernel keeps a running best (exact fraction, lowest
-// index), one partial per (query, workgroup), reduced by batch_reduce_kernel.
+// index), one partial per (query, workgroup), reduced by batch_reduce_kernel.  The threshold-match
+// form (iris_template_batch_matches) keeps the walk and appends, per query, the records below the
+// threshold to the query's own MatchSink instead.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "iris_device.hpp"
 
@@ -82,10 +86,17 @@ __global__ void __launch_bounds__(256) batch_reduce_kernel(const Partial *__rest
 // beyond L2 is applied to 16 tiles; 128 accumulators).  Cross-checked alternative (the
 // IRIS_BATCH_KERNEL=2 test hook): BQL = 4, WQL = 4, WT = 1 (8 tiles per N-group, the round-2
 // shape), whose SIMD partners run their N-groups half a group apart (kStagger).
-template <int NW, int WT, int WQL, int BQL, int GPL = 4>
+//
+// MATCH (iris_template_batch_matches): the same walk with another end of an N-group.  outp is then
+// the device array of the launch's MatchSinks, one per padded query (qtiles' order); a wave reads
+// its WQL sinks once before the walk and, per tile and query, appends the records whose best
+// rotation lies below the threshold (best_rotation + match_hit, then append_matches<WT> per query).  No running
+// best, no reduction and no partials: the kernel ends with the walk.
+template <int NW, int WT, int WQL, int BQL, bool MATCH = false, int GPL = 4>
 __global__ void __launch_bounds__(64 * NW, 1)
     batch_lds_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qtiles, uint64_t tile0, uint64_t ntiles,
-                     uint64_t first, uint64_t end, uint32_t nqg, uint32_t G, Partial *__restrict__ partials) {
+                     uint64_t first, uint64_t end, uint32_t nqg, uint32_t G,
+                     typename std::conditional<MATCH, const MatchSink, Partial>::type *__restrict__ outp) {
     constexpr int kGP = GPL;                        // chunk pairs per K-step
     constexpr int kSteps = kPlaneGroups / kGP;
     static_assert(kPlaneGroups % kGP == 0, "K-step must tile the 100 chunk pairs");
@@ -168,6 +179,15 @@ __global__ void __launch_bounds__(64 * NW, 1)
         run_jr[qi] = 0;
     }
     Partial wave_best;
+    // MATCH: this wave's sinks, held wave-uniform (the wave index through readfirstlane, so the
+    // 32 bytes of a sink are scalar loads).  A padding query's sink has cap 0 and a counter of its
+    // own; its zero tile gives den = 0 in every row, so it never has a hit to append.
+    MatchSink sink[WQL];
+    if constexpr (MATCH) {
+        const int qs = __builtin_amdgcn_readfirstlane(w) % QW;
+#pragma unroll
+        for (int qi = 0; qi < WQL; ++qi) sink[qi] = outp[qg * kBQ + qs * WQL + qi];
+    }
     v16f den[WQL][WT], sacc[WQL][WT];
     auto zero = [&] {
 #pragma unroll
@@ -258,39 +278,72 @@ __global__ void __launch_bounds__(64 * NW, 1)
         if (s + 1 >= off && (s + 1 - off) % kSteps == 0) {  // N-group done: this wave's tiles, every query
             const bool live = s >= off;
             const uint32_t j = live ? (s + 1 - off) / kSteps - 1 : 0u;
-            // per lane and query: the best of the lane's 16 rotation rows, folded into the
-            // lane's running best (no cross-lane work until the end of the walk)
             const int h = lane >> 5;
+            if constexpr (MATCH) {
+                // per tile and query: the record's best rotation from both halves of the wave (the
+                // k = 31 zero row and den = 0 rows are no candidates), decided in lanes 0..31.  An
+                // idle staggered wave (!live), a clamped tile and a record outside [first, end)
+                // are not valid and never vote.
+                // All WQL x WT decisions first, in straight-line code, so that their scans, exchanges
+                // and divisions interleave; then one append per query over its WT tiles.
+                bool hit[WQL][WT];
+                uint32_t bn[WQL][WT], bd[WQL][WT];
+                int br[WQL][WT];
+                uint64_t idx[WT];
 #pragma unroll
-            for (int t = 0; t < WT; ++t) {
-                const uint64_t trel = (gi + (uint64_t)j * G) * kTilesPerGroup + tset * WT + t;
-                const uint64_t tg = (tile0 + trel) * 32 + (lane & 31);
-                const bool valid = live && trel < ntiles && tg >= first && tg < end;
+                for (int t = 0; t < WT; ++t) {
+                    const uint64_t trel = (gi + (uint64_t)j * G) * kTilesPerGroup + tset * WT + t;
+                    const uint64_t tg = (tile0 + trel) * 32 + (lane & 31);
+                    const bool valid = live && trel < ntiles && tg >= first && tg < end;
+                    idx[t] = tg - first;
 #pragma unroll
-                for (int qi = 0; qi < WQL; ++qi) {
-                    // (bn, bd) = (1, 0) is "none": a row with den 0 (no jointly valid bit; also the
-                    // zero row k = 31) is (0, 0) and never wins, n * 0 < 1 * d holds for any real
-                    // candidate, so the scan needs no validity tests
-                    // (the selects stay compare + v_cndmask: bit-field inserts under a sign mask,
-                    // forced with inline asm, measured 1.5 % slower, profiles/r03_batch_epilogue_bfi.txt)
-                    uint32_t bn = 1, bd = 0, br = 0;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int k = (r & 3) + 8 * (r >> 2) + 4 * h;  // ascending in r: ties keep the lower k
-                        const uint32_t dd = (uint32_t)den[qi][t][r];
-                        const uint32_t nn = (uint32_t)(((int)dd - (int)sacc[qi][t][r]) >> 1);
-                        if (__umul24(nn, bd) < __umul24(bn, dd)) {
-                            bn = nn;
-                            bd = dd;
-                            br = (uint32_t)k;
-                        }
+                    for (int qi = 0; qi < WQL; ++qi) {
+                        best_rotation(
+                            lane,
+                            [&](int r, uint32_t &nn, uint32_t &dd) {
+                                dd = (uint32_t)den[qi][t][r];
+                                nn = (uint32_t)(((int)dd - (int)sacc[qi][t][r]) >> 1);
+                            },
+                            bn[qi][t], bd[qi][t], br[qi][t]);
+                        hit[qi][t] = match_hit(sink[qi], valid && h == 0, bn[qi][t], bd[qi][t]);
                     }
-                    const uint32_t rn = run_nd[qi] & 0xFFFFu, rd = run_nd[qi] >> 16;
-                    // strict <: an equal fraction keeps the earlier (lower-index) template; the
-                    // running best starts as (1, 0) too
-                    if (valid && __umul24(bn, rd) < __umul24(rn, bd)) {
-                        run_nd[qi] = bn | (bd << 16);
-                        run_jr[qi] = ((j * (uint32_t)WT + (uint32_t)t) << 5) | br;
+                }
+#pragma unroll
+                for (int qi = 0; qi < WQL; ++qi) append_matches<WT>(sink[qi], lane, hit[qi], bn[qi], bd[qi], br[qi], idx);
+            } else {
+                // per lane and query: the best of the lane's 16 rotation rows, folded into the
+                // lane's running best (no cross-lane work until the end of the walk)
+#pragma unroll
+                for (int t = 0; t < WT; ++t) {
+                    const uint64_t trel = (gi + (uint64_t)j * G) * kTilesPerGroup + tset * WT + t;
+                    const uint64_t tg = (tile0 + trel) * 32 + (lane & 31);
+                    const bool valid = live && trel < ntiles && tg >= first && tg < end;
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) {
+                        // (bn, bd) = (1, 0) is "none": a row with den 0 (no jointly valid bit; also the
+                        // zero row k = 31) is (0, 0) and never wins, n * 0 < 1 * d holds for any real
+                        // candidate, so the scan needs no validity tests
+                        // (the selects stay compare + v_cndmask: bit-field inserts under a sign mask,
+                        // forced with inline asm, measured 1.5 % slower, profiles/r03_batch_epilogue_bfi.txt)
+                        uint32_t bn = 1, bd = 0, br = 0;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int k = (r & 3) + 8 * (r >> 2) + 4 * h;  // ascending in r: ties keep the lower k
+                            const uint32_t dd = (uint32_t)den[qi][t][r];
+                            const uint32_t nn = (uint32_t)(((int)dd - (int)sacc[qi][t][r]) >> 1);
+                            if (__umul24(nn, bd) < __umul24(bn, dd)) {
+                                bn = nn;
+                                bd = dd;
+                                br = (uint32_t)k;
+                            }
+                        }
+                        const uint32_t rn = run_nd[qi] & 0xFFFFu, rd = run_nd[qi] >> 16;
+                        // strict <: an equal fraction keeps the earlier (lower-index) template; the
+                        // running best starts as (1, 0) too
+                        if (valid && __umul24(bn, rd) < __umul24(rn, bd)) {
+                            run_nd[qi] = bn | (bd << 16);
+                            run_jr[qi] = ((j * (uint32_t)WT + (uint32_t)t) << 5) | br;
+                        }
                     }
                 }
             }
@@ -299,42 +352,44 @@ __global__ void __launch_bounds__(64 * NW, 1)
         barrier();
     }
 
-    // the lanes' running bests -> one Partial per query (lane qi holds query qi's): exact
-    // fraction, then the lowest index, then the lowest rotation (the two halves of a
-    // template's rotations live in lanes l and l ^ 32)
-    {
-        Partial best = partial_none();
+    if constexpr (!MATCH) {
+        // the lanes' running bests -> one Partial per query (lane qi holds query qi's): exact
+        // fraction, then the lowest index, then the lowest rotation (the two halves of a
+        // template's rotations live in lanes l and l ^ 32)
+        {
+            Partial best = partial_none();
 #pragma unroll
-        for (int qi = 0; qi < WQL; ++qi) {
-            Partial c = partial_none();
-            if (run_nd[qi] >> 16) {
-                const uint32_t jt = run_jr[qi] >> 5, jj = jt / WT, t = jt - jj * WT;
-                const uint64_t trel = (gi + (uint64_t)jj * G) * kTilesPerGroup + tset * WT + t;
-                c.num = run_nd[qi] & 0xFFFFu;
-                c.den = run_nd[qi] >> 16;
-                c.rot = (int)(run_jr[qi] & 31u);
-                c.idx = (tile0 + trel) * 32 + (lane & 31) - first;
-            }
+            for (int qi = 0; qi < WQL; ++qi) {
+                Partial c = partial_none();
+                if (run_nd[qi] >> 16) {
+                    const uint32_t jt = run_jr[qi] >> 5, jj = jt / WT, t = jt - jj * WT;
+                    const uint64_t trel = (gi + (uint64_t)jj * G) * kTilesPerGroup + tset * WT + t;
+                    c.num = run_nd[qi] & 0xFFFFu;
+                    c.den = run_nd[qi] >> 16;
+                    c.rot = (int)(run_jr[qi] & 31u);
+                    c.idx = (tile0 + trel) * 32 + (lane & 31) - first;
+                }
 #pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const Partial o = partial_shfl_xor(c, off);
-                if (partial_better_rot(o, c)) c = o;
+                for (int off = 32; off >= 1; off >>= 1) {
+                    const Partial o = partial_shfl_xor(c, off);
+                    if (partial_better_rot(o, c)) c = o;
+                }
+                if (lane == qi) best = c;
             }
-            if (lane == qi) best = c;
+            wave_best = best;
         }
-        wave_best = best;
-    }
 
-    __syncthreads();
-    Partial *sP = (Partial *)&afrag[0][0][0][0][0];  // [wave][query of the wave]
-    if (lane < WQL) sP[w * WQL + lane] = wave_best;
-    __syncthreads();
-    if (tid < kBQ) {  // query tid: the waves of its query set, one per tile set
-        const int qs = tid / WQL, qi = tid % WQL;
-        Partial b = sP[qs * WQL + qi];
-        for (int ww = qs + QW; ww < NW; ww += QW)
-            if (partial_better_dev(sP[ww * WQL + qi], b)) b = sP[ww * WQL + qi];
-        partials[(uint64_t)(qg * kBQ + tid) * G + gi] = b;
+        __syncthreads();
+        Partial *sP = (Partial *)&afrag[0][0][0][0][0];  // [wave][query of the wave]
+        if (lane < WQL) sP[w * WQL + lane] = wave_best;
+        __syncthreads();
+        if (tid < kBQ) {  // query tid: the waves of its query set, one per tile set
+            const int qs = tid / WQL, qi = tid % WQL;
+            Partial b = sP[qs * WQL + qi];
+            for (int ww = qs + QW; ww < NW; ww += QW)
+                if (partial_better_dev(sP[ww * WQL + qi], b)) b = sP[ww * WQL + qi];
+            outp[(uint64_t)(qg * kBQ + tid) * G + gi] = b;
+        }
     }
 }
 
@@ -372,6 +427,18 @@ int launch_batch(const Hooks &h, void *stream, const void *db, const void *qtile
     if (hipGetLastError() != hipSuccess) return -1;
     hipLaunchKernelGGL(batch_reduce_kernel, dim3(g.nqg * g.qper), dim3(256), 0, (hipStream_t)stream, partials, g.G, out,
                        idx_base);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The threshold-match form of that pass: g = batch_geometry of the queries qtiles holds, sinks = the
+// device array of their g.nqg * g.qper MatchSinks (counters zeroed on the stream by the caller).
+// One launch, no reduce.
+int launch_batch_match(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                       const BatchGeometry &g, const MatchSink *sinks) {
+    if (r.n == 0) return 0;
+    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, true> : batch_lds_kernel<8, 2, 2, 2, true>;
+    hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
+                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G, sinks);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -105,6 +105,9 @@ struct iris_device {
     // threshold matching (iris_*_matches): the hits' records and the 8-byte counter a pass appends
     // through (iris::MatchSink); the counter is zeroed on the stream before every launch
     DevBuf matches, match_count;
+    // the MatchSinks of a template batch match pass, one per padded query (the GEMM reads them
+    // from memory: up to 1024 and more do not travel as kernel arguments)
+    DevBuf match_sinks;
     // zeroed device word of the fused (last-workgroup) search reduce; searches on the stream
     // are serialised, and each launch leaves it zeroed
     DevBuf ticket;

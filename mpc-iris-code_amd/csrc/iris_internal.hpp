@@ -308,6 +308,10 @@ BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq);
 uint32_t batch_query_group();  // padding unit of a batched engine's queries
 int launch_batch(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r, const BatchGeometry &g,
                  Partial *partials, Partial *out, uint64_t idx_base = 0);
+// the threshold-match form of that pass (batch_lds_kernel<..., MATCH>): sinks = DEVICE array of one
+// MatchSink per query of g (g.nqg * g.qper, in qtiles' order; a padding query's has cap 0)
+int launch_batch_match(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                       const BatchGeometry &g, const MatchSink *sinks);
 int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
                     double *dist_out, Partial *partials);
 int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,

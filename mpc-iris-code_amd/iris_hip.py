@@ -190,6 +190,8 @@ def load_library(path=None):
                                              ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
             "iris_resolver_batch_matches_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_double,
                                                    ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
+            "iris_template_batch_matches": ([P, P, u64, u64, u64, ctypes.c_double, ctypes.POINTER(Match), u64,
+                                             ctypes.POINTER(u64)], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
                                         ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
             "iris_engine_query_tables": ([P, P, ctypes.c_size_t, P, ctypes.c_size_t], ctypes.c_int),
@@ -258,7 +260,7 @@ def exported_symbols():
         "iris_masks_batch_engine_new", "iris_masks_batch_process", "iris_masks_batch_process_device",
         "iris_resolver_batch_search_masks",
         "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
-        "iris_resolver_batch_matches_masks",
+        "iris_resolver_batch_matches_masks", "iris_template_batch_matches",
     ]
 
 
@@ -1090,6 +1092,40 @@ class TemplateBatchEngine(_Engine):
         _check(load_library().iris_template_batch_search(self.handle, db.handle, int(first), int(n), int(index_base),
                                                          out))
         return list(out)
+
+    def matches(self, db, threshold, first=0, n=None, index_base=0, cap=None, out=None):
+        """Every query's records whose distance is below `threshold`, in one pass over the
+        templates (iris_template_batch_matches; the threshold has no reference counterpart).
+        -> (lists, counts): lists[q] is the list[Match] TemplateEngine(queries[q]).matches gives
+        over the same range (ascending index, index_base + first + i), counts[q] its exact total.
+        cap is per query: None asks for every match (room for min(1024, max(16, 65536 // nq)) a
+        query first -- 64 at 1024 queries, 2 MB of Match -- then once more with room for the longest
+        reported list); 0 with out=None only counts.  out: a (Match * (nq * cap)) ctypes array
+        filled in place, query-major (entries past a query's list stay untouched); cap defaults to
+        len(out) // nq."""
+        n = (len(db) - first) if n is None else n
+        counts = (ctypes.c_uint64 * self.nq)()
+        f = load_library().iris_template_batch_matches
+
+        def call(buf, room):
+            _check(f(self.handle, db.handle, int(first), int(n), int(index_base), float(threshold), buf, room, counts))
+
+        want_all = out is None and cap is None
+        if out is not None:
+            cap = len(out) // self.nq if cap is None else int(cap)
+            if self.nq * cap > len(out):
+                raise IrisError(-1, "nq * cap exceeds len(out)")
+            buf = out
+        else:
+            cap = min(1024, max(16, 65536 // self.nq)) if want_all else int(cap)
+            buf = (Match * (self.nq * cap))() if cap else None
+        call(buf, cap)
+        if want_all and max(counts) > cap:
+            cap = max(counts)
+            buf = (Match * (self.nq * cap))()
+            call(buf, cap)
+        totals = [int(c) for c in counts]
+        return [[buf[q * cap + j] for j in range(min(cap, totals[q]))] for q in range(self.nq)], totals
 
 
 class DistanceBatchEngine(_Engine):

@@ -1,0 +1,105 @@
+"""CPU: the ABI surface of template batch threshold matching (iris_template_batch_matches) -- the
+entry point is exported and named in the header, the Rust declarations, iris_hip.hpp, the Python
+mirror and the three documents; its header comment cites the reference lines it generalises and
+states the byte-for-byte contract; it refuses bad value arguments with a message before it looks at
+a handle; and a C++ program using TemplateBatchEngine::matches compiles and links
+(tests/test_gpu_template_batch_matches.py runs it)."""
+import ctypes
+import math
+import pathlib
+import re
+import subprocess
+
+import iris_hip as ih
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+CPP_SRC = ROOT / "tests" / "cpp" / "template_batch_matches.cpp"
+NAME = "iris_template_batch_matches"
+E_ARG = -1
+
+
+def build_cpp_program(outdir):
+    """Compiles tests/cpp/template_batch_matches.cpp against the in-tree library -> the binary's path."""
+    exe = pathlib.Path(outdir) / "template_batch_matches"
+    lib = ROOT / "mpc-iris-code_amd"
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", f"-I{ROOT / 'include'}", str(CPP_SRC), "-o",
+                        str(exe), f"-L{lib}", "-liris_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath-link,/opt/rocm/lib"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
+def _last_error(lib):
+    return lib.iris_last_error().decode(errors="replace")
+
+
+def test_symbol_exported_and_named_everywhere():
+    lib = ih.load_library()
+    assert hasattr(lib, NAME)
+    assert NAME in ih.exported_symbols()
+    header = (ROOT / "include" / "iris_hip.h").read_text()
+    assert re.search(r"\bint " + NAME + r"\(", header)
+    # declared in the threshold-matching section, after the masks batch form
+    assert header.index("int " + NAME + "(") > header.index("int iris_resolver_batch_matches_masks(")
+    ffi = (ROOT / "bindings" / "rust" / "src" / "iris_hip" / "ffi.rs").read_text()
+    assert f"pub fn {NAME}(" in ffi
+    engines = (ROOT / "bindings" / "rust" / "src" / "iris_hip" / "engines.rs").read_text()
+    assert "pub struct TemplateBatchEngine" in engines and "ffi::" + NAME in engines
+    hpp = (ROOT / "include" / "iris_hip.hpp").read_text()
+    assert NAME + "(" in hpp and "class TemplateBatchEngine" in hpp
+    assert hasattr(ih.TemplateBatchEngine, "matches")
+    for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
+        assert NAME in (ROOT / doc).read_text(), doc
+
+
+def test_header_comment_cites_the_reference_and_the_contract():
+    header = (ROOT / "include" / "iris_hip.h").read_text()
+    decl = header.index("int " + NAME + "(")
+    comment = header[header.rindex("/*", 0, decl):decl]
+    for cite in ("src/template.rs:43-47", "src/main.rs:616-621"):
+        assert cite in comment, cite
+    assert "byte for byte" in comment and "iris_template_matches" in comment
+    assert "NaN" in comment and "counts" in comment and "TILES" in comment
+    # the scope paragraph of the section: the template batch engine is in
+    sec = header[header.index("threshold matching"):header.index("int iris_resolver_matches_masks(")]
+    scope = sec[sec.index("Out of scope"):]
+    assert NAME in scope and "distance" in scope and "device groups" in scope
+
+
+def _call(lib, threshold, out, cap, counts):
+    """The entry point with NULL handles and otherwise plausible arguments."""
+    return lib.iris_template_batch_matches(None, None, 0, 1, 0, threshold, out, cap, counts)
+
+
+def test_value_arguments_are_refused_before_the_handles():
+    lib = ih.load_library()
+    out = (ih.Match * 2)()
+    ctypes.memset(out, 0x5A, ctypes.sizeof(out))
+    before = bytes(out)
+    counts = (ctypes.c_uint64 * 2)(77, 78)
+    for nan in (math.nan, -math.nan):
+        assert _call(lib, nan, out, 1, counts) == E_ARG
+        assert "NaN" in _last_error(lib)
+    assert _call(lib, 0.5, out, 1, None) == E_ARG
+    assert "count" in _last_error(lib)
+    assert _call(lib, 0.5, None, 1, counts) == E_ARG
+    assert "out is NULL" in _last_error(lib)
+    # valid value arguments: the NULL handles are what is refused
+    assert _call(lib, 0.5, out, 1, counts) == E_ARG
+    assert "NULL argument" in _last_error(lib)
+    assert _call(lib, 0.5, None, 0, counts) == E_ARG
+    assert "NULL argument" in _last_error(lib)
+    assert list(counts) == [77, 78] and bytes(out) == before
+
+
+def test_single_query_call_still_refuses_a_batch_engine():
+    """iris_template_matches goes through template_args, which refuses an engine with nq > 0."""
+    src = (ROOT / "mpc-iris-code_amd" / "csrc" / "iris_api.hip").read_text()
+    body = src[src.index("int iris_template_matches("):src.index("int iris_resolver_matches(")]
+    assert "CHK(template_args(e, db));" in body
+    args = src[src.index("static int template_args("):]
+    assert re.search(r"ARG\(e->kind == IRIS_KIND_TEMPLATES && e->nq == 0,", args[:args.index("}")])
+
+
+def test_cpp_program_compiles(tmp_path):
+    assert build_cpp_program(tmp_path).exists()
