@@ -41,6 +41,41 @@ fn collect_matches(
     Ok((buf.iter().map(match_to_pair).collect(), count))
 }
 
+/// Runs one `iris_*_topk` call: `call(out, count)` on a k-entry array -> the listed records as
+/// `(distance, index)`, best first.
+fn collect_topk(k: u32, mut call: impl FnMut(*mut ffi::IrisMatch, *mut u32) -> i32) -> Result<Vec<(f64, usize)>> {
+    let mut count = 0u32;
+    let mut buf = vec![ffi::IrisMatch::default(); k.max(1) as usize];
+    check(call(buf.as_mut_ptr(), &mut count))?;
+    buf.truncate(count as usize);
+    Ok(buf.iter().map(match_to_pair).collect())
+}
+
+/// The k closest rows of the resolver's aggregation over device arrays of n * 31 u16, best first
+/// (iris_resolver_topk; k = 1..=ffi::IRIS_TOPK_MAX has no reference counterpart).
+pub fn resolver_topk(
+    dev: &Device,
+    shares_device: &[*const u16],
+    denoms_device: *const u16,
+    n: u64,
+    index_base: u64,
+    k: u32,
+) -> Result<Vec<(f64, usize)>> {
+    collect_topk(k, |out, count| unsafe {
+        ffi::iris_resolver_topk(
+            dev.raw(),
+            shares_device.as_ptr(),
+            shares_device.len() as u32,
+            denoms_device,
+            n,
+            index_base,
+            k,
+            out,
+            count,
+        )
+    })
+}
+
 /// An engine handle plus the device it lives on (kept alive by the clone).
 struct Handle {
     raw: *mut ffi::IrisEngine,
@@ -224,6 +259,25 @@ impl MasksEngine {
                 threshold,
                 out,
                 room,
+                count,
+            )
+        })
+    }
+
+    /// The k closest records of that step, best first (iris_resolver_topk_masks; k has no reference
+    /// counterpart): indices are the rows within the range.
+    pub fn topk(&self, masks: &Database, first: u64, n: u64, shares_device: &[*const u16], k: u32) -> Result<Vec<(f64, usize)>> {
+        collect_topk(k, |out, count| unsafe {
+            ffi::iris_resolver_topk_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                0,
+                k,
+                out,
                 count,
             )
         })
@@ -466,6 +520,14 @@ impl TemplateEngine {
     ) -> Result<(Vec<(f64, usize)>, u64)> {
         collect_matches(cap, |out, room, count| unsafe {
             ffi::iris_template_matches(self.h.raw, db.raw(), first, n, index_base, threshold, out, room, count)
+        })
+    }
+
+    /// The k closest records of [first, first + n), best first, in one database pass
+    /// (iris_template_topk; k has no reference counterpart); indices are `index_base + first + i`.
+    pub fn topk(&self, db: &Database, first: u64, n: u64, index_base: u64, k: u32) -> Result<Vec<(f64, usize)>> {
+        collect_topk(k, |out, count| unsafe {
+            ffi::iris_template_topk(self.h.raw, db.raw(), first, n, index_base, k, out, count)
         })
     }
 

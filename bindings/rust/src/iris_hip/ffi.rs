@@ -16,6 +16,7 @@ pub const IRIS_BITS: usize = 12800;
 pub const IRIS_LIMBS: usize = 200;
 pub const IRIS_ROTATIONS: usize = 31;
 pub const IRIS_MAX_ROTATION: i32 = 15;
+pub const IRIS_TOPK_MAX: u32 = 64;
 
 /// Status codes.
 pub const IRIS_OK: c_int = 0;
@@ -322,6 +323,47 @@ extern "C" {
         index_base: u64,
         dist_out_device: *mut f64,
         out: *mut IrisMatch,
+    ) -> c_int;
+    // top-k: the k closest records, best first (k = 1..IRIS_TOPK_MAX has no reference counterpart)
+    pub fn iris_template_topk(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        k: u32,
+        out: *mut IrisMatch,
+        count: *mut u32,
+    ) -> c_int;
+    pub fn iris_resolver_topk(
+        dev: *mut IrisDevice,
+        shares_device: *const *const u16,
+        parts: u32,
+        denoms_device: *const u16,
+        n: u64,
+        index_base: u64,
+        k: u32,
+        out: *mut IrisMatch,
+        count: *mut u32,
+    ) -> c_int;
+    pub fn iris_resolver_topk_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        k: u32,
+        out: *mut IrisMatch,
+        count: *mut u32,
+    ) -> c_int;
+    pub fn iris_topk_merge(
+        records: *const IrisMatch,
+        nrecords: u64,
+        k: u32,
+        out: *mut IrisMatch,
+        count: *mut u32,
     ) -> c_int;
     // threshold matching: every record below a distance (no reference counterpart for the threshold)
     pub fn iris_template_matches(

@@ -521,6 +521,59 @@ int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint
                                 uint64_t index_base, double threshold,
                                 iris_match_t *out, uint64_t cap, uint64_t *counts);
 
+/* ------------------------------------------------------------------- top-k
+ * The k closest records of a range, best first, in one database pass -- the ranked candidate
+ * list of rank-k identification, a review queue or threshold calibration, with no threshold
+ * known in advance.  The reference has only the minimum: src/template.rs:43-47 per record, folded
+ * over records by src/main.rs:616-621.  The calls below generalise that fold from "the first
+ * record of the order" to "the first k"; k itself has no reference counterpart.
+ *
+ * The order is the sibling search's (iris_template_search, iris_resolver_search,
+ * iris_resolver_search_masks): records are ordered by the exact fraction num/den of their best
+ * rotation (u32 cross-multiplication, never a float), then by the lowest index; the best rotation
+ * is the exact fraction minimum, lowest rotation on ties (decode_distance of the wrapping share
+ * sum, src/lib.rs:97-107, for the resolver forms).  A record without a valid rotation (every
+ * den == 0, distance +inf) is never listed.
+ *
+ * k: 1..IRIS_TOPK_MAX (IRIS_E_ARG otherwise).  out: host array of k iris_match_t; count
+ * (required): *count = min(k, records of the range with a valid rotation).  out[0..*count) are
+ * the first *count records of the order, best first, each filled as the sibling search fills its
+ * one result (distance is the one IEEE division num/den, index = index_base + the sibling's
+ * offset, num, den, rotation, reserved = 0); entries past *count are left untouched.  n == 0
+ * gives *count = 0.  The order is total (indices are unique), so identical calls return identical
+ * bytes.  It follows that out[0] is byte for byte the sibling search's result (*count == 0 where
+ * the search reports +inf), that a call with k' < k returns the first k' entries of the call
+ * with k, and that the entries below a threshold are the sibling *_matches list.
+ *
+ * The value arguments (k, out, count) are checked before the handles; engine-kind, database,
+ * layout and range checks and the locking are the sibling search's; a batch engine is refused.
+ * There is no dist_out_device.  The bytes copied back per call are 24 k, whatever n is.
+ *
+ * Out of scope: the batch engines, the host-array forms (*_host), the asynchronous pipeline,
+ * device groups (iris_topk_merge below is the hand-sharding answer) and k > 64. */
+#define IRIS_TOPK_MAX 64
+/* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
+ * index_base + first + i. */
+int iris_template_topk(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                       uint64_t index_base, uint32_t k, iris_match_t *out, uint32_t *count);
+/* iris_resolver_search's sibling (src/main.rs:597-621; the per-row minimum over rotations is
+ * decode_distance's, src/lib.rs:97-107): DEVICE arrays of n*31 uint16_t; indices are index_base + i. */
+int iris_resolver_topk(iris_device_t *dev, const uint16_t *const *shares_device, uint32_t parts,
+                       const uint16_t *denoms_device, uint64_t n, uint64_t index_base, uint32_t k,
+                       iris_match_t *out, uint32_t *count);
+/* iris_resolver_search_masks' sibling (src/main.rs:510-519 + 597-621): indices are
+ * index_base + i, i the row within the range. */
+int iris_resolver_topk_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                             const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                             uint32_t k, iris_match_t *out, uint32_t *count);
+/* Host only, no device: merges top-k lists (of shards, chunks, GPUs) that carry global indices
+ * into one -- the top-k counterpart of iris_match_merge, src/main.rs:616-621 generalised to k.
+ * The same order over nrecords records; records with den == 0 or index == UINT64_MAX are
+ * ignored; two records with the same index are a caller error (IRIS_E_ARG).  out (k records,
+ * not overlapping `records`) receives *count = min(k, valid records) records, best first, copied
+ * as given; entries past *count are left untouched. */
+int iris_topk_merge(const iris_match_t *records, uint64_t nrecords, uint32_t k, iris_match_t *out, uint32_t *count);
+
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):
  *   dot_bool(&[u64;200], &[u64;200]) -> u16   src/arch/generic.rs:4-9

@@ -89,6 +89,15 @@ inline Matches collect_matches(uint64_t cap, F call) {
     m.list.resize(std::min<uint64_t>(cap, m.count));
     return m;
 }
+// call(out, &count) -> rc on a k-entry array (iris_*_topk) -> the listed entries
+template <class F>
+inline std::vector<Match> collect_topk(uint32_t k, F call) {
+    std::vector<Match> list(std::max<uint32_t>(k, 1));
+    uint32_t count = 0;
+    check(call(list.data(), &count));
+    list.resize(count);
+    return list;
+}
 }  // namespace detail
 
 class Device {
@@ -551,6 +560,15 @@ public:
                                                (uint32_t)shares_device.size(), index_base, threshold, out, c, count);
         });
     }
+    // The k closest records of that resolver step, best first (iris_resolver_topk_masks; k has no
+    // reference counterpart); indices are index_base + row.
+    std::vector<Match> topk(const Database &db, const std::vector<const uint16_t *> &shares_device, uint32_t k,
+                            uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        return detail::collect_topk(k, [&](Match *out, uint32_t *count) {
+            return iris_resolver_topk_masks(h_, db.handle(), first, n, shares_device.data(), (uint32_t)shares_device.size(),
+                                            index_base, k, out, count);
+        });
+    }
     // The same with the participants' outputs in host memory (the rows as they arrive): summed on
     // the host, the sum uploaded (iris_resolver_search_masks_host).
     Match resolve_host(const Database &db, const std::vector<const std::vector<Rotations> *> &shares, uint64_t first,
@@ -680,6 +698,13 @@ public:
             return iris_template_matches(h_, db.handle(), first, n, index_base, threshold, out, c, count);
         });
     }
+    // The k closest records of the range, best first, in one database pass (iris_template_topk; k has
+    // no reference counterpart); indices are index_base + first + i.
+    std::vector<Match> topk(const Database &db, uint32_t k, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        return detail::collect_topk(k, [&](Match *out, uint32_t *count) {
+            return iris_template_topk(h_, db.handle(), first, n, index_base, k, out, count);
+        });
+    }
     // pipelined form: returns once the search is enqueued (the engine may be destroyed before the wait)
     PendingSearch search_async(const Database &db, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
         iris_pending_t *p = nullptr;
@@ -801,6 +826,22 @@ inline Matches resolver_matches(Device &dev, const std::vector<const uint16_t *>
     return detail::collect_matches(cap, [&](Match *out, uint64_t c, uint64_t *count) {
         return iris_resolver_matches(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
                                      index_base, threshold, out, c, count);
+    });
+}
+
+// Device-array form of the resolver's top-k (iris_resolver_topk): the k closest rows, best first.
+inline std::vector<Match> resolver_topk(Device &dev, const std::vector<const uint16_t *> &shares_device,
+                                        const uint16_t *denoms_device, uint64_t n, uint32_t k, uint64_t index_base = 0) {
+    return detail::collect_topk(k, [&](Match *out, uint32_t *count) {
+        return iris_resolver_topk(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
+                                  index_base, k, out, count);
+    });
+}
+// Merges top-k lists that carry global indices (shards, chunks, GPUs) into the k best, best first
+// (iris_topk_merge; host only).
+inline std::vector<Match> topk_merge(const std::vector<Match> &records, uint32_t k) {
+    return detail::collect_topk(k, [&](Match *out, uint32_t *count) {
+        return iris_topk_merge(records.data(), records.size(), k, out, count);
     });
 }
 

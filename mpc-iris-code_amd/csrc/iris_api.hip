@@ -2305,6 +2305,107 @@ int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t 
     });
 }
 
+// ------------------------------------------------------------------ top-k
+
+static int topk_args(uint32_t k, const iris_match_t *out, const uint32_t *count) {
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");
+    ARG(out, "out is NULL");
+    ARG(count, "count is NULL");
+    return 0;
+}
+
+// One top-k call over n records: `launch` enqueues the pass whose `units` waves each store their
+// k best at the lists it is given (the device's match buffer: units lists, then the merge's spare
+// lists), the merge levels follow on the stream and the last one writes k records to the pinned
+// host result -- 24 k bytes whatever n is -- and the call waits once.  The list is sorted with the
+// empty entries (den = 0) last, so the count is the length of its valid prefix.
+static int topk_run(iris_device *d, uint64_t n, uint64_t base, uint32_t k, iris_match_t *out, uint32_t *count,
+                    const char *name, uint64_t units, const std::function<int(const MatchSink &)> &launch) {
+    *count = 0;
+    if (n == 0) return 0;
+    CHK(ensure(d, d->matches, (units + topk_spare_lists(units)) * k * sizeof(Partial)));
+    CHK(ensure_host_result(d, (size_t)k * sizeof(Partial)));
+    Partial *lists = (Partial *)d->matches.p, *spare = lists + units * k;
+    CHK(timed(d, name, n, [&] { return launch(topk_sink(lists, k)); }));
+    CHK(timed(d, "topk_merge", units,
+              [&] { return launch_topk_merge(d->stream, lists, spare, units, k, (Partial *)d->host_result); }));
+    CHK(sync(d));
+    const Partial *res = (const Partial *)d->host_result;
+    uint32_t c = 0;
+    while (c < k && res[c].den != 0) ++c;
+    for (uint32_t i = 0; i < c; ++i) match_from(res[i], true, base, &out[i]);
+    *count = c;
+    return 0;
+}
+
+// iris_template_search's top-k sibling (header: "top-k")
+int iris_template_topk(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                       uint32_t k, iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(topk_args(k, out, count));  // the value arguments first: refused whatever the handles
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const uint64_t units = n ? (tiles ? mfma_topk_units(d->hooks, r) : template_topk_units(r)) : 0;
+    return topk_run(d, n, index_base + first, k, out, count, "template_topk", units, [&](const MatchSink &ts) {
+        return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts)
+                     : launch_template_topk(d->stream, db->data, e->qtab, r, ts);
+    });
+}
+
+// iris_resolver_search's top-k sibling
+int iris_resolver_topk(iris_device_t *d, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms,
+                       uint64_t n, uint64_t index_base, uint32_t k, iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(topk_args(k, out, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(d, "NULL argument");
+    ARG(n == 0 || (shares && denoms), "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares[p], "NULL share array");
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
+        return launch_resolver_topk(d->stream, shares, parts, denoms, n, ts);
+    });
+}
+
+// iris_resolver_search_masks' top-k sibling: TILES runs the fused masks_mfma_kernel<MASKS_TOPK>;
+// LANES the masks kernel into a workspace and then the resolver top-k kernel.
+int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                             const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base, uint32_t k,
+                             iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(topk_args(k, out, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_MASKS && db->k.kind == IRIS_KIND_MASKS, "needs a masks engine and a masks database");
+    ARG(e->nq == 0, "a masks batch engine has no top-k form");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    ARG(n == 0 || shares_device, "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    if (db->k.layout == IRIS_LAYOUT_TILES)
+        return topk_run(d, n, index_base, k, out, count, "masks_topk", n ? masks_topk_units(d->hooks, r) : 0,
+                        [&](const MatchSink &ts) {
+                            return launch_masks_topk(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, ts);
+                        });
+    if (n) {
+        CHK(ensure(d, d->out_a, n * kRot * 2));
+        CHK(timed(d, "masks", n, [&] { return launch_masks(d->stream, db->data, e->qtab, r, (uint16_t *)d->out_a.p); }));
+    }
+    return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
+        return launch_resolver_topk(d->stream, shares_device, parts, (const uint16_t *)d->out_a.p, n, ts);
+    });
+}
+
 // iris_resolver_batch_search_masks' threshold sibling, and that call's dispatch: TILES ranges the
 // batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass of
 // masks_batch_kernel<BATCH_MATCH> ("masks_batch_match") appending to the group's sinks, a single
@@ -2851,6 +2952,33 @@ int iris_match_merge(const iris_match_t *recs, uint64_t count, iris_match_t *out
         if (take) best = c;
     }
     *out = best;
+    return 0;
+}
+
+// iris_match_merge's top-k counterpart, host only: the k first records of the search order
+// (exact fraction, then lowest index) among `count` records that carry global indices.
+int iris_topk_merge(const iris_match_t *recs, uint64_t nrecords, uint32_t k, iris_match_t *out, uint32_t *count) {
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");
+    ARG(out, "out is NULL");
+    ARG(count, "count is NULL");
+    ARG(nrecords == 0 || recs, "records is NULL");
+    std::vector<const iris_match_t *> v;
+    try {
+        v.reserve(nrecords);
+    } catch (const std::bad_alloc &) {
+        return fail(IRIS_E_NOMEM, "out of host memory");
+    }
+    for (uint64_t i = 0; i < nrecords; ++i)
+        if (recs[i].den != 0 && recs[i].index != UINT64_MAX) v.push_back(&recs[i]);
+    std::sort(v.begin(), v.end(), [](const iris_match_t *a, const iris_match_t *b) { return a->index < b->index; });
+    for (size_t i = 1; i < v.size(); ++i) ARG(v[i]->index != v[i - 1]->index, "two records carry the same index");
+    const size_t take = std::min<size_t>(k, v.size());
+    std::partial_sort(v.begin(), v.begin() + take, v.end(), [](const iris_match_t *a, const iris_match_t *b) {
+        const uint64_t l = (uint64_t)a->num * b->den, r = (uint64_t)b->num * a->den;
+        return l != r ? l < r : a->index < b->index;
+    });
+    for (size_t i = 0; i < take; ++i) out[i] = *v[i];
+    *count = (uint32_t)take;
     return 0;
 }
 

@@ -268,6 +268,55 @@ __device__ __forceinline__ void append_matches(const MatchSink &m, int lane, con
     }
 }
 
+// Top-k (iris_*_topk).  A wave keeps its best candidates so far as ONE sorted list, entry j in
+// lane j (`entry`; den = 0 is an empty entry, empties last), in the search order of
+// partial_better_dev -- a total order, indices being unique.  It takes the place of the search
+// form's running best.  Lanes >= k hold the overflow of earlier inserts and are never stored.
+__device__ __forceinline__ Partial partial_readlane(const Partial &c, int src) {  // src: wave-uniform
+    Partial o;
+    o.num = (uint32_t)__builtin_amdgcn_readlane((int)c.num, src);
+    o.den = (uint32_t)__builtin_amdgcn_readlane((int)c.den, src);
+    o.rot = __builtin_amdgcn_readlane(c.rot, src);
+    o.pad = 0;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)c.idx, src);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(c.idx >> 32), src);
+    o.idx = ((uint64_t)hi << 32) | lo;
+    return o;
+}
+// One record group's candidates (one per lane, `valid` lanes only; every lane of the wave calls
+// this) against the wave's list: a ballot finds the candidates that beat the k-th entry (lane
+// k - 1, broadcast once) -- after a short warm-up usually none, and the group costs one compare
+// and one ballot.  Each set bit, in ascending lane order, is broadcast, its position is the
+// number of entries that beat it (a popcount: the list is sorted), the entries from there on move
+// up one lane and lane `pos` takes it; a candidate that an earlier insert of the same group
+// pushed past k - 1 finds pos >= k and is dropped.
+__device__ __forceinline__ void topk_insert(Partial &entry, uint32_t k, int lane, Partial c, bool valid) {
+    if (!valid) c.den = 0;
+    const Partial kth = partial_readlane(entry, (int)k - 1);
+    uint64_t vote = __ballot(partial_better_dev(c, kth));
+    while (vote) {  // wave-uniform
+        const int src = __builtin_ctzll(vote);
+        vote &= vote - 1;
+        const Partial x = partial_readlane(c, src);
+        const uint32_t pos = (uint32_t)__popcll(__ballot(partial_better_dev(entry, x)));
+        if (pos >= k) continue;
+        Partial up;
+        up.num = __shfl_up(entry.num, 1);
+        up.den = __shfl_up(entry.den, 1);
+        up.rot = __shfl_up(entry.rot, 1);
+        up.pad = 0;
+        up.idx = ((uint64_t)__shfl_up((uint32_t)(entry.idx >> 32), 1) << 32) | __shfl_up((uint32_t)entry.idx, 1);
+        if ((uint32_t)lane > pos) entry = up;
+        else if ((uint32_t)lane == pos) entry = x;
+    }
+}
+// The wave's list -> lists[unit][0..k) (topk_sink, iris_internal.hpp: buf = lists, cap = k): plain
+// vector stores at a place only this wave writes, empty entries included, so the merge reads no
+// stale record and nothing needs zeroing or an atomic.
+__device__ __forceinline__ void topk_store(const MatchSink &m, uint64_t unit, int lane, const Partial &entry) {
+    if ((uint64_t)lane < m.cap) m.buf[unit * m.cap + (uint64_t)lane] = entry;
+}
+
 // Last-workgroup reduction (a search's partials reduce without a second launch).  Thread 0
 // publishes this workgroup's partial with agent-scope atomic stores (sc1: written through
 // past the XCD's L2, coherent across the XCDs without an L2 writeback / invalidate -- a full

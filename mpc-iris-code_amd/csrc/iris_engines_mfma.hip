@@ -35,8 +35,8 @@ constexpr int kTile = 32;
 // costs registers: 5.1 vs 2.7 ms)
 constexpr int kMasksTiles = 7;
 constexpr int kResolveTiles = 4;
-// MASKS_RESOLVE (1) and MASKS_MATCH (3) share the resolver step's shape
-constexpr bool masks_resolving(int mode) { return mode == 1 || mode == 3; }
+// MASKS_RESOLVE (1), MASKS_MATCH (3) and MASKS_TOPK (4) share the resolver step's shape
+constexpr bool masks_resolving(int mode) { return mode == 1 || mode == 3 || mode == 4; }
 template <int MODE>
 constexpr int masks_tiles() { return !masks_resolving(MODE) ? kMasksTiles : kResolveTiles; }
 constexpr int kMasksBlocksPerCu = 2;  // persistent grid: workgroups per CU
@@ -102,7 +102,9 @@ struct MaskResolve {
 // MASKS_PACKED: the [u16;31] rows in the read-ahead's packed form (store_tile_packed, iris_device.hpp)
 // MASKS_MATCH: MASKS_RESOLVE's staging and decode; in place of the running best, the records below
 // rs.match.threshold are appended to rs.match (iris_resolver_matches_masks)
-enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3 };
+// MASKS_TOPK: MASKS_RESOLVE's staging and decode; the running best becomes the wave's top-k list
+// (topk_insert), stored at rs.match.buf[wave] (rs.match = topk_sink; iris_resolver_topk_masks)
+enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3, MASKS_TOPK = 4 };
 
 // Persistent: each wave walks the tile groups wave, wave + nwaves, ... as one
 // flat stream of (group, step) K-steps, so the loads of the next group are in
@@ -197,6 +199,11 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
         c.rot = br;
         c.pad = 0;
         c.idx = tg - first;
+        if constexpr (MODE == MASKS_TOPK) {  // best: this lane's entry of the wave's list
+            topk_insert(best, (uint32_t)rs.match.cap, lane, c, h == 0);
+            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+            return;
+        }
         if (partial_better_dev(c, best)) best = c;
         __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
     };
@@ -258,6 +265,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
             compute(sc, s + 2);
         }
     }
+    if constexpr (MODE == MASKS_TOPK) topk_store(rs.match, wave, lane, best);  // every wave of the grid: one list
     if constexpr (MODE == MASKS_RESOLVE) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
@@ -420,6 +428,31 @@ int launch_masks_match(const Hooks &h, void *stream, const void *db, const void 
     rs.parts = parts;
     rs.match = ms;
     auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_MATCH, 1> : masks_mfma_kernel<MASKS_MATCH>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, rs);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+uint64_t masks_topk_units(const Hooks &h, LaunchRange r) { return (uint64_t)masks_resolve_partials(h, r) * kWaveSlots; }
+
+// launch_masks_resolve's dispatch and grid with the MASKS_TOPK epilogue
+int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                      const uint16_t *const *shares, uint32_t parts, const MatchSink &ts) {
+    if (r.n == 0) return 0;
+    if (parts == 0 || parts > 8) return -1;
+    const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles);
+    const Tiles t = tiles_of(r, tpw);
+    const uint64_t grid = masks_resolve_partials(h, r);
+    MaskResolve rs{};
+    rs.aligned = true;
+    for (uint32_t p = 0; p < parts; ++p) {
+        rs.shares[p] = shares[p];
+        rs.aligned &= ((uintptr_t)shares[p] & 15) == 0;
+    }
+    rs.parts = parts;
+    rs.match = ts;
+    auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_TOPK, 1> : masks_mfma_kernel<MASKS_TOPK>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
                        (uint16_t *)nullptr, rs);

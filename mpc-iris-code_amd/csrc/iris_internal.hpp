@@ -158,6 +158,13 @@ struct MatchSink {
     uint64_t *count;   // device counter, zeroed on the stream before the launch
     double threshold;  // never NaN (the API refuses it)
 };
+// A top-k pass (iris_*_topk) takes the same struct, so the kernels keep one signature:
+// buf = lists[units][k], cap = k (1..kTopkMax); count and threshold are unused.  Every unit (a
+// wave that can hold candidates) stores its k best records, best first, empty entries (den = 0)
+// last, at buf[unit * k + j]; launch_topk_merge then folds the lists.
+constexpr uint32_t kTopkMax = 64;    // one list entry per lane
+constexpr uint32_t kTopkFanIn = 64;  // lists one merge workgroup folds into one
+inline MatchSink topk_sink(Partial *lists, uint32_t k) { return MatchSink{lists, k, nullptr, 0.0}; }
 
 // ---------------------------------------------------------------- generator
 // Counter-based synthetic data: limb = splitmix64 output number
@@ -299,6 +306,24 @@ int launch_resolver_match(void *stream, const uint16_t *const *shares, uint32_t 
                           const MatchSink &ms);
 int launch_masks_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
                        const uint16_t *const *shares, uint32_t parts, const MatchSink &ms);
+// Top-k passes (iris_*_topk): the sibling search's streaming loop and dispatch with the wave-
+// resident list (topk_insert, iris_device.hpp) as epilogue; *_topk_units is the number of lists
+// the pass writes.  launch_topk_merge folds `units` lists of k at `lists` level by level
+// (kTopkFanIn lists per workgroup, ping-pong between `lists` and `spare`, which holds
+// topk_spare_lists(units) lists) and writes the final k records to `out`.
+uint64_t mfma_topk_units(const Hooks &h, LaunchRange r);
+uint64_t template_topk_units(LaunchRange r);
+uint64_t resolver_topk_units(uint64_t n);
+uint64_t masks_topk_units(const Hooks &h, LaunchRange r);
+int launch_template_mfma_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                              const MatchSink &ts);
+int launch_template_topk(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ts);
+int launch_resolver_topk(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                         const MatchSink &ts);
+int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                      const uint16_t *const *shares, uint32_t parts, const MatchSink &ts);
+inline uint64_t topk_spare_lists(uint64_t units) { return (units + kTopkFanIn - 1) / kTopkFanIn; }
+int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t units, uint32_t k, Partial *out);
 struct BatchGeometry {
     uint64_t tile0, ntiles;
     uint32_t nqg, G;  // query groups, workgroups per query group

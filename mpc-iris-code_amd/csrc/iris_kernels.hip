@@ -115,7 +115,9 @@ __device__ __forceinline__ Partial wave_best(Partial c) {
 // ------------------------------------------------------------------ template kernel
 
 // MODE_MATCH: the records below ms.threshold are appended to ms (iris_template_matches)
-enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2 };
+// MODE_TOPK: the wave's min(k, 64) best records go to its list ms.buf[wave] (ms = topk_sink,
+// iris_template_topk)
+enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2, MODE_TOPK = 3 };
 
 // Each wave: one 64-record block.  Workgroup: 4 waves.
 template <int MODE>
@@ -193,6 +195,12 @@ __global__ void __launch_bounds__(256, 5)
             const int hr[1] = {c.rot};
             const uint64_t hi[1] = {o};
             append_matches<1>(ms, lane, hit, hn, hd, hr, hi);
+            return;
+        }
+        if constexpr (MODE == MODE_TOPK) {
+            Partial entry = partial_none();
+            topk_insert(entry, (uint32_t)ms.cap, lane, c, valid);
+            topk_store(ms, wave, lane, entry);
             return;
         }
         if (valid && dist_out) dist_out[o] = c.den ? (double)c.num / (double)c.den : __builtin_inf();
@@ -340,6 +348,41 @@ __global__ void __launch_bounds__(256) group_merge_kernel(const Partial *__restr
         if (better(p, c)) c = p;
     }
     out[q] = c;
+}
+
+// Top-k merge (launch_topk_merge): workgroup b folds the lists in[b * kTopkFanIn, +kTopkFanIn)
+// (clipped to nin; k records each, contiguous) into out[b].  The lists' records are read 64 at a
+// time, one per lane, list boundaries ignored -- wave w takes the groups w, w + 4, ..., all its
+// loads issued up front (at most 16 records per lane) -- and go through the same wave-resident
+// list as the passes' epilogue (topk_insert); waves 1..3 then hand their lists to wave 0 through
+// LDS.  The order is total, so the result does not depend on how the records were grouped.
+__global__ void __launch_bounds__(256) topk_merge_kernel(const Partial *__restrict__ in, uint64_t nin, uint32_t k,
+                                                         Partial *__restrict__ out) {
+    constexpr int kGroups = (int)(kTopkFanIn * kTopkMax / 64 / kWaveSlots);  // per wave, at most
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t l0 = (uint64_t)blockIdx.x * kTopkFanIn;
+    const uint64_t l1 = l0 + kTopkFanIn < nin ? l0 + kTopkFanIn : nin;
+    const uint64_t e0 = l0 * k, e1 = l1 * k;
+    Partial c[kGroups];
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+        const uint64_t e = e0 + (uint64_t)(g * kWaveSlots + w) * 64 + lane;
+        c[g] = partial_none();
+        if (e < e1) c[g] = in[e];
+    }
+    Partial entry = partial_none();
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+        if (e0 + (uint64_t)(g * kWaveSlots + w) * 64 >= e1) break;  // wave-uniform
+        topk_insert(entry, k, lane, c[g], true);
+    }
+    __shared__ Partial sh[kWaveSlots - 1][64];
+    if (w) sh[w - 1][lane] = entry;
+    __syncthreads();
+    if (w) return;
+#pragma unroll
+    for (int i = 0; i < kWaveSlots - 1; ++i) topk_insert(entry, k, lane, sh[i][lane], true);
+    if ((uint32_t)lane < k) out[(uint64_t)blockIdx.x * k + lane] = entry;
 }
 
 constexpr uint32_t kReduceChunk = 1024;  // partials per first-stage workgroup
@@ -524,6 +567,35 @@ int launch_template_match(void *stream, const void *db, const void *qtab, Launch
                        (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
                        (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, ms);
     return check_launch();
+}
+
+uint64_t template_topk_units(LaunchRange r) { return block_range(r).grid * kWaveSlots; }
+
+int launch_template_topk(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ts) {
+    if (r.n == 0) return 0;
+    const BlockRange b = block_range(r);
+    hipLaunchKernelGGL(template_kernel<MODE_TOPK>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, ts);
+    return check_launch();
+}
+
+// Folds `units` lists of k records at `lists` into one, kTopkFanIn lists per workgroup and
+// level: level 1 writes to `spare`, level 2 back to the start of `lists` (whose records level 1
+// has consumed), and so on; the last level -- there is always one, a single list is copied --
+// writes the k records (empty ones last, den = 0) to `out`.
+int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t units, uint32_t k, Partial *out) {
+    if (units == 0 || k == 0 || k > kTopkMax) return -1;
+    Partial *src = lists, *dst = spare;
+    for (;;) {
+        const uint64_t groups = topk_spare_lists(units);
+        hipLaunchKernelGGL(topk_merge_kernel, dim3((uint32_t)groups), dim3(256), 0, (hipStream_t)stream,
+                           (const Partial *)src, units, k, groups == 1 ? out : dst);
+        if (check_launch() != 0) return -1;
+        if (groups == 1) return 0;
+        units = groups;
+        std::swap(src, dst);
+    }
 }
 
 // Consumes the partials (a large set is folded in place by a first stage).

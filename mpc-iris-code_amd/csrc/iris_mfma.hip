@@ -75,7 +75,9 @@ __device__ __forceinline__ uint4 stream_load(const uint4 *p) {
 
 // MF_MATCH: every record of the range whose best rotation's f64 distance is below ms.threshold
 // is appended to ms (iris_template_matches); no partials, no reduce
-enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2 };
+// MF_TOPK: the wave's k best records (ms = topk_sink: k = ms.cap) go to its list ms.buf[wave]
+// (iris_template_topk); the running best becomes the wave-resident list, no partials, no reduce
+enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2, MF_TOPK = 3 };
 
 // KS > 1 (small ranges, T = kSplitT): the KS waves of a tile group split K -- wave w computes
 // chunk groups [w' * 100 / KS, +100 / KS) of tiles T * (blockIdx.x * (4 / KS) + w / KS) + t (w' = w % KS)
@@ -209,10 +211,20 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     uint32_t hn[T], hd[T];
     int hr[T];
     uint64_t hi[T];
+    // MF_TOPK recomputes the wave's first tile here from an opaque copy of threadIdx.x: at T = 4 the
+    // main loop has no register to spare, and the 64-bit tile numbers this epilogue needs would
+    // otherwise be spilled across it
+    uint64_t twe = tw, wave_e = wave;
+    if constexpr (MODE == MF_TOPK) {
+        uint32_t tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+        wave_e = (uint64_t)blockIdx.x * (W / KS) + (tx >> 6) / KS;
+        twe = wave_e * T;
+    }
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        const uint64_t t0 = (tile0 + tw + t) * kTileRecs;  // global index of the tile's first template
-        const bool tv = active && (tw + t < ntiles) && slice == 0;
+        const uint64_t t0 = (tile0 + twe + t) * kTileRecs;  // global index of the tile's first template
+        const bool tv = active && (twe + t < ntiles) && slice == 0;
         if constexpr (MODE == MF_COUNTS) {
             __shared__ __attribute__((aligned(16))) uint16_t sh_out[W][1024];
             uint16_t *lds = sh_out[wslot];
@@ -240,6 +252,12 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                 hi[t] = o;
                 continue;
             }
+            if constexpr (MODE == MF_TOPK) {  // den = 0: no candidate (half 0 votes)
+                hn[t] = bn;
+                hd[t] = valid && h == 0 ? bd : 0;
+                hr[t] = br;
+                continue;
+            }
             if (valid && dist_out && h == 0) dist_out[o] = bd ? (double)bn / (double)bd : __builtin_inf();
             Partial c;
             c.num = bn;
@@ -251,6 +269,21 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         }
     }
     if constexpr (MODE == MF_MATCH) append_matches<T>(ms, lane, hit, hn, hd, hr, hi);
+    // MF_TOPK: the tiles' candidates go into the wave's list once the accumulators are dead (best:
+    // this lane's entry).  One list per tile group: with a K-split only slice 0's wave holds sums.
+    if constexpr (MODE == MF_TOPK) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            Partial c;
+            c.num = hn[t];
+            c.den = hd[t];
+            c.rot = hr[t];
+            c.pad = 0;
+            c.idx = (tile0 + twe + t) * kTileRecs + (lane & 31) - first;
+            topk_insert(best, (uint32_t)ms.cap, lane, c, true);
+        }
+        if (slice == 0) topk_store(ms, wave_e, lane, best);
+    }
     if constexpr (MODE == MF_SEARCH) {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
@@ -604,6 +637,25 @@ int launch_template_mfma_match(const Hooks &h, void *stream, const void *db, con
     hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
                        (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, ms);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// lists a top-k pass writes: one per wave that holds sums (a workgroup's one tile group under the K-split)
+uint64_t mfma_topk_units(const Hooks &h, LaunchRange r) {
+    const TileRange t = tile_range(h, r);
+    return t.grid * (uint64_t)(t.ksplit > 1 ? 1 : kWaveSlots);
+}
+
+// the search's dispatch without the fused finish, MF_TOPK epilogue
+int launch_template_mfma_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                              const MatchSink &ts) {
+    if (r.n == 0) return 0;
+    const TileRange t = tile_range(h, r);
+    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_TOPK, kSplitT, 4>
+                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_TOPK, 1> : template_mfma_kernel<MF_TOPK>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, ts);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -51,7 +51,8 @@ constexpr int kSlots = (kWords + 63) / 64;         // 4
 
 // MATCH (iris_resolver_matches): the load and sum path is the search's; after the per-row decode
 // the rows below ms.threshold are appended to ms (idx = row) instead of the argmin.
-template <bool MATCH = false>
+// TOPK (iris_resolver_topk): the wave's k best rows go to its list ms.buf[wave] (ms = topk_sink).
+template <bool MATCH = false, bool TOPK = false>
 __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uint16_t *__restrict__ denoms,
                                                        uint64_t n, double *__restrict__ dist_out,
                                                        Partial *__restrict__ partials, MatchSink ms) {
@@ -117,6 +118,12 @@ __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uin
         append_matches<1>(ms, lane, hit, hn, hd, hr, hi);
         return;
     }
+    if constexpr (TOPK) {
+        Partial entry = partial_none();
+        topk_insert(entry, (uint32_t)ms.cap, lane, c, (uint64_t)lane < rows);
+        topk_store(ms, (uint64_t)blockIdx.x * kWaveSlots + ws, lane, entry);
+        return;
+    }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const Partial o = partial_shfl_xor(c, off);
@@ -157,6 +164,20 @@ int launch_resolver_match(void *stream, const uint16_t *const *shares, uint32_t 
     a.parts = parts;
     hipLaunchKernelGGL(resolver_kernel<true>, dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a, denoms, n,
                        (double *)nullptr, (Partial *)nullptr, ms);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+uint64_t resolver_topk_units(uint64_t n) { return (uint64_t)resolver_partials(n) * kWaveSlots; }
+
+int launch_resolver_topk(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                         const MatchSink &ts) {
+    if (n == 0) return 0;
+    if (parts == 0 || parts > (uint32_t)kMaxParts) return -1;
+    ResolverArgs a{};
+    for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
+    a.parts = parts;
+    hipLaunchKernelGGL((resolver_kernel<false, true>), dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a,
+                       denoms, n, (double *)nullptr, (Partial *)nullptr, ts);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -192,6 +192,14 @@ def load_library(path=None):
                                                    ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
             "iris_template_batch_matches": ([P, P, u64, u64, u64, ctypes.c_double, ctypes.POINTER(Match), u64,
                                              ctypes.POINTER(u64)], ctypes.c_int),
+            "iris_template_topk": ([P, P, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(Match),
+                                    ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "iris_resolver_topk": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.c_uint32,
+                                    ctypes.POINTER(Match), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "iris_resolver_topk_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_uint32,
+                                          ctypes.POINTER(Match), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "iris_topk_merge": ([ctypes.POINTER(Match), u64, ctypes.c_uint32, ctypes.POINTER(Match),
+                                 ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
                                         ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
             "iris_engine_query_tables": ([P, P, ctypes.c_size_t, P, ctypes.c_size_t], ctypes.c_int),
@@ -261,6 +269,7 @@ def exported_symbols():
         "iris_resolver_batch_search_masks",
         "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
         "iris_resolver_batch_matches_masks", "iris_template_batch_matches",
+        "iris_template_topk", "iris_resolver_topk", "iris_resolver_topk_masks", "iris_topk_merge",
     ]
 
 
@@ -517,6 +526,32 @@ def decode_distance(distances, denominators):
     _check(load_library().iris_decode_distance(_ptr(_c(distances, np.uint16)), _ptr(_c(denominators, np.uint16)),
                                                ctypes.byref(out)))
     return out.value
+
+
+TOPK_MAX = 64  # IRIS_TOPK_MAX
+
+
+def _collect_topk(call, k):
+    """Runs call(out, count) on a k-entry array -> the listed entries as a list of Match."""
+    room = max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1
+    arr = (Match * room)()
+    cnt = ctypes.c_uint32(0)
+    _check(call(arr, ctypes.byref(cnt)))
+    return [_copy_match(arr[i]) for i in range(cnt.value)]
+
+
+def _copy_match(m):
+    c = Match()
+    ctypes.memmove(ctypes.byref(c), ctypes.byref(m), ctypes.sizeof(Match))
+    return c
+
+
+def merge_topk(matches, k):
+    """Merges top-k lists that carry global indices (shards, chunks, GPUs) into the k best, best
+    first (iris_topk_merge; host only) -> list[Match]."""
+    matches = list(matches)
+    arr = (Match * max(1, len(matches)))(*matches)
+    return _collect_topk(lambda o, cnt: load_library().iris_topk_merge(arr, len(matches), int(k), o, cnt), k)
 
 
 def merge_matches(matches):
@@ -973,6 +1008,36 @@ class MasksEngine(_Engine):
                 dev.free(p)
 
 
+    def topk(self, db, shares, k, first=0, n=None, index_base=0):
+        """The k closest records of the resolver step, best first (iris_resolver_topk_masks; k has
+        no reference counterpart): shares as in matches().  Indices are index_base + row.
+        -> list[Match] of min(k, rows with a valid rotation) entries."""
+        if n is None:
+            n = len(db) - int(first)
+        dev = self.device
+        tmp = []
+        try:
+            ptrs = []
+            for a in shares:
+                if isinstance(a, int):
+                    ptrs.append(a)
+                    continue
+                a = _c(a, np.uint16)
+                if a.shape != (n, ROTATIONS):
+                    raise IrisError(-1, "shares must be [n, 31] uint16")
+                p = dev.alloc(max(a.nbytes, 16))
+                tmp.append(p)
+                dev.h2d(p, a)
+                ptrs.append(p)
+            arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+            f = load_library().iris_resolver_topk_masks
+            return _collect_topk(lambda o, cnt: f(self.handle, db.handle, int(first), int(n), arr, len(ptrs),
+                                                  int(index_base), int(k), o, cnt), k)
+        finally:
+            for p in tmp:
+                dev.free(p)
+
+
 class DistanceEngine(_Engine):
     """DistanceEngine (src/lib.rs:28-53): out[k] = dot_u16(rot(query, k-15), entry)."""
 
@@ -1049,6 +1114,16 @@ class TemplateEngine(_Engine):
         f = load_library().iris_template_matches
         return _collect_matches(lambda o, c, cnt: f(self.handle, db.handle, int(first), int(n), int(index_base),
                                                     float(threshold), o, c, cnt), cap, out, self)
+
+
+    def topk(self, db, k, first=0, n=None, index_base=0):
+        """The k closest records of the range, best first, in one database pass
+        (iris_template_topk; k = 1..TOPK_MAX has no reference counterpart) -> list[Match] of
+        min(k, records with a valid rotation) entries; [0] is search()'s result."""
+        n = (len(db) - first) if n is None else n
+        f = load_library().iris_template_topk
+        return _collect_topk(lambda o, cnt: f(self.handle, db.handle, int(first), int(n), int(index_base), int(k),
+                                              o, cnt), k)
 
 
 class PendingSearch:
@@ -1515,6 +1590,15 @@ def resolver_matches(device, share_ptrs, denoms_ptr, n, threshold, index_base=0,
                                                 int(index_base), float(threshold), o, c, cnt), cap, out, device)
 
 
+def resolver_topk(device, share_ptrs, denoms_ptr, n, k, index_base=0):
+    """The k closest rows of the resolver's aggregation, best first (iris_resolver_topk; device
+    arrays of n*31 u16; indices are index_base + row) -> list[Match]."""
+    ptrs = (ctypes.c_void_p * len(share_ptrs))(*share_ptrs)
+    f = load_library().iris_resolver_topk
+    return _collect_topk(lambda o, cnt: f(device.handle, ptrs, len(share_ptrs), ctypes.c_void_p(denoms_ptr), int(n),
+                                          int(index_base), int(k), o, cnt), k)
+
+
 # ====================================================================== arch plugin
 
 
@@ -1552,7 +1636,7 @@ def f64_bits(x):
 
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
-    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "dot_bool", "dot_u16",
+    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "TOPK_MAX", "dot_bool", "dot_u16",
     "Group", "GroupDatabase", "GroupPendingSearch",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
