@@ -320,7 +320,8 @@ int iris_template_search(iris_engine_t *engine, const iris_db_t *db, uint64_t fi
  * at once; iris_pending_wait blocks for THAT search only and frees the handle,
  * so the next query's search can be enqueued (and its engine built) while the
  * caller exchanges or consumes this result.  The engine may be destroyed
- * before the wait; the database must stay alive and unmodified until it. */
+ * before the wait; the database must stay alive and unmodified until it.
+ * Results and ordering are as before; a later search of the same records may be partly computed by an earlier pass. */
 int iris_template_search_async(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                                uint64_t index_base, iris_pending_t **out);
 int iris_pending_wait(iris_pending_t *pending, iris_match_t *out);

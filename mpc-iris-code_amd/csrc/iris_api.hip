@@ -67,6 +67,7 @@ int ensure_upin(iris_device *d) {
 int iris_api::db_write_pinned(iris_db *db, uint64_t index, const void *records, uint64_t n, const SlotFill *fill) {
     iris_device *d = db->dev;
     const KindInfo &k = db->k;
+    db_written(db);
     // at least four slots per write (so the host's copy of one overlaps the copy engine's of another)
     const size_t piece = std::min(kUploadSlot, std::max(kUploadPieceMin, (size_t)n * k.rec_bytes / 4));
     const uint64_t ch = std::max<uint64_t>(64, piece / k.rec_bytes / 64 * 64);
@@ -122,6 +123,7 @@ int iris_api::db_store_locked(iris_db *db, uint64_t index, const void *records, 
     if (n > db->cap - index) return fail(IRIS_E_RANGE, "iris_db_write: database capacity exceeded");
     if (n == 0) return 0;
     ARG(records != nullptr, "iris_db_write: records is NULL");
+    db_written(db);
     const KindInfo &k = db->k;
     const size_t bytes = (size_t)n * k.rec_bytes;
     if (d->hooks.upload == 1 && bytes >= kUploadTuneMin) return db_write_pinned(db, index, records, n);
@@ -517,6 +519,7 @@ int readahead_u16_call(iris_engine *e, const iris_db *a, uint64_t first, uint64_
 
 constexpr size_t kQbufAlign = 256;
 constexpr size_t kQpoolMax = 16;
+constexpr size_t kTemplateTabBytes = (size_t)kPlaneDwords * kTemplateTabStride * 4;  // a template engine's LANES table
 
 inline size_t qalign(size_t b) { return (b + kQbufAlign - 1) / kQbufAlign * kQbufAlign; }
 
@@ -553,6 +556,7 @@ void iris_api::engine_free(iris_engine *e) {
         if (d->qpool.size() < kQpoolMax) d->qpool.emplace_back(e->qbuf_bytes, e->qbuf);
         else (void)hipFree(e->qbuf);
     }
+    delete e->host_query;
     delete e;
 }
 
@@ -664,6 +668,15 @@ void device_teardown(iris_device *d) {
             if (d->upin[b]) (void)hipHostFree(d->upin[b]);
             if (d->upin_ev[b]) (void)hipEventDestroy(d->upin_ev[b]);
         }
+        for (SharePass &s : d->share_ring) {
+            if (s.slot) (void)hipFree(s.slot);
+            if (s.done.p) (void)hipFree(s.done.p);
+            if (s.qbuf) (void)hipFree(s.qbuf);
+            if (s.ended) (void)hipEventDestroy(s.ended);
+        }
+        if (d->share_count) (void)hipFree(d->share_count);
+        if (d->share_reg) (void)hipEventDestroy(d->share_reg);
+        if (d->share) (void)hipStreamDestroy(d->share);
         if (d->aux) (void)hipStreamDestroy(d->aux);
         if (d->aux2) (void)hipStreamDestroy(d->aux2);
         if (d->host_result) (void)hipHostFree(d->host_result);
@@ -856,6 +869,20 @@ int iris_device_kernel_stats(iris_device_t *d, const char *kernel, uint64_t *lau
     IRIS_KEEP_DEVICE();
     ARG(d && kernel, "NULL argument");
     std::lock_guard<std::recursive_mutex> g(d->mu);
+    if (!strcmp(kernel, "search_shared")) {
+        // shared passes: launches = searches registered as guests, items = tile groups carried for
+        // them (a device counter, read behind whatever the device stream holds); no time of its own
+        unsigned long long carried = 0;
+        if (d->share_count) {
+            CHK(set_device(d));
+            HIPCHK(hipMemcpyAsync(&carried, d->share_count, sizeof(carried), hipMemcpyDeviceToHost, d->stream));
+            HIPCHK(hipStreamSynchronize(d->stream));
+        }
+        if (launches) *launches = d->share_regs;
+        if (total_ms) *total_ms = 0;
+        if (items) *items = carried;
+        return 0;
+    }
     auto it = d->stats.find(kernel);
     KStat s = it == d->stats.end() ? KStat{} : it->second;
     if (launches) *launches = s.launches;
@@ -882,6 +909,11 @@ int iris_device_reset_stats(iris_device_t *d) {
     std::lock_guard<std::recursive_mutex> g(d->mu);
     d->stats.clear();
     d->ra_launches = d->ra_records = d->ra_window_max = 0;
+    d->share_regs = 0;
+    if (d->share_count) {
+        CHK(set_device(d));
+        HIPCHK(hipMemsetAsync(d->share_count, 0, sizeof(*d->share_count), d->stream));
+    }
     return 0;
 }
 
@@ -937,6 +969,7 @@ int iris_db_create_ex(iris_device_t *d, int kind, uint64_t capacity, int layout,
     iris_db *db = new (std::nothrow) iris_db();
     if (db) db->version = next_db_version();
     if (!db) return fail(IRIS_E_NOMEM, "out of host memory");
+    db_written(db);
     db->dev = d;
     db->k = kind_info(kind, layout);
     const uint64_t blocks = std::max<uint64_t>(1, capacity / db->k.block + (capacity % db->k.block != 0));
@@ -1179,8 +1212,16 @@ int iris_distance_engine_new(iris_device_t *d, const uint16_t query[IRIS_BITS], 
 
 int iris_api::template_engine_locked(iris_device *d, const iris_template_t *query, iris_engine **out) {
     // [LANES table | TILES fragments], both built by one launch
-    return engine_from_host_query(d, IRIS_KIND_TEMPLATES, query, (size_t)kPlaneDwords * kTemplateTabStride * 4,
-                                  kTemplateFragDwords * 4, out, launch_query_template);
+    iris_template_t *copy = new (std::nothrow) iris_template_t(*query);
+    if (!copy) return fail(IRIS_E_NOMEM, "out of host memory");
+    const int rc = engine_from_host_query(d, IRIS_KIND_TEMPLATES, query, kTemplateTabBytes, kTemplateFragDwords * 4,
+                                          out, launch_query_template);
+    if (rc != 0) {
+        delete copy;
+        return rc;
+    }
+    (*out)->host_query = copy;
+    return 0;
 }
 
 extern "C" {
@@ -1350,12 +1391,56 @@ int iris_template_counts(iris_engine_t *e, const iris_db_t *db, uint64_t first, 
 // partials buffers, and `done` (if given) is recorded there after it.
 }  // extern "C"
 
+namespace {
+
+// A ring entry for the sharing pass about to be launched (*out = nullptr: the next entry is still in
+// use, or the device has no memory to spare -- the pass then runs today's kernel and shares nothing).
+int share_take(iris_device *d, uint32_t np, SharePass **out) {
+    *out = nullptr;
+    SharePass &s = d->share_ring[d->share_next];
+    if (s.used) {
+        // its kernel, and the kernel of the pass registered as its guest (whose registration wrote
+        // the slot and whose hosting read qbuf and wrote done), must have ended; an entry taken again
+        // since records a later point of the same stream in `ended`, which says no less
+        if (hipEventQuery(s.ended) != hipSuccess) return 0;
+        if (s.guest >= 0 && hipEventQuery(d->share_ring[s.guest].ended) != hipSuccess) return 0;
+    }
+    if (!d->share) HIPCHK(hipStreamCreateWithFlags(&d->share, hipStreamNonBlocking));
+    if (!d->share_reg) HIPCHK(hipEventCreateWithFlags(&d->share_reg, hipEventDisableTiming));
+    if (!d->share_count) {
+        void *p = nullptr;
+        if (dev_malloc(d, &p, 256, "sharing counter") != 0) return 0;
+        d->share_count = (unsigned long long *)p;
+        HIPCHK(hipMemsetAsync(p, 0, 256, d->stream));
+    }
+    if (!s.ended) HIPCHK(hipEventCreateWithFlags(&s.ended, hipEventDisableTiming));
+    if (!s.slot) {
+        void *p = nullptr;
+        if (dev_malloc(d, &p, 256, "guest slot") != 0) return 0;
+        s.slot = (iris::GuestSlot *)p;
+    }
+    if (!s.qbuf && dev_malloc(d, &s.qbuf, qalign(kTemplateTabBytes) + kTemplateFragDwords * 4, "shared query") != 0)
+        return 0;
+    if (ensure(d, s.done, (size_t)np * sizeof(uint32_t)) != 0) return 0;
+    s.used = true;
+    s.guest = -1;
+    d->share_next = (d->share_next + 1) % kShareRing;
+    *out = &s;
+    return 0;
+}
+
+}  // namespace
+
 int iris_api::search_enqueue(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, double *dist_dev,
                              Partial *dst, bool side, hipEvent_t done, uint64_t idx_base, uint32_t *host_done,
-                             uint32_t seq, bool *flagged) {
+                             uint32_t seq, bool *flagged, bool share) {
     iris_device *d = e->dev;
     if (flagged) *flagged = false;
     if (n == 0) return 0;
+    // only the latest search pass of the device can host, and only if this call finds it to be one
+    // of the sharing form (set again below)
+    const int share_host = d->share_last;
+    d->share_last = -1;
     LaunchRange r{first, n};
     const int layout = db->k.layout;
     if (layout == IRIS_LAYOUT_TILES && fused_search_ok(d->hooks, r)) {
@@ -1397,11 +1482,64 @@ int iris_api::search_enqueue(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     CHK(ensure(d, *buf, pbytes));
     Partial *part = (Partial *)buf->p;
     uint32_t written = 0;
-    CHK(timed(d, "template_search", n, [&] {
-        if (layout == IRIS_LAYOUT_TILES)
-            return launch_template_mfma_search(d->hooks, d->stream, db->data, e->qfrag, r, dist_dev, part, &written);
-        return launch_template_search(d->stream, db->data, e->qtab, r, dist_dev, part, &written);
-    }));
+    // the sharing form: asynchronous searches of large TILES ranges
+    const bool share_form = share && side && layout == IRIS_LAYOUT_TILES && !dist_dev && e->host_query &&
+                            share_search_ok(d->hooks, r);
+    if (share_form) {
+        SharePass *sp = nullptr;
+        if (d->hooks.search_share) CHK(share_take(d, np, &sp));
+        bool guest = false;
+        if (sp) {
+            sp->db = db;
+            sp->writes = db->writes;
+            sp->first = first;
+            sp->n = n;
+            // the pass before this one hosts it if it searches the same records of the same
+            // database, unwritten since, has no guest yet and has not ended
+            SharePass *host = share_host >= 0 ? &d->share_ring[share_host] : nullptr;
+            guest = host && host != sp && host->guest < 0 && host->db == db && host->writes == db->writes &&
+                    host->first == first && host->n == n && hipEventQuery(host->ended) == hipErrorNotReady;
+            // on the sharing stream: behind the reduce that last read this search's partials buffer,
+            // the slot (and done words) zeroed, then, for a guest, its fragments built from the
+            // engine's host copy of the query (the engine's own buffer is built in device-stream
+            // order, behind the running pass) and the slot of the hosting pass published
+            HIPCHK(hipStreamWaitEvent(d->share, d->apart_read[b], 0));
+            if (launch_share_prepare(d->share, sp->slot, guest ? (uint32_t *)sp->done.p : nullptr, np) != 0)
+                return fail(IRIS_E_HIP, "kernel launch failed: share_prepare");
+            if (guest) {
+                uint32_t *tab = (uint32_t *)sp->qbuf;
+                uint32_t *frag = (uint32_t *)((char *)sp->qbuf + qalign(kTemplateTabBytes));
+                if (launch_query_template(d->share, e->host_query, tab, frag) != 0 ||
+                    launch_share_publish(d->share, host->slot, frag, part, (uint32_t *)sp->done.p) != 0)
+                    return fail(IRIS_E_HIP, "kernel launch failed: share_publish");
+                host->guest = (int)(sp - d->share_ring);
+                d->share_regs += 1;
+            }
+            HIPCHK(hipEventRecord(d->share_reg, d->share));
+            HIPCHK(hipStreamWaitEvent(d->stream, d->share_reg, 0));
+            if (d->hooks.search_share_delay_us) {  // test hook: the next registration lands before this pass starts
+                int khz = 0;
+                HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d->ordinal));
+                if (launch_share_delay(d->stream, (uint64_t)d->hooks.search_share_delay_us * khz / 1000) != 0)
+                    return fail(IRIS_E_HIP, "kernel launch failed: share_delay");
+            }
+        }
+        CHK(timed(d, "template_search", n, [&] {
+            return launch_template_share_search(d->hooks, d->stream, db->data, e->qfrag, r, part, &written,
+                                                sp ? sp->slot : nullptr, guest ? (const uint32_t *)sp->done.p : nullptr,
+                                                sp ? d->share_count : nullptr);
+        }));
+        if (sp) {
+            HIPCHK(hipEventRecord(sp->ended, d->stream));
+            d->share_last = (int)(sp - d->share_ring);
+        }
+    } else {
+        CHK(timed(d, "template_search", n, [&] {
+            if (layout == IRIS_LAYOUT_TILES)
+                return launch_template_mfma_search(d->hooks, d->stream, db->data, e->qfrag, r, dist_dev, part, &written);
+            return launch_template_search(d->stream, db->data, e->qtab, r, dist_dev, part, &written);
+        }));
+    }
     if (!side)  // the reduce writes the winner straight into pinned host memory: no copy before the wait
         return timed(d, "reduce", written, [&] { return launch_reduce(d->stream, part, written, dst, idx_base); });
     HIPCHK(hipEventRecord(d->apart_written[b], d->stream));
@@ -1563,7 +1701,7 @@ int iris_template_search_async(iris_engine_t *e, const iris_db_t *db, uint64_t f
         p->ev = take_event(d);
         if (!p->ev) rc = fail(IRIS_E_HIP, "hipEventCreate failed");
     }
-    if (rc == 0) rc = search_enqueue(e, db, first, n, nullptr, p->slot, true, p->ev);
+    if (rc == 0) rc = search_enqueue(e, db, first, n, nullptr, p->slot, true, p->ev, 0, nullptr, 0, nullptr, true);
     if (rc != 0) {
         if (p->slot) d->free_slots.push_back(p->slot);
         if (p->ev) d->event_pool.push_back(p->ev);

@@ -90,6 +90,21 @@ struct UploadTune {
     }
 };
 
+// Shared passes (iris_template_search_async over large TILES ranges): what one such
+// pass owns on the device.  The entries form a ring; one is taken again only once its own pass and
+// the pass that registered as its guest (the only other one that touches it) have ended.
+constexpr int kShareRing = 8;
+struct SharePass {
+    iris::GuestSlot *slot = nullptr;  // this pass's guest slot, read by its kernel
+    DevBuf done;                      // as a guest: the words the hosting pass sets, read by this pass's kernel
+    void *qbuf = nullptr;             // as a guest: [table | fragments] of the query, read by the hosting pass
+    hipEvent_t ended = nullptr;       // recorded on the device stream after this pass's kernel
+    bool used = false;
+    int guest = -1;                   // ring index of the pass registered as this one's guest
+    const struct iris_db *db = nullptr;  // what the pass searches: a guest must ask for the same
+    uint64_t writes = 0, first = 0, n = 0;
+};
+
 struct iris_device {
     int ordinal = 0;
     int numa_node = -1;  // host NUMA node of the device's PCI function (-1: unknown)
@@ -132,6 +147,16 @@ struct iris_device {
     DevBuf apart[2];
     hipEvent_t apart_read[2] = {nullptr, nullptr}, apart_written[2] = {nullptr, nullptr};
     int apart_next = 0;
+    // shared passes: the ring, the latest pass that may still take a guest (-1: none), the stream
+    // registrations run on (the side stream waits behind the running pass, so it cannot carry them),
+    // the event that orders a pass behind its registration, and the device counter of tile groups
+    // carried for guests (kernel stats "search_shared", with the registrations as its launches)
+    SharePass share_ring[kShareRing];
+    int share_next = 0, share_last = -1;
+    hipStream_t share = nullptr;
+    hipEvent_t share_reg = nullptr;
+    unsigned long long *share_count = nullptr;
+    uint64_t share_regs = 0;
     // handles alive on this device (1 for the device handle itself + 1 per database
     // and engine handle): the device is torn down when the last one is released,
     // so handles may be destroyed in any order
@@ -183,7 +208,15 @@ struct iris_db {
     // process-unique, renewed by every change of the records (db_detach) and every attachment:
     // an engine's read-ahead rows are valid for one version of one database
     uint64_t version = 0;
+    // process-unique, renewed by every call that enqueues a store into the records (db_written): a
+    // running search pass computes for a later search only if this has not changed since its launch
+    uint64_t writes = 0;
 };
+
+inline void db_written(iris_db *db) {
+    static std::atomic<uint64_t> w{0};
+    db->writes = ++w;
+}
 
 inline uint64_t next_db_version() {
     static std::atomic<uint64_t> v{0};
@@ -224,6 +257,7 @@ struct iris_engine {
     size_t qbuf_bytes = 0;
     void *qtab = nullptr;     // SGPR rotated-query table (LANES kernels)
     void *qfrag = nullptr;    // MFMA query fragments (TILES kernels)
+    iris_template_t *host_query = nullptr;  // template engines: the query (a shared pass builds its own fragments from it)
     uint32_t nq = 0;          // > 0: batched template engine (qfrag = nq padded query tiles)
     std::vector<iris_engine *> sub;  // streaming batched engine: one single-query engine per query
     Readahead ra;             // masks / distance engines: host-slice calls on attached databases
@@ -392,6 +426,7 @@ inline int sync(iris_device *d) {
     HIPCHK(hipStreamSynchronize(d->stream));
     if (d->aux) HIPCHK(hipStreamSynchronize(d->aux));
     if (d->aux2) HIPCHK(hipStreamSynchronize(d->aux2));
+    if (d->share) HIPCHK(hipStreamSynchronize(d->share));
     fold_done(d);
     return 0;
 }
@@ -409,6 +444,7 @@ inline int check_kind(int kind) {
 // Any change to a database's records ends its host attachment (caller holds the device lock).
 inline void db_detach(iris_db *db) {
     db->version = next_db_version();  // read-ahead rows of the old records no longer match
+    db_written(db);
     if (!db->host_base) return;
     auto &v = db->dev->attached;
     v.erase(std::remove(v.begin(), v.end(), db), v.end());
@@ -433,6 +469,7 @@ inline int ensure_aux(iris_device *d) {
 inline void side_sync(iris_device *d) {
     if (d->aux) (void)hipStreamSynchronize(d->aux);
     if (d->aux2) (void)hipStreamSynchronize(d->aux2);
+    if (d->share) (void)hipStreamSynchronize(d->share);
 }
 
 // Shared by the API translation units (defined in iris_api.hip).
@@ -445,11 +482,13 @@ int template_engine_locked(iris_device *d, const iris_template_t *query, iris_en
 // range-relative index + idx_base) lands in `dst` (pinned host or device memory); nothing
 // waits.  side = true: the reduce runs on the device's side stream over one of two
 // alternating partials buffers, and `done` (if given) is recorded there after it.
+// share = true (iris_template_search_async): a large TILES range runs the sharing kernel and may
+// be computed in part by the pass before it (SharePass).
 // host_done / seq: the fused small-range form also stores seq into the coherent host word
 // host_done after writing dst; *flagged reports whether that form ran (else nothing is stored).
 int search_enqueue(iris_engine *e, const iris_db *db, uint64_t first, uint64_t n, double *dist_dev, iris::Partial *dst,
                    bool side = false, hipEvent_t done = nullptr, uint64_t idx_base = 0, uint32_t *host_done = nullptr,
-                   uint32_t seq = 0, bool *flagged = nullptr);
+                   uint32_t seq = 0, bool *flagged = nullptr, bool share = false);
 // Fills dst with the source bytes [off, off + bytes) of a write; false on a read error (errno set).
 using SlotFill = std::function<bool(void *dst, size_t off, size_t bytes)>;
 // Stores host records [0, n) at database index `index` through two pinned 64-MB slots the helper

@@ -520,7 +520,8 @@ constexpr const char *kHookNames[] = {"IRIS_TILES_PER_WAVE",  "IRIS_FUSED_REDUCE
                                       "IRIS_SCHEDULE",        "IRIS_LOAD_PREAD",   "IRIS_GROUP_DELAY_US",
                                       "IRIS_GROUP_STALL",     "IRIS_GROUP_UNORDERED", "IRIS_UPLOAD",
                                       "IRIS_LOAD_WINDOWS",    "IRIS_READAHEAD_WINDOW", "IRIS_RESIDENT_BUDGET_MB",
-                                      "IRIS_READAHEAD_PACKED", "IRIS_READAHEAD_WINDOW_MAX"};
+                                      "IRIS_READAHEAD_PACKED", "IRIS_READAHEAD_WINDOW_MAX", "IRIS_SEARCH_SHARE",
+                                      "IRIS_SEARCH_SHARE_DELAY_US"};
 constexpr int kNumHooks = (int)(sizeof(kHookNames) / sizeof(kHookNames[0]));
 
 const char *env(const char *name) {
@@ -565,6 +566,8 @@ void read_hooks(Hooks *h) {
         case 11: h->resident_budget_mb = env_u32(v, 1u << 30); break;
         case 12: h->ra_packed = v[0] != '0'; break;
         case 13: h->ra_window_max = env_u32(v, 1024); break;
+        case 14: h->search_share = v[0] != '0'; break;
+        case 15: h->search_share_delay_us = env_u32(v, 1000000); break;
         }
     }
 }
@@ -590,7 +593,9 @@ size_t format_hooks(const Hooks &h, char *buf, size_t len) {
              " readahead_window_max=" + std::to_string(h.ra_window_max) +
              " group_delay_us=" + std::to_string(h.group_delay_us) +
              " group_stall=" + std::to_string(h.group_stall) + " group_unordered=" + std::to_string(h.group_unordered) +
-             " upload=" + upload_names[h.upload & 3];
+             " upload=" + upload_names[h.upload & 3] +
+             " search_share=" + std::to_string(h.search_share) +
+             " search_share_delay_us=" + std::to_string(h.search_share_delay_us);
     std::string ign;
     for (int i = 0; i < kNumHooks; ++i)
         if (h.ignored >> i & 1u) ign += (ign.empty() ? "" : ",") + std::string(kHookNames[i]);

@@ -210,6 +210,8 @@ struct Hooks {
     uint32_t resident_budget_mb = 0; // IRIS_RESIDENT_BUDGET_MB: resident copies hold at most this (0: free memory)
     bool ra_packed = true;           // IRIS_READAHEAD_PACKED=0: masks read-ahead rows cross the host link unpacked
     uint32_t ra_window_max = 0;      // IRIS_READAHEAD_WINDOW_MAX=1..1024: cap of a read-ahead window, chunks (0: by records)
+    bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches never register as guests
+    uint32_t search_share_delay_us = 0;  // IRIS_SEARCH_SHARE_DELAY_US: device-stream spin ahead of a pass that can host
     uint32_t ignored = 0;            // bit i: test hook kHookNames[i] was set without IRIS_TEST_HOOKS=1
 };
 // The bound of forming a device group when IRIS_GROUP_TIMEOUT_MS is not set (iris_group.hip)
@@ -268,6 +270,32 @@ bool fused_search_ok(const Hooks &h, LaunchRange r);
 int launch_template_mfma_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, double *dist_out,
                                 Partial *partials, uint32_t *n_partials, const FusedFinish *fin = nullptr);
 uint32_t mfma_search_partials(const Hooks &h, LaunchRange r);
+// Shared passes (iris_template_search_async): while a pass streams the database, a
+// later search of the same range may register as its guest; every workgroup that starts after that
+// computes both queries for its 16 tiles from one read of them, writes both partials and marks its
+// tile group in the guest's done array, and the guest's own launch skips the groups marked there.
+// The slot is device memory, zeroed before the hosting pass's launch and written once by
+// launch_share_publish (the fields, then ready with agent-scope release).
+struct GuestSlot {
+    uint32_t ready;
+    uint32_t pad;
+    const void *frag;   // the guest's query fragments (a buffer of the sharing ring, not the engine's)
+    Partial *partials;  // the guest's partials buffer
+    uint32_t *done;     // the guest's done array, one word per workgroup
+};
+// whether a range runs the form that can share: 4 tiles per wave, no K-split, separate reduce
+bool share_search_ok(const Hooks &h, LaunchRange r);
+// The sharing form of the search: slot = this pass's guest slot (NULL: never hosts), own_done =
+// NULL or the words an earlier pass set for the tile groups it computed for this query, count =
+// NULL or a device counter of tile groups carried for guests.
+int launch_template_share_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                                 Partial *partials, uint32_t *n_partials, const GuestSlot *slot,
+                                 const uint32_t *own_done, unsigned long long *count);
+// zeroes a pass's guest slot and, if given, its done array of n words
+int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n);
+int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done);
+// test hook IRIS_SEARCH_SHARE_DELAY_US: a one-thread kernel that spins for `ticks` of the wall clock
+int launch_share_delay(void *stream, uint64_t ticks);
 // nq = 2 queries per streamed pass; partials [nq][*n_partials]
 uint32_t multi_search_partials(LaunchRange r, int nq);
 int launch_template_multi_search(void *stream, const void *db, const void *const *qfrags, int nq, LaunchRange r,

@@ -431,6 +431,229 @@ __global__ void __launch_bounds__(256, 2)
     }
 }
 
+// ------------------------------------------------------------------ shared passes
+
+// One round of a sharing pass: NQ queries against the T tiles from tw (relative to tile0), the
+// streaming loop and epilogue of template_mfma_kernel<MF_SEARCH> (NQ = 1, T = 4) and of
+// template_multi_kernel<2> (NQ = 2, T = 2); the round's candidates are folded into best[].
+// Query fragments as pointers into global memory by type: the guest's pointer comes out of LDS, and
+// as a generic pointer its loads would be flat ones, behind which every wait drains the whole
+// load queue -- the prefetch ring of both paths would collapse.
+typedef const __attribute__((address_space(1))) u32x4 *GlobalFrag;
+__device__ __forceinline__ uint4 frag_load(GlobalFrag p) {
+    const u32x4 v = *p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+template <int NQ, int T>
+__device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[NQ], uint64_t tile0,
+                                            uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
+                                            Partial (&best)[NQ]) {
+    const bool active = tw < ntiles;  // wave-uniform
+    v16f den[NQ][T], s[NQ][T];
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi)
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                den[qi][t][i] = 0.f;
+                s[qi][t][i] = 0.f;
+            }
+
+    if (active) {
+        const uint4 *dp[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint64_t rel = (tw + t < ntiles) ? tw + t : ntiles - 1;  // clamp: extra tiles re-read a valid one
+            dp[t] = db + (tile0 + rel) * (uint64_t)kTileUint4 + lane;
+        }
+        struct Stage {
+            uint4 d[T];
+            uint4 q[NQ][2];
+        };
+        auto load = [&](Stage &st, int g) {
+            g = g < kPlaneGroups ? g : kPlaneGroups - 1;
+#pragma unroll
+            for (int t = 0; t < T; ++t) st.d[t] = stream_load(dp[t] + g * 64);
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) {
+                st.q[qi][0] = frag_load(qf[qi] + (2 * g) * 64 + lane);
+                st.q[qi][1] = frag_load(qf[qi] + (2 * g + 1) * 64 + lane);
+            }
+            __builtin_amdgcn_sched_barrier(0);  // as in template_mfma_kernel: the stage's loads stay together
+        };
+        auto compute = [&](const Stage &st) {
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) {
+                const QFrag f0 = qfrag_of(st.q[qi][0]);
+#pragma unroll
+                for (int t = 0; t < T; ++t) chunk_step(st.d[t].x, st.d[t].y, f0, den[qi][t], s[qi][t]);
+                const QFrag f1 = qfrag_of(st.q[qi][1]);
+#pragma unroll
+                for (int t = 0; t < T; ++t) chunk_step(st.d[t].z, st.d[t].w, f1, den[qi][t], s[qi][t]);
+            }
+        };
+        Stage sa, sb, sc;
+        load(sa, 0);
+        load(sb, 1);
+        int g = 0;
+#pragma unroll 1
+        for (; g + 3 <= kPlaneGroups; g += 3) {
+            load(sc, g + 2);
+            compute(sa);
+            load(sa, g + 3);
+            compute(sb);
+            load(sb, g + 4);
+            compute(sc);
+        }
+        if constexpr (kPlaneGroups % 3 >= 1) compute(sa);
+        if constexpr (kPlaneGroups % 3 == 2) compute(sb);
+    }
+
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+        const bool valid = active && (tw + t < ntiles) && tg >= first && tg < end;
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) {
+            uint32_t bn, bd;
+            int br;
+            best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
+                dd = (uint32_t)den[qi][t][r];
+                nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);  // num = (den - S) / 2
+            }, bn, bd, br);
+            Partial c;
+            c.num = bn;
+            c.den = valid ? bd : 0;
+            c.rot = br;
+            c.pad = 0;
+            c.idx = tg - first;
+            if (partial_better_dev(c, best[qi])) best[qi] = c;
+        }
+    }
+}
+
+// A round's bests of NQ queries -> the wave's entries sh[qi * N + pos] (LDS: nothing of a round
+// stays in registers across the next one).
+template <int NQ, int N>
+__device__ __forceinline__ void share_stash(Partial (&best)[NQ], int lane, int pos, Partial *sh) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const Partial ot = partial_shfl_xor(best[qi], off);
+            if (partial_better_dev(ot, best[qi])) best[qi] = ot;
+        }
+        if (lane == 0) sh[qi * N + pos] = best[qi];
+    }
+}
+
+// The N stashed entries of query threadIdx.x < NQ -> its Partial in out[qi][blockIdx.x] (global by
+// type, as the fragments: no flat store either).
+typedef __attribute__((address_space(1))) Partial *GlobalPartial;
+template <int NQ, int N>
+__device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPartial (&out)[NQ]) {
+    __syncthreads();
+    if (threadIdx.x < NQ) {
+        const int qi = threadIdx.x;
+        Partial b = sh[qi * N];
+#pragma unroll
+        for (int w = 1; w < N; ++w)
+            if (partial_better_dev(sh[qi * N + w], b)) b = sh[qi * N + w];
+        const GlobalPartial o = out[qi] + blockIdx.x;
+        o->num = b.num;
+        o->den = b.den;
+        o->rot = b.rot;
+        o->pad = b.pad;
+        o->idx = b.idx;
+    }
+}
+
+// The search of iris_template_search_async over large TILES ranges (4 tiles per wave, separate
+// reduce).  Each workgroup decides at its start, from words another stream may write while the
+// pass runs: its tile group was computed for this query by the pass that hosted it (own_done) ->
+// nothing to do; a guest has been published in the slot -> both queries for the workgroup's 16
+// tiles in the two-query shape (2 tiles x 2 queries per wave, twice), both partials, then the
+// guest's done word; else the single-query pass.
+__global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
+    template_share_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, uint64_t tile0, uint64_t ntiles,
+                          uint64_t first, uint64_t end, Partial *__restrict__ partials, const GuestSlot *slot,
+                          const uint32_t *own_done, unsigned long long *count) {
+    // one thread reads the words (agent-scope acquire: a plain load could be served from the scalar
+    // cache) and the slot's fields behind them; LDS makes the decision the same for every wave
+    __shared__ uint32_t sh_flag[2];
+    __shared__ uint64_t sh_guest[3];
+    if (threadIdx.x == 0) {
+        const uint32_t dn =
+            own_done ? __hip_atomic_load(own_done + blockIdx.x, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        uint32_t rdy = 0;
+        if (slot && !dn) rdy = __hip_atomic_load(&slot->ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (rdy) {
+            sh_guest[0] = (uint64_t)slot->frag;
+            sh_guest[1] = (uint64_t)slot->partials;
+            sh_guest[2] = (uint64_t)slot->done;
+        }
+        sh_flag[0] = dn;
+        sh_flag[1] = rdy;
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(sh_flag[0])) return;
+    const bool shared = __builtin_amdgcn_readfirstlane(sh_flag[1]) != 0;
+    const int lane = threadIdx.x & 63;
+    const int wslot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: kept in SGPRs
+    const uint64_t tw = ((uint64_t)blockIdx.x * kWaveSlots + wslot) * kMfmaTiles;
+    auto uniform64 = [](uint64_t v) {  // the builtin returns int: each half goes through uint32_t, unextended
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+        return (uint64_t)hi << 32 | lo;
+    };
+    constexpr int kRounds = kMfmaTiles / 2;
+    __shared__ Partial sh_best[2 * kRounds * kWaveSlots];
+    if (!shared) {
+        Partial best[1] = {partial_none()};
+        const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
+        share_round<1, kMfmaTiles>(db, qf, tile0, ntiles, tw, first, end, lane, best);
+        share_stash<1, kWaveSlots>(best, lane, wslot, sh_best);
+        const GlobalPartial out[1] = {(GlobalPartial)partials};
+        share_finish<1, kWaveSlots>(sh_best, out);
+        return;
+    }
+    const GlobalFrag qf[2] = {(GlobalFrag)qfrag, (GlobalFrag)uniform64(sh_guest[0])};
+#pragma unroll  // two copies of the loop: kept as a loop, the round counter and tile numbers spill
+    for (int rd = 0; rd < kRounds; ++rd) {
+        Partial best[2] = {partial_none(), partial_none()};
+        share_round<2, 2>(db, qf, tile0, ntiles, tw + 2 * rd, first, end, lane, best);
+        share_stash<2, kRounds * kWaveSlots>(best, lane, rd * kWaveSlots + wslot, sh_best);
+    }
+    const GlobalPartial out[2] = {(GlobalPartial)partials, (GlobalPartial)uniform64(sh_guest[1])};
+    __attribute__((address_space(1))) uint32_t *const guest_done =
+        (__attribute__((address_space(1))) uint32_t *)uniform64(sh_guest[2]);
+    share_finish<2, kRounds * kWaveSlots>(sh_best, out);
+    if (threadIdx.x == 1) {  // the thread that stored the guest's partial
+        __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (count) atomicAdd(count, 1ull);
+    }
+}
+
+__global__ void share_prepare_kernel(GuestSlot *slot, uint32_t *done, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *slot = GuestSlot{};
+    if (done && i < n) done[i] = 0;
+}
+
+__global__ void share_publish_kernel(GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done) {
+    slot->frag = frag;
+    slot->partials = partials;
+    slot->done = done;
+    __hip_atomic_store(&slot->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void share_delay_kernel(uint64_t ticks) {
+    const uint64_t t0 = wall_clock64();
+    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
+}
+
 // ------------------------------------------------------------------ TILES layout plumbing
 
 // reference Template record (pattern dwords 0..399, mask dwords 400..799) ->
@@ -624,6 +847,40 @@ int launch_template_mfma_search(const Hooks &h, void *stream, const void *db, co
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
                        (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials, fin ? *fin : FusedFinish{},
                        MatchSink{});
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+bool share_search_ok(const Hooks &h, LaunchRange r) {
+    if (r.n == 0 || fused_search_ok(h, r)) return false;
+    const TileRange t = search_range(h, r);
+    return t.ksplit == 1 && t.tiles_per_wave == kMfmaTiles;
+}
+
+int launch_template_share_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                                 Partial *partials, uint32_t *n_partials, const GuestSlot *slot,
+                                 const uint32_t *own_done, unsigned long long *count) {
+    if (!share_search_ok(h, r)) return -1;  // the caller asks first
+    const TileRange t = search_range(h, r);
+    *n_partials = (uint32_t)t.grid;
+    hipLaunchKernelGGL(template_share_kernel, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, partials,
+                       slot, own_done, count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n) {
+    const uint32_t words = done ? (n ? n : 1) : 1;
+    hipLaunchKernelGGL(share_prepare_kernel, dim3((words + 255) / 256), dim3(256), 0, (hipStream_t)stream, slot, done, n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done) {
+    hipLaunchKernelGGL(share_publish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, partials, done);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_share_delay(void *stream, uint64_t ticks) {
+    hipLaunchKernelGGL(share_delay_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ticks);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

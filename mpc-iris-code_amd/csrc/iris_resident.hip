@@ -281,6 +281,7 @@ Resident *make_resident(iris_device *d, int kind, uintptr_t p, uint64_t n) {
     r->db->cap = blocks * k.block;
     r->db->len = nrec;  // every record is addressable; only uploaded granules are ever computed on
     r->db->version = next_db_version();
+    db_written(r->db);
     r->kind = kind;
     r->lo = v.lo;
     r->hi = v.hi;
