@@ -75,6 +75,28 @@ def test_prepare_c_vs_numpy_and_identity():
             assert (s_c[0][0] != s_c[0][1]).any()         # distinct keystream per template
 
 
+def test_prepare_c_vs_numpy_high_words():
+    """The two restatements agree where the block counter crosses 2^32 (3 parties from global
+    index 2^32 // 800 - 30: word 13 goes from 0 to 1 inside the range) and where the index
+    and the nonce both have high words; the device tests lean on the C one there."""
+    key = bytes(range(7, 39))
+    g0 = 2**32 // 800 - 30
+    assert g0 == 5_368_679 and g0 * 2 * 400 < 2**32 < ((g0 + 59) * 2 + 1) * 400 + 399
+    for parties, base, n, nonce in ((3, g0, 60, 11), (5, 2**40 + 3, 3, 0xDEADBEEF12345678)):
+        t = oc.gen_templates(31, 0, n)
+        s_c, m_c = oc.prepare_shares(t, key, nonce=nonce, parties=parties, index_base=base)
+        s_n, m_n = on.prepare_shares(t, key, nonce=nonce, parties=parties, index_base=base)
+        assert (s_c == s_n).all() and (m_c == m_n).all() and (m_c == t[:, 200:]).all()
+
+
+def test_prepare_identity_64_parties():
+    t = oc.gen_templates(12, 0, 3)
+    s, m = oc.prepare_shares(t, bytes(range(7, 39)), nonce=11, parties=64, index_base=1000)
+    assert s.shape == (64, 3, 12800) and (m == t[:, 200:]).all()
+    assert (s.astype(np.uint64).sum(axis=0) % 65536 == np.stack([oc.encode(x) for x in t])).all()
+    assert len({s[j].tobytes() for j in range(64)}) == 64  # no two parties share a stream
+
+
 def test_prepare_stream_independent_of_batching():
     """Template g's shares depend only on (key, nonce, g): preparing [0, 4) at once equals
     preparing each template alone at its index (what lets shards prepare independently)."""
