@@ -423,6 +423,41 @@ impl MasksBatchEngine {
             })
             .collect())
     }
+
+    /// Every query's k closest records of that step, best first, in one pass over the masks
+    /// (iris_resolver_batch_topk_masks; k = 1..=ffi::IRIS_TOPK_MAX has no reference counterpart):
+    /// entry q is what `MasksEngine::topk` gives for query q on slab q of every part.
+    pub fn batch_topk(
+        &self,
+        masks: &Database,
+        first: u64,
+        n: u64,
+        shares_device: &[*const u16],
+        k: u32,
+    ) -> Result<Vec<Vec<(f64, usize)>>> {
+        let room = k.clamp(1, ffi::IRIS_TOPK_MAX) as usize;
+        let mut buf = vec![ffi::IrisMatch::default(); self.nq * room];
+        let mut counts = vec![0u32; self.nq];
+        check(unsafe {
+            ffi::iris_resolver_batch_topk_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                0,
+                k,
+                buf.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        })?;
+        Ok(counts
+            .iter()
+            .enumerate()
+            .map(|(q, &c)| buf[q * room..q * room + c as usize].iter().map(match_to_pair).collect())
+            .collect())
+    }
 }
 
 /// `distances` (src/lib.rs:82-87).

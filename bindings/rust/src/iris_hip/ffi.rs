@@ -358,6 +358,18 @@ extern "C" {
         out: *mut IrisMatch,
         count: *mut u32,
     ) -> c_int;
+    pub fn iris_resolver_batch_topk_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        k: u32,
+        out: *mut IrisMatch,
+        counts: *mut u32,
+    ) -> c_int;
     pub fn iris_topk_merge(
         records: *const IrisMatch,
         nrecords: u64,

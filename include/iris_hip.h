@@ -547,10 +547,13 @@ int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint
  * with k, and that the entries below a threshold are the sibling *_matches list.
  *
  * The value arguments (k, out, count) are checked before the handles; engine-kind, database,
- * layout and range checks and the locking are the sibling search's; a batch engine is refused.
- * There is no dist_out_device.  The bytes copied back per call are 24 k, whatever n is.
+ * layout and range checks and the locking are the sibling search's; the single-query calls refuse
+ * a batch engine (a masks batch engine has iris_resolver_batch_topk_masks below).  There is no
+ * dist_out_device.  The bytes copied back per call are 24 k per query, whatever n is.
  *
- * Out of scope: the batch engines, the host-array forms (*_host), the asynchronous pipeline,
+ * Out of scope: of the batch engines, the distance batch engine (its rows are shares, no
+ * distances) and the template batch engine (a follow-up; the masks batch engine has
+ * iris_resolver_batch_topk_masks); the host-array forms (*_host), the asynchronous pipeline,
  * device groups (iris_topk_merge below is the hand-sharding answer) and k > 64. */
 #define IRIS_TOPK_MAX 64
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
@@ -567,6 +570,33 @@ int iris_resolver_topk(iris_device_t *dev, const uint16_t *const *shares_device,
 int iris_resolver_topk_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
                              const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
                              uint32_t k, iris_match_t *out, uint32_t *count);
+/* iris_resolver_batch_search_masks' sibling, for a masks batch engine (iris_masks_batch_engine_new,
+ * nq = 1..64): the k closest records of every query in one pass over masks records
+ * [first, first+n) (src/main.rs:510-519 + 597-621 per query; rotations folded as in
+ * src/template.rs:43-47; k has no reference counterpart).  The inputs are
+ * iris_resolver_batch_search_masks': shares_device[p] is participant p's query-major DEVICE array
+ * of nq*n*31 uint16_t (parts = 1..8).  One k (1..IRIS_TOPK_MAX) for the whole batch.
+ *
+ * out: host array of nq*k iris_match_t, query-major; counts (required): host array of nq uint32_t,
+ * counts[q] = min(k, records of the range with a valid rotation for query q).  out[q*k + j],
+ * j < counts[q], are the first records of the search order, best first, each filled as
+ * iris_resolver_topk_masks fills it (index = index_base + row within the range, reserved = 0);
+ * entries past a query's count are left untouched.  n == 0 sets every count to 0.
+ *
+ * Contract: query q's list and count are byte for byte what iris_resolver_topk_masks returns for
+ * MasksEngine(query_masks[q]) with slab q of every part.  It follows that out[q*k] is
+ * iris_resolver_batch_search_masks' result for q, that a smaller k returns per-query prefixes and
+ * that identical calls return identical bytes.  The value arguments (k, out, counts, parts) are
+ * checked before the handles; engine, database and range checks are
+ * iris_resolver_batch_search_masks'.  There is no dist_out_device.
+ *
+ * On TILES ranges the batch kernel runs (past 1024 tiles) the masks are read once per group of up
+ * to four queries, every wave keeping one resident list per query; elsewhere each query runs
+ * iris_resolver_topk_masks' own pass on its slab.  The call waits once and copies back 24 k bytes
+ * per query. */
+int iris_resolver_batch_topk_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                   const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                   uint32_t k, iris_match_t *out, uint32_t *counts);
 /* Host only, no device: merges top-k lists (of shards, chunks, GPUs) that carry global indices
  * into one -- the top-k counterpart of iris_match_merge, src/main.rs:616-621 generalised to k.
  * The same order over nrecords records; records with den == 0 or index == UINT64_MAX are

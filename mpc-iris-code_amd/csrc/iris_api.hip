@@ -2521,7 +2521,7 @@ int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_MASKS && db->k.kind == IRIS_KIND_MASKS, "needs a masks engine and a masks database");
-    ARG(e->nq == 0, "a masks batch engine has no top-k form");
+    ARG(e->nq == 0, "a masks batch engine runs through iris_resolver_batch_topk_masks");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     ARG(n == 0 || shares_device, "NULL argument");
     for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
@@ -2542,6 +2542,118 @@ int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
         return launch_resolver_topk(d->stream, shares_device, parts, (const uint16_t *)d->out_a.p, n, ts);
     });
+}
+
+// A launch unit of a batched top-k call: m queries from q0 on (m <= kMasksBatchG) whose pass writes
+// `lists` lists of k records per query; launch(base, stride) enqueues the pass(es), query q0 + s
+// storing its lists at base + s * stride.
+struct TopkUnit {
+    uint32_t q0, m;
+    uint64_t lists;
+    std::function<int(Partial *, uint64_t)> launch;
+};
+
+// topk_run for the nq queries of a batch engine.  One lists region of the device's match buffer
+// -- per query of a unit its lists and then the merge's spare lists, (lists + spare) * k records,
+// at most kMasksBatchG queries -- serves every unit in stream order: a unit's merge has consumed the
+// region before the next unit's pass writes it.  Each unit's pass is followed by its merge levels,
+// one launch per level for the unit's queries together (launch_topk_merge_level); the last level
+// writes query q's k records at q * k of the pinned host result.  The call waits once; every
+// query's count is the length of its list's valid prefix.
+static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k, iris_match_t *out, uint32_t *counts,
+                          uint32_t nq, const std::vector<TopkUnit> &units) {
+    for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
+    if (n == 0) return 0;
+    uint64_t room = 0;
+    for (const TopkUnit &u : units) room = std::max(room, u.m * (u.lists + topk_spare_lists(u.lists)) * k);
+    CHK(ensure(d, d->matches, room * sizeof(Partial)));
+    CHK(ensure_host_result(d, (size_t)nq * k * sizeof(Partial)));
+    Partial *region = (Partial *)d->matches.p, *res = (Partial *)d->host_result;
+    for (const TopkUnit &u : units) {
+        const uint64_t stride = (u.lists + topk_spare_lists(u.lists)) * k;
+        CHK(u.launch(region, stride));
+        Partial *src = region, *dst = region + u.lists * k;
+        for (uint64_t left = u.lists;;) {
+            const uint64_t groups = topk_spare_lists(left);
+            const bool last = groups == 1;
+            CHK(timed(d, "topk_merge", left * u.m, [&] {
+                return launch_topk_merge_level(d->stream, src, left, k, last ? res + (size_t)u.q0 * k : dst, u.m, stride,
+                                               last ? k : stride);
+            }));
+            if (last) break;
+            left = groups;
+            std::swap(src, dst);
+        }
+    }
+    CHK(sync(d));
+    for (uint32_t q = 0; q < nq; ++q) {
+        const Partial *r = res + (size_t)q * k;
+        uint32_t c = 0;
+        while (c < k && r[c].den != 0) ++c;
+        for (uint32_t i = 0; i < c; ++i) match_from(r[i], true, base, &out[(size_t)q * k + i]);
+        counts[q] = c;
+    }
+    return 0;
+}
+
+// iris_resolver_batch_search_masks' top-k sibling, with iris_resolver_batch_matches_masks' dispatch:
+// TILES ranges the batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass
+// of masks_batch_kernel<BATCH_TOPK> ("masks_batch_topk") storing every wave's list per query, a
+// single left-over query one launch_masks_topk on its slab; other TILES ranges one launch_masks_topk
+// per query; LANES the masks kernel into the workspace and the resolver top-k kernel per query.
+int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                   const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base, uint32_t k,
+                                   iris_match_t *out, uint32_t *counts) {
+    IRIS_KEEP_DEVICE();
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");
+    ARG(out, "out is NULL");
+    ARG(counts, "counts is NULL");
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(masks_batch_args(e, db));
+    ARG(n == 0 || shares_device, "NULL argument");
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(shares_device[p], "NULL share array");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    const LaunchRange r{first, n};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const bool batch = tiles && masks_batch_runs(d->hooks, r);
+    const uint64_t slab = n * (uint64_t)kRot;
+    if (n && !tiles) CHK(ensure(d, d->out_a, n * kRot * 2));
+    std::vector<TopkUnit> units;
+    for (uint32_t q0 = 0; n && q0 < nq;) {
+        const uint32_t m = batch ? std::min<uint32_t>(nq - q0, kMasksBatchG) : 1;
+        if (m > 1) {
+            units.push_back(TopkUnit{q0, m, masks_batch_topk_units(d->hooks, r, m), [=](Partial *lists, uint64_t stride) {
+                const void *frags[kMasksBatchG];
+                for (uint32_t s = 0; s < m; ++s) frags[s] = e->sub[q0 + s]->qfrag;
+                return timed(d, "masks_batch_topk", n * m, [&] {
+                    return launch_masks_batch_topk(d->hooks, d->stream, db->data, frags, m, r, shares_device, parts, q0,
+                                                   lists, stride, k);
+                });
+            }});
+        } else {
+            // one query through the single-query forms, on its slab of every part
+            const uint64_t lists = tiles ? masks_topk_units(d->hooks, r) : resolver_topk_units(n);
+            units.push_back(TopkUnit{q0, 1, lists, [=](Partial *buf, uint64_t) {
+                const uint16_t *sl[8];
+                for (uint32_t p = 0; p < parts; ++p) sl[p] = shares_device[p] + q0 * slab;
+                const iris_engine *c = e->sub[q0];
+                if (tiles)
+                    return timed(d, "masks_topk", n, [&] {
+                        return launch_masks_topk(d->hooks, d->stream, db->data, c->qfrag, r, sl, parts, topk_sink(buf, k));
+                    });
+                CHK(timed(d, "masks", n, [&] { return launch_masks(d->stream, db->data, c->qtab, r, (uint16_t *)d->out_a.p); }));
+                return timed(d, "resolver_topk", n, [&] {
+                    return launch_resolver_topk(d->stream, sl, parts, (const uint16_t *)d->out_a.p, n, topk_sink(buf, k));
+                });
+            }});
+        }
+        q0 += m;
+    }
+    return topk_run_units(d, n, index_base, k, out, counts, nq, units);
 }
 
 // iris_resolver_batch_search_masks' threshold sibling, and that call's dispatch: TILES ranges the

@@ -352,6 +352,10 @@ int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *
                       const uint16_t *const *shares, uint32_t parts, const MatchSink &ts);
 inline uint64_t topk_spare_lists(uint64_t units) { return (units + kTopkFanIn - 1) / kTopkFanIn; }
 int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t units, uint32_t k, Partial *out);
+// one level, `slots` queries that share `units` at a time (blockIdx.y): slot s reads src + s * src_stride
+// and writes its topk_spare_lists(units) lists at dst + s * dst_stride
+int launch_topk_merge_level(void *stream, const Partial *src, uint64_t units, uint32_t k, Partial *dst, uint32_t slots,
+                            uint64_t src_stride, uint64_t dst_stride);
 struct BatchGeometry {
     uint64_t tile0, ntiles;
     uint32_t nqg, G;  // query groups, workgroups per query group
@@ -403,6 +407,12 @@ int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void 
 int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
                              LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0,
                              const MatchSink *sinks);
+// the top-k form of that pass: every wave stores its k best records of query s (slab q0 + s of every
+// part) at lists + s * stride + wave * k; masks_batch_topk_units = the lists per query (the grid's waves)
+uint64_t masks_batch_topk_units(const Hooks &h, LaunchRange r, uint32_t m);
+int launch_masks_batch_topk(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                            LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0, Partial *lists,
+                            uint64_t stride, uint32_t k);
 int launch_template_search(void *stream, const void *db, const void *qtab, LaunchRange r, double *dist_out,
                            Partial *partials, uint32_t *n_partials);
 // consumes partials; the winner's idx (range-relative) is offset by idx_base

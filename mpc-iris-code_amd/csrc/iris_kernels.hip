@@ -356,9 +356,14 @@ __global__ void __launch_bounds__(256) group_merge_kernel(const Partial *__restr
 // loads issued up front (at most 16 records per lane) -- and go through the same wave-resident
 // list as the passes' epilogue (topk_insert); waves 1..3 then hand their lists to wave 0 through
 // LDS.  The order is total, so the result does not depend on how the records were grouped.
+// blockIdx.y selects the slot (a query of a batched pass): slot s reads its nin lists at
+// in + s * in_stride and writes at out + s * out_stride; a single-query merge has one slot.
 __global__ void __launch_bounds__(256) topk_merge_kernel(const Partial *__restrict__ in, uint64_t nin, uint32_t k,
-                                                         Partial *__restrict__ out) {
+                                                         Partial *__restrict__ out, uint64_t in_stride,
+                                                         uint64_t out_stride) {
     constexpr int kGroups = (int)(kTopkFanIn * kTopkMax / 64 / kWaveSlots);  // per wave, at most
+    in += (uint64_t)blockIdx.y * in_stride;
+    out += (uint64_t)blockIdx.y * out_stride;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint64_t l0 = (uint64_t)blockIdx.x * kTopkFanIn;
     const uint64_t l1 = l0 + kTopkFanIn < nin ? l0 + kTopkFanIn : nin;
@@ -589,13 +594,21 @@ int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t uni
     Partial *src = lists, *dst = spare;
     for (;;) {
         const uint64_t groups = topk_spare_lists(units);
-        hipLaunchKernelGGL(topk_merge_kernel, dim3((uint32_t)groups), dim3(256), 0, (hipStream_t)stream,
-                           (const Partial *)src, units, k, groups == 1 ? out : dst);
-        if (check_launch() != 0) return -1;
+        if (launch_topk_merge_level(stream, src, units, k, groups == 1 ? out : dst, 1, 0, 0) != 0) return -1;
         if (groups == 1) return 0;
         units = groups;
         std::swap(src, dst);
     }
+}
+
+// One level of that fold for `slots` queries that share `units` (a batched pass): slot s folds the
+// units lists at src + s * src_stride into topk_spare_lists(units) lists at dst + s * dst_stride.
+int launch_topk_merge_level(void *stream, const Partial *src, uint64_t units, uint32_t k, Partial *dst, uint32_t slots,
+                            uint64_t src_stride, uint64_t dst_stride) {
+    if (units == 0 || k == 0 || k > kTopkMax || slots == 0 || slots > 65535) return -1;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((uint32_t)topk_spare_lists(units), slots), dim3(256), 0,
+                       (hipStream_t)stream, src, units, k, dst, src_stride, dst_stride);
+    return check_launch();
 }
 
 // Consumes the partials (a large set is folded in place by a first stage).

@@ -11,6 +11,9 @@
 // (the resolver step of src/main.rs:510-519 + 597-621) and keeps one running best per query.
 // The match form decodes the same way and, in place of the running best, appends every record
 // below the threshold to the query's own MatchSink (iris_resolver_batch_matches_masks).
+// The top-k form keeps, in place of the running best, each query's k best records of the wave as
+// a wave-resident sorted list (topk_insert, iris_device.hpp) and stores one list per wave and
+// query for launch_topk_merge to fold (iris_resolver_batch_topk_masks).
 //
 // The query side: each wave reads the G queries' compact words (16 B per lane, step and query)
 // from L2, as masks_mfma_kernel<MASKS_RESOLVE> does for its one query; a query's fragments are
@@ -34,7 +37,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTile = 32;
 constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
 
-enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2 };
+enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2, BATCH_TOPK = 3 };
 
 __device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
     const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
@@ -71,7 +74,7 @@ struct MaskBatchArgs {
     int valid;
     // BATCH_OUT: the slot's [n][31] u16 slab
     uint16_t *out[G];
-    // BATCH_RESOLVE, BATCH_MATCH: the participants' query-major arrays; slot g's slab starts slab[g]
+    // BATCH_RESOLVE, BATCH_MATCH, BATCH_TOPK: the participants' query-major arrays; slot g's slab starts slab[g]
     // elements in
     const uint16_t *shares[8];
     uint64_t slab[G];
@@ -80,6 +83,7 @@ struct MaskBatchArgs {
     uint32_t parts;
     uint32_t aligned;       // bit g: slab g of every part starts 16-B aligned
     MatchSink match[G];     // BATCH_MATCH: the slot's own records, room, counter and threshold
+                            // BATCH_TOPK: topk_sink -- buf = the slot's lists [gridDim.x * 4][k], cap = k
 };
 
 }  // namespace
@@ -90,6 +94,11 @@ struct MaskBatchArgs {
 // BATCH_MATCH: BATCH_RESOLVE's staging and decode; each tile's records below a.match[g].threshold
 // are appended to a.match[g] (one atomic per wave, tile and slot with a hit) -- no running best,
 // no partials, nothing after the loop.
+// BATCH_TOPK: BATCH_RESOLVE's staging and decode; best[g] is this lane's entry of slot g's list of
+// the wave (topk_insert; half 0 votes, as in masks_mfma_kernel<MASKS_TOPK>), resident while the wave
+// walks its tile groups.  After the loop every wave of the grid -- one with no tile group stores
+// an empty list, launch_topk_merge reads them all -- stores each valid slot's list at
+// a.match[g].buf[wave]: no shuffle reduction, no sh_best, no partials.
 template <int G, int T, int MODE>
 __global__ void __launch_bounds__(256, 2)
     masks_batch_kernel(const uint4 *__restrict__ db, MaskBatchArgs<G> a, uint64_t tile0, uint64_t ntiles, uint64_t first,
@@ -99,7 +108,7 @@ __global__ void __launch_bounds__(256, 2)
     const uint64_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaveSlots + (threadIdx.x >> 6));
     const uint64_t nwaves = (uint64_t)gridDim.x * kWaveSlots;
     const uint64_t ngroups = (ntiles + T - 1) / T;
-    if (MODE != BATCH_RESOLVE && wave >= ngroups) return;
+    if (MODE != BATCH_RESOLVE && MODE != BATCH_TOPK && wave >= ngroups) return;
     const uint32_t total = wave < ngroups ? (uint32_t)((ngroups - wave + nwaves - 1) / nwaves) * kSteps : 0;
     uint16_t *lds = sh_out[threadIdx.x >> 6];
     Partial best[G];
@@ -160,13 +169,19 @@ __global__ void __launch_bounds__(256, 2)
             __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
             return;
         }
-        if (valid && a.dist[g] && h == 0) a.dist[g][tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
+        if constexpr (MODE == BATCH_RESOLVE)
+            if (valid && a.dist[g] && h == 0) a.dist[g][tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
         Partial c;
         c.num = bn;
         c.den = valid ? bd : 0;
         c.rot = br;
         c.pad = 0;
         c.idx = tg - first;
+        if constexpr (MODE == BATCH_TOPK) {  // bq: this lane's entry of the slot's list
+            topk_insert(bq, (uint32_t)a.match[g].cap, lane, c, h == 0);
+            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+            return;
+        }
         if (partial_better_dev(c, bq)) bq = c;
         __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
     };
@@ -256,6 +271,11 @@ __global__ void __launch_bounds__(256, 2)
             step(d2, d1, w1, w0, s + 5);
         }
     }
+    if constexpr (MODE == BATCH_TOPK) {
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (g < a.valid) topk_store(a.match[g], wave, lane, best[g]);  // every wave of the grid: one list per slot
+    }
     if constexpr (MODE == BATCH_RESOLVE) {
         __shared__ Partial sh_best[G][kWaveSlots];
 #pragma unroll
@@ -291,7 +311,9 @@ namespace {
 // form 4.17 against 4.42); the resolve form of four queries 7.40 ms at 2 tiles against 8.65 at 1.
 // VGPRs (no scratch in any instantiation): rows form 98 / 242 for two queries at 1 / 4 tiles,
 // 164 / 234 for four at 1 / 2; resolve form 122 / 256 and 192 / 256; match form 110 / 245 and
-// 169 / 233 (it keeps no running best: profiles/r10_masks_batch_matches.txt).
+// 169 / 233 (it keeps no running best: profiles/r10_masks_batch_matches.txt); top-k form 120 / 254
+// and 188 / 252 (the lists live in the running bests' registers, topk_insert's broadcasts in SGPRs:
+// profiles/r14_masks_batch_topk.txt), so this mode takes the resolve form's choice unchanged.
 template <int G>
 constexpr int batch_big_tiles() { return G == 2 ? 4 : 2; }
 constexpr uint64_t kMasksBatchSplitTiles = 1024;  // = kMasksSplitTiles (iris_engines_mfma.hip)
@@ -329,7 +351,8 @@ int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const 
 
 template <int G>
 int launch_slots(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
-                 uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks = nullptr) {
+                 uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks = nullptr,
+                 bool topk = false) {
     const BatchTiles t = batch_tiles(h, r, batch_big_tiles<G>());
     if (np) *np = t.grid;
     const uint64_t slab = r.n * (uint64_t)kRot;
@@ -356,6 +379,7 @@ int launch_slots(const Hooks &h, void *stream, const void *db, const void *const
     if (!rs) return launch_group<G, BATCH_OUT>(stream, db, a, t, r);
     a.parts = rs->parts;
     for (uint32_t p = 0; p < rs->parts; ++p) a.shares[p] = rs->shares[p];
+    if (sinks && topk) return launch_group<G, BATCH_TOPK>(stream, db, a, t, r);
     if (sinks) return launch_group<G, BATCH_MATCH>(stream, db, a, t, r);
     return launch_group<G, BATCH_RESOLVE>(stream, db, a, t, r);
 }
@@ -399,6 +423,27 @@ int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const
     const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
     if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
     return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
+}
+
+// the lists each query of a top-k pass over r writes: one per wave of the grid (launch_slots')
+uint64_t masks_batch_topk_units(const Hooks &h, LaunchRange r, uint32_t m) {
+    if (r.n == 0) return 0;
+    return (uint64_t)batch_tiles(h, r, m == 2 ? batch_big_tiles<2>() : batch_big_tiles<kMasksBatchG>()).grid * kWaveSlots;
+}
+
+// The top-k form of the same pass (launch_masks_batch's slots, tiles per wave and grid): query s
+// decodes slab q0 + s of every part and every wave stores its k best records of that query at
+// lists + s * stride + wave * k (masks_batch_topk_units lists per query); nothing needs zeroing.
+int launch_masks_batch_topk(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                            LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0, Partial *lists,
+                            uint64_t stride, uint32_t k) {
+    if (r.n == 0) return 0;
+    if (m < 2 || m > (uint32_t)kMasksBatchG || parts == 0 || parts > 8 || !lists || k == 0 || k > kTopkMax) return -1;
+    const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
+    MatchSink sinks[kMasksBatchG];
+    for (uint32_t s = 0; s < m; ++s) sinks[s] = topk_sink(lists + s * stride, k);
+    if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks, true);
+    return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks, true);
 }
 
 }  // namespace iris

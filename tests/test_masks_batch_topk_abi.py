@@ -1,0 +1,110 @@
+"""CPU: the ABI surface of batched top-k (iris_resolver_batch_topk_masks) -- the entry point is
+exported and named in the header, the Rust declarations, iris_hip.hpp, the Python mirror and the
+documents; its header comment cites the reference lines it generalises; it refuses bad value
+arguments with a message before it looks at a handle; the single-query call's refusal of a batch
+engine names it; and a C++ program using MasksBatchEngine::topk compiles and links
+(tests/test_gpu_masks_batch_topk.py runs it)."""
+import ctypes
+import pathlib
+import re
+import subprocess
+
+import numpy as np
+
+import iris_hip as ih
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+CPP_SRC = ROOT / "tests" / "cpp" / "masks_batch_topk.cpp"
+NAME = "iris_resolver_batch_topk_masks"
+E_ARG = -1
+
+
+def build_cpp_program(outdir):
+    """Compiles tests/cpp/masks_batch_topk.cpp against the in-tree library -> the binary's path."""
+    exe = pathlib.Path(outdir) / "masks_batch_topk"
+    lib = ROOT / "mpc-iris-code_amd"
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", f"-I{ROOT / 'include'}", str(CPP_SRC), "-o",
+                        str(exe), f"-L{lib}", "-liris_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath-link,/opt/rocm/lib"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
+def _last_error(lib):
+    return lib.iris_last_error().decode(errors="replace")
+
+
+def test_symbol_exported_and_named_everywhere():
+    lib = ih.load_library()
+    assert hasattr(lib, NAME)
+    assert NAME in ih.exported_symbols()
+    header = (ROOT / "include" / "iris_hip.h").read_text()
+    assert re.search(r"\bint " + NAME + r"\(", header)
+    # in the top-k section, declared after the single-query call it batches
+    assert header.index("int iris_resolver_topk_masks(") < header.index("int " + NAME + "(") < header.index(
+        "int iris_topk_merge(")
+    ffi = (ROOT / "bindings" / "rust" / "src" / "iris_hip" / "ffi.rs").read_text()
+    assert f"pub fn {NAME}(" in ffi
+    engines = (ROOT / "bindings" / "rust" / "src" / "iris_hip" / "engines.rs").read_text()
+    assert "pub fn batch_topk(" in engines and "ffi::" + NAME in engines
+    hpp = (ROOT / "include" / "iris_hip.hpp").read_text()
+    assert NAME + "(" in hpp
+    assert re.search(r"std::vector<std::vector<Match>> topk\(", hpp)
+    assert hasattr(ih.MasksBatchEngine, "topk")
+    for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
+        assert NAME in (ROOT / doc).read_text(), doc
+
+
+def test_header_comment_cites_the_reference_and_the_contract():
+    header = (ROOT / "include" / "iris_hip.h").read_text()
+    decl = header.index("int " + NAME + "(")
+    comment = header[header.rindex("/*", 0, decl):decl]
+    for cite in ("src/main.rs:510-519", "597-621", "src/template.rs:43-47"):
+        assert cite in comment, cite
+    assert "byte for byte" in comment and "iris_resolver_topk_masks" in comment
+    assert "no reference counterpart" in comment and "counts" in comment
+    # the scope paragraph of the section: the masks batch engine is in, the other two stay out
+    sec = header[header.index("- top-k\n"):header.index("int iris_template_topk(")]
+    scope = sec[sec.index("Out of scope"):]
+    assert NAME in scope and "template" in scope and "distance" in scope
+
+
+def _call(lib, k, out, counts, parts=1):
+    """The entry point with NULL handles and otherwise plausible arguments."""
+    rows = np.zeros(31, np.uint16)
+    ptrs = (ctypes.c_void_p * 1)(rows.ctypes.data)
+    return lib.iris_resolver_batch_topk_masks(None, None, 0, 1, ptrs, parts, 0, k, out, counts)
+
+
+def test_value_arguments_are_refused_before_the_handles():
+    lib = ih.load_library()
+    out = (ih.Match * 2)()
+    ctypes.memset(out, 0x5A, ctypes.sizeof(out))
+    before = bytes(out)
+    counts = (ctypes.c_uint32 * 2)(77, 78)
+    for k in (0, 65, 2**31):
+        assert _call(lib, k, out, counts) == E_ARG, k
+        assert re.search(r"\bk\b", _last_error(lib)), k
+    assert _call(lib, 1, None, counts) == E_ARG
+    assert "out is NULL" in _last_error(lib)
+    assert _call(lib, 1, out, None) == E_ARG
+    assert "counts" in _last_error(lib)
+    for parts in (0, 9, 2**31):
+        assert _call(lib, 1, out, counts, parts) == E_ARG, parts
+        assert "parts" in _last_error(lib), parts
+    # valid value arguments: the NULL handles are what is refused
+    for k in (1, 64):
+        assert _call(lib, k, out, counts) == E_ARG
+        assert "NULL" in _last_error(lib)
+    assert list(counts) == [77, 78] and bytes(out) == before
+
+
+def test_single_query_call_names_the_batch_call():
+    """iris_resolver_topk_masks keeps refusing a masks batch engine; its message names this call."""
+    src = (ROOT / "mpc-iris-code_amd" / "csrc" / "iris_api.hip").read_text()
+    body = src[src.index("int iris_resolver_topk_masks("):src.index("int iris_resolver_batch_topk_masks(")]
+    assert re.search(r'ARG\(e->nq == 0, "[^"]*' + NAME, body)
+
+
+def test_cpp_program_compiles(tmp_path):
+    assert build_cpp_program(tmp_path).exists()
