@@ -521,7 +521,7 @@ constexpr const char *kHookNames[] = {"IRIS_TILES_PER_WAVE",  "IRIS_FUSED_REDUCE
                                       "IRIS_GROUP_STALL",     "IRIS_GROUP_UNORDERED", "IRIS_UPLOAD",
                                       "IRIS_LOAD_WINDOWS",    "IRIS_READAHEAD_WINDOW", "IRIS_RESIDENT_BUDGET_MB",
                                       "IRIS_READAHEAD_PACKED", "IRIS_READAHEAD_WINDOW_MAX", "IRIS_SEARCH_SHARE",
-                                      "IRIS_SEARCH_SHARE_DELAY_US"};
+                                      "IRIS_SEARCH_SHARE_DELAY_US", "IRIS_SEARCH_SHARE_EVEN"};
 constexpr int kNumHooks = (int)(sizeof(kHookNames) / sizeof(kHookNames[0]));
 
 const char *env(const char *name) {
@@ -568,6 +568,7 @@ void read_hooks(Hooks *h) {
         case 13: h->ra_window_max = env_u32(v, 1024); break;
         case 14: h->search_share = v[0] != '0'; break;
         case 15: h->search_share_delay_us = env_u32(v, 1000000); break;
+        case 16: h->search_share_even = v[0] != '0'; break;
         }
     }
 }
@@ -595,7 +596,8 @@ size_t format_hooks(const Hooks &h, char *buf, size_t len) {
              " group_stall=" + std::to_string(h.group_stall) + " group_unordered=" + std::to_string(h.group_unordered) +
              " upload=" + upload_names[h.upload & 3] +
              " search_share=" + std::to_string(h.search_share) +
-             " search_share_delay_us=" + std::to_string(h.search_share_delay_us);
+             " search_share_delay_us=" + std::to_string(h.search_share_delay_us) +
+             " search_share_even=" + std::to_string(h.search_share_even);
     std::string ign;
     for (int i = 0; i < kNumHooks; ++i)
         if (h.ignored >> i & 1u) ign += (ign.empty() ? "" : ",") + std::string(kHookNames[i]);

@@ -212,6 +212,7 @@ struct Hooks {
     uint32_t ra_window_max = 0;      // IRIS_READAHEAD_WINDOW_MAX=1..1024: cap of a read-ahead window, chunks (0: by records)
     bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches never register as guests
     uint32_t search_share_delay_us = 0;  // IRIS_SEARCH_SHARE_DELAY_US: device-stream spin ahead of a pass that can host
+    bool search_share_even = false;  // IRIS_SEARCH_SHARE_EVEN=1: a pass that is nobody's guest sees no guest in odd tile groups
     uint32_t ignored = 0;            // bit i: test hook kHookNames[i] was set without IRIS_TEST_HOOKS=1
 };
 // The bound of forming a device group when IRIS_GROUP_TIMEOUT_MS is not set (iris_group.hip)
@@ -275,7 +276,9 @@ uint32_t mfma_search_partials(const Hooks &h, LaunchRange r);
 // computes both queries for its 16 tiles from one read of them, writes both partials and marks its
 // tile group in the guest's done array, and the guest's own launch skips the groups marked there.
 // The slot is device memory, zeroed before the hosting pass's launch and written once by
-// launch_share_publish (the fields, then ready with agent-scope release).
+// launch_share_publish (the fields, then ready with agent-scope release).  Nothing else is read
+// while its writer runs: done words and a guest's partials reach their readers (the guest's own
+// launch and reduce, later on the device stream) with the end of the hosting kernel.
 struct GuestSlot {
     uint32_t ready;
     uint32_t pad;

@@ -576,20 +576,30 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
 // nothing to do; a guest has been published in the slot -> both queries for the workgroup's 16
 // tiles in the two-query shape (2 tiles x 2 queries per wave, twice), both partials, then the
 // guest's done word; else the single-query pass.
+//   Memory order: only the slot is written while the pass runs.  The done words and the partials
+// a pass writes for its guest are read by the guest's own launch and its reduce, which follow the
+// pass on the device stream, so the end of the kernel publishes them: they are plain stores, and
+// own_done is read relaxed.  (An agent-scope release store per tile group wrote the XCD's L2 back
+// 19 532 times a pass, 0.43 ms of a 7.8-ms two-query pass; an acquire load invalidates the CU's
+// L1 under the other workgroup's query fragments.)  `ready` is read relaxed, and only a workgroup
+// that finds it set pays the acquire, ahead of the slot's fields and the guest's fragments.
+// even_only (test hook): the guest counts as not visible in odd tile groups.
 __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     template_share_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, uint64_t tile0, uint64_t ntiles,
                           uint64_t first, uint64_t end, Partial *__restrict__ partials, const GuestSlot *slot,
-                          const uint32_t *own_done, unsigned long long *count) {
-    // one thread reads the words (agent-scope acquire: a plain load could be served from the scalar
+                          const uint32_t *own_done, unsigned long long *count, uint32_t even_only) {
+    // one thread reads the words (agent-scope atomics: a plain load could be served from the scalar
     // cache) and the slot's fields behind them; LDS makes the decision the same for every wave
     __shared__ uint32_t sh_flag[2];
     __shared__ uint64_t sh_guest[3];
     if (threadIdx.x == 0) {
         const uint32_t dn =
-            own_done ? __hip_atomic_load(own_done + blockIdx.x, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            own_done ? __hip_atomic_load(own_done + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
         uint32_t rdy = 0;
-        if (slot && !dn) rdy = __hip_atomic_load(&slot->ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (slot && !dn && !(even_only && (blockIdx.x & 1)))
+            rdy = __hip_atomic_load(&slot->ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (rdy) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             sh_guest[0] = (uint64_t)slot->frag;
             sh_guest[1] = (uint64_t)slot->partials;
             sh_guest[2] = (uint64_t)slot->done;
@@ -631,7 +641,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         (__attribute__((address_space(1))) uint32_t *)uniform64(sh_guest[2]);
     share_finish<2, kRounds * kWaveSlots>(sh_best, out);
     if (threadIdx.x == 1) {  // the thread that stored the guest's partial
-        __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (count) atomicAdd(count, 1ull);
     }
 }
@@ -862,9 +872,12 @@ int launch_template_share_search(const Hooks &h, void *stream, const void *db, c
     if (!share_search_ok(h, r)) return -1;  // the caller asks first
     const TileRange t = search_range(h, r);
     *n_partials = (uint32_t)t.grid;
+    // test hook: a pass that is nobody's guest carries its guest in even tile groups only (the
+    // guest's own launch then computes the odd ones, and carries its own guest there)
+    const bool even_only = h.search_share_even && !own_done;
     hipLaunchKernelGGL(template_share_kernel, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, partials,
-                       slot, own_done, count);
+                       slot, own_done, count, (uint32_t)even_only);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
