@@ -1,0 +1,535 @@
+// iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
+// and batched, with the runners that turn launch units into match lists.  Calls, locking and
+// errors: see iris_api.hip.
+#include <string.h>
+
+#include <new>
+
+#include "iris_handles.hpp"
+
+using namespace iris;
+using namespace iris_api;
+
+extern "C" {
+
+// ------------------------------------------------------------------ threshold matching
+
+// Records the first pass has room for when the caller's cap asks for fewer: a threshold that
+// matters matches a handful of records, so this covers every sparse list in one pass (24 KB).
+constexpr uint64_t kMatchFirstRoom = 1024;
+
+static int matches_args(double threshold, const iris_match_t *out, uint64_t cap, const uint64_t *count) {
+    ARG(threshold == threshold, "threshold is NaN");
+    ARG(count, "count is NULL");
+    ARG(cap == 0 || out, "out is NULL with cap > 0");
+    return 0;
+}
+
+// One launch unit of a threshold-match call: queries q0 .. q0 + m - 1, whose hits one pass appends.
+// launch(sinks) enqueues that pass (timed under its own names); sinks[s] is query q0 + s's.  A pass
+// whose kernel takes more sinks than the unit has queries (the template batch GEMM's padding
+// queries) asks for `pad` more after them: cap 0, no buffer, a zeroed counter of their own.
+struct MatchUnit {
+    uint32_t q0, m;
+    std::function<int(const MatchSink *)> launch;
+    uint32_t pad = 0;
+};
+
+// A first pass that one launch runs for all queries at once (the template batch GEMM), the units
+// then being only what runs again: launch(sinks) takes nqp sinks, the queries' and the padding
+// queries' after them.
+struct MatchWhole {
+    uint32_t nqp;
+    std::function<int(const MatchSink *)> launch;
+};
+
+// One threshold-match call of nq queries over n records each.  Every query has a counter of its
+// own (all zeroed on the stream before the first launch) and a region of `room` records of the
+// device's match buffer; the first pass -- `whole`, or else every unit's -- is enqueued before the
+// one wait.  The counters always count, so a query whose hits did not fit reports how many there
+// are: its unit -- that unit alone -- runs once more, its regions grown to exactly the reported
+// counts (at most n records a query), one unit at a time, its records copied back before the next
+// unit runs.  A query's records are then sorted by index -- the append order depends on which wave
+// adds first -- and the min(count, cap) lowest become iris_match_t at out + q * cap as match_from
+// fills them (idx + base).  cap == 0 needs no record, so never a second pass.  reuse_grown (the
+// single-query calls): a buffer an earlier call grew is used in full by the first pass.  budget
+// (0: none): the bytes all first-pass regions may take together, while a query keeps room for
+// kMatchFirstRoom records -- a large cap times many queries asks for no more.
+static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
+                             uint64_t *counts, uint32_t nq, bool reuse_grown, const std::vector<MatchUnit> &units,
+                             const MatchWhole *whole = nullptr, uint64_t budget = 0) {
+    for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
+    if (n == 0) return 0;
+    uint32_t nc = whole ? std::max(nq, whole->nqp) : nq;  // counters and first-pass sinks
+    for (const MatchUnit &u : units) nc = std::max(nc, u.q0 + u.m + u.pad);
+    CHK(ensure(d, d->match_count, nc * sizeof(uint64_t)));
+    CHK(ensure_host_result(d, nq * sizeof(uint64_t)));
+    uint64_t room = 0;
+    if (cap) {
+        uint64_t want = cap;
+        if (budget) want = std::min<uint64_t>(want, budget / (sizeof(Partial) * nq));
+        room = std::min<uint64_t>(n, std::max<uint64_t>(want, kMatchFirstRoom));
+        if (reuse_grown) room = std::max<uint64_t>(room, std::min<uint64_t>(n, d->matches.cap / sizeof(Partial)));
+    }
+    CHK(ensure(d, d->matches, nq * room * sizeof(Partial)));
+    uint64_t *cnt = (uint64_t *)d->match_count.p;
+    HIPCHK(hipMemsetAsync(cnt, 0, nc * sizeof(uint64_t), d->stream));
+    std::vector<MatchSink> sinks;  // by query; a unit's own during its rerun
+    std::vector<uint64_t> total, off;
+    try {
+        sinks.resize(nc);
+        total.resize(nq);
+        off.reserve(kMasksBatchG + 1);
+    } catch (const std::bad_alloc &) {
+        return fail(IRIS_E_NOMEM, "out of host memory");
+    }
+    for (uint32_t q = 0; q < nc; ++q)
+        sinks[q] = q < nq ? MatchSink{(Partial *)d->matches.p + q * room, room, cnt + q, threshold}
+                          : MatchSink{nullptr, 0, cnt + q, threshold};
+    if (whole) {
+        CHK(whole->launch(sinks.data()));
+    } else {
+        for (const MatchUnit &u : units) CHK(u.launch(sinks.data() + u.q0));
+    }
+    HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+    CHK(sync(d));
+    memcpy(total.data(), d->host_result, nq * sizeof(uint64_t));
+    for (uint32_t q = 0; q < nq; ++q)
+        if (total[q] > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+    // query q's total[q] records at src -> counts[q] and its list
+    std::vector<Partial> recs;
+    auto finish = [&](uint32_t q, const Partial *src) -> int {
+        counts[q] = total[q];
+        const uint64_t take = std::min(total[q], cap);
+        if (take == 0) return 0;
+        try {
+            recs.resize(total[q]);
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        HIPCHK(hipMemcpyAsync(recs.data(), src, total[q] * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+        const auto by_index = [](const Partial &a, const Partial &b) { return a.idx < b.idx; };
+        if (take < total[q]) std::nth_element(recs.begin(), recs.begin() + take, recs.end(), by_index);
+        std::sort(recs.begin(), recs.begin() + take, by_index);
+        for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[q * cap + i]);
+        return 0;
+    };
+    auto overflows = [&](const MatchUnit &u) {
+        for (uint32_t s = 0; cap && s < u.m; ++s)
+            if (total[u.q0 + s] > room) return true;
+        return false;
+    };
+    // the units whose lists fit first: a rerun below may replace the buffer their records are in
+    for (const MatchUnit &u : units) {
+        if (overflows(u)) continue;
+        for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + (u.q0 + s) * room));
+    }
+    for (const MatchUnit &u : units) {
+        if (!overflows(u)) continue;
+        off.assign(u.m + 1, 0);
+        for (uint32_t s = 0; s < u.m; ++s) off[s + 1] = off[s] + total[u.q0 + s];
+        CHK(ensure(d, d->matches, off[u.m] * sizeof(Partial)));
+        for (uint32_t s = 0; s < u.m + u.pad; ++s)
+            sinks[s] = s < u.m ? MatchSink{(Partial *)d->matches.p + off[s], total[u.q0 + s], cnt + u.q0 + s, threshold}
+                               : MatchSink{nullptr, 0, cnt + u.q0 + s, threshold};
+        HIPCHK(hipMemsetAsync(cnt + u.q0, 0, u.m * sizeof(uint64_t), d->stream));
+        CHK(u.launch(sinks.data()));
+        HIPCHK(hipMemcpyAsync(d->host_result, cnt + u.q0, u.m * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+        if (memcmp(d->host_result, total.data() + u.q0, u.m * sizeof(uint64_t)) != 0)
+            return fail(IRIS_E_HIP, "match pass counts differ between two runs");
+        for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + off[s]));
+    }
+    return 0;
+}
+
+// The single-query calls: one unit of one query, `launch` timed as `name`.
+static int matches_run(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
+                       uint64_t *count, const char *name, const std::function<int(const MatchSink &)> &launch) {
+    const std::vector<MatchUnit> unit{MatchUnit{0, 1, [&](const MatchSink *ms) {
+        return timed(d, name, n, [&] { return launch(ms[0]); });
+    }}};
+    return matches_run_units(d, n, base, threshold, out, cap, count, 1, true, unit);
+}
+
+// iris_template_search's threshold sibling (header: "threshold matching")
+int iris_template_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                          double threshold, iris_match_t *out, uint64_t cap, uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, count));  // the value arguments first: refused whatever the handles
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    return matches_run(d, n, index_base + first, threshold, out, cap, count, "template_match", [&](const MatchSink &ms) {
+        return db->k.layout == IRIS_LAYOUT_TILES
+                   ? launch_template_mfma_match(d->hooks, d->stream, db->data, e->qfrag, r, ms)
+                   : launch_template_match(d->stream, db->data, e->qtab, r, ms);
+    });
+}
+
+// iris_resolver_search's threshold sibling
+int iris_resolver_matches(iris_device_t *d, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms,
+                          uint64_t n, uint64_t index_base, double threshold, iris_match_t *out, uint64_t cap,
+                          uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(d, "NULL argument");
+    CHK(share_args(shares, parts, n, denoms != nullptr));
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
+        return launch_resolver_match(d->stream, shares, parts, denoms, n, ms);
+    });
+}
+
+// iris_resolver_search_masks' threshold sibling: TILES runs the fused masks_mfma_kernel<MASKS_MATCH>;
+// LANES the masks kernel into a workspace and then the resolver match kernel.
+int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                double threshold, iris_match_t *out, uint64_t cap, uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(single_masks_args(e, db, "iris_resolver_batch_matches_masks"));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    if (db->k.layout == IRIS_LAYOUT_TILES)
+        return matches_run(d, n, index_base, threshold, out, cap, count, "masks_match", [&](const MatchSink &ms) {
+            return launch_masks_match(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, ms);
+        });
+    const uint16_t *den = nullptr;
+    if (n) CHK(enqueue_masks_denoms(e, db, r, &den));
+    return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
+        return launch_resolver_match(d->stream, shares_device, parts, den, n, ms);
+    });
+}
+
+// ------------------------------------------------------------------ top-k
+
+static int topk_args(uint32_t k, const iris_match_t *out, const uint32_t *count) {
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");
+    ARG(out, "out is NULL");
+    ARG(count, "count is NULL");
+    return 0;
+}
+
+// One top-k call over n records: `launch` enqueues the pass whose `units` waves each store their
+// k best at the lists it is given (the device's match buffer: units lists, then the merge's spare
+// lists), the merge levels follow on the stream and the last one writes k records to the pinned
+// host result -- 24 k bytes whatever n is -- and the call waits once.  The list is sorted with the
+// empty entries (den = 0) last, so the count is the length of its valid prefix.
+static int topk_run(iris_device *d, uint64_t n, uint64_t base, uint32_t k, iris_match_t *out, uint32_t *count,
+                    const char *name, uint64_t units, const std::function<int(const MatchSink &)> &launch) {
+    *count = 0;
+    if (n == 0) return 0;
+    CHK(ensure(d, d->matches, (units + topk_spare_lists(units)) * k * sizeof(Partial)));
+    CHK(ensure_host_result(d, (size_t)k * sizeof(Partial)));
+    Partial *lists = (Partial *)d->matches.p, *spare = lists + units * k;
+    CHK(timed(d, name, n, [&] { return launch(topk_sink(lists, k)); }));
+    CHK(timed(d, "topk_merge", units,
+              [&] { return launch_topk_merge(d->stream, lists, spare, units, k, (Partial *)d->host_result); }));
+    CHK(sync(d));
+    const Partial *res = (const Partial *)d->host_result;
+    uint32_t c = 0;
+    while (c < k && res[c].den != 0) ++c;
+    for (uint32_t i = 0; i < c; ++i) match_from(res[i], true, base, &out[i]);
+    *count = c;
+    return 0;
+}
+
+// iris_template_search's top-k sibling (header: "top-k")
+int iris_template_topk(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                       uint32_t k, iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(topk_args(k, out, count));  // the value arguments first: refused whatever the handles
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const uint64_t units = n ? (tiles ? mfma_topk_units(d->hooks, r) : template_topk_units(r)) : 0;
+    return topk_run(d, n, index_base + first, k, out, count, "template_topk", units, [&](const MatchSink &ts) {
+        return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts)
+                     : launch_template_topk(d->stream, db->data, e->qtab, r, ts);
+    });
+}
+
+// iris_resolver_search's top-k sibling
+int iris_resolver_topk(iris_device_t *d, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms,
+                       uint64_t n, uint64_t index_base, uint32_t k, iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(topk_args(k, out, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(d, "NULL argument");
+    CHK(share_args(shares, parts, n, denoms != nullptr));
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
+        return launch_resolver_topk(d->stream, shares, parts, denoms, n, ts);
+    });
+}
+
+// iris_resolver_search_masks' top-k sibling: TILES runs the fused masks_mfma_kernel<MASKS_TOPK>;
+// LANES the masks kernel into a workspace and then the resolver top-k kernel.
+int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                             const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base, uint32_t k,
+                             iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    CHK(topk_args(k, out, count));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(single_masks_args(e, db, "iris_resolver_batch_topk_masks"));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    if (db->k.layout == IRIS_LAYOUT_TILES)
+        return topk_run(d, n, index_base, k, out, count, "masks_topk", n ? masks_topk_units(d->hooks, r) : 0,
+                        [&](const MatchSink &ts) {
+                            return launch_masks_topk(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, ts);
+                        });
+    const uint16_t *den = nullptr;
+    if (n) CHK(enqueue_masks_denoms(e, db, r, &den));
+    return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
+        return launch_resolver_topk(d->stream, shares_device, parts, den, n, ts);
+    });
+}
+
+// A launch unit of a batched top-k call: m queries from q0 on (m <= kMasksBatchG) whose pass writes
+// `lists` lists of k records per query; launch(base, stride) enqueues the pass(es), query q0 + s
+// storing its lists at base + s * stride.
+struct TopkUnit {
+    uint32_t q0, m;
+    uint64_t lists;
+    std::function<int(Partial *, uint64_t)> launch;
+};
+
+// topk_run for the nq queries of a batch engine.  One lists region of the device's match buffer
+// -- per query of a unit its lists and then the merge's spare lists, (lists + spare) * k records,
+// at most kMasksBatchG queries -- serves every unit in stream order: a unit's merge has consumed the
+// region before the next unit's pass writes it.  Each unit's pass is followed by its merge levels,
+// one launch per level for the unit's queries together (launch_topk_merge_level); the last level
+// writes query q's k records at q * k of the pinned host result.  The call waits once; every
+// query's count is the length of its list's valid prefix.
+static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k, iris_match_t *out, uint32_t *counts,
+                          uint32_t nq, const std::vector<TopkUnit> &units) {
+    for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
+    if (n == 0) return 0;
+    uint64_t room = 0;
+    for (const TopkUnit &u : units) room = std::max(room, u.m * (u.lists + topk_spare_lists(u.lists)) * k);
+    CHK(ensure(d, d->matches, room * sizeof(Partial)));
+    CHK(ensure_host_result(d, (size_t)nq * k * sizeof(Partial)));
+    Partial *region = (Partial *)d->matches.p, *res = (Partial *)d->host_result;
+    for (const TopkUnit &u : units) {
+        const uint64_t stride = (u.lists + topk_spare_lists(u.lists)) * k;
+        CHK(u.launch(region, stride));
+        Partial *src = region, *dst = region + u.lists * k;
+        for (uint64_t left = u.lists;;) {
+            const uint64_t groups = topk_spare_lists(left);
+            const bool last = groups == 1;
+            CHK(timed(d, "topk_merge", left * u.m, [&] {
+                return launch_topk_merge_level(d->stream, src, left, k, last ? res + (size_t)u.q0 * k : dst, u.m, stride,
+                                               last ? k : stride);
+            }));
+            if (last) break;
+            left = groups;
+            std::swap(src, dst);
+        }
+    }
+    CHK(sync(d));
+    for (uint32_t q = 0; q < nq; ++q) {
+        const Partial *r = res + (size_t)q * k;
+        uint32_t c = 0;
+        while (c < k && r[c].den != 0) ++c;
+        for (uint32_t i = 0; i < c; ++i) match_from(r[i], true, base, &out[(size_t)q * k + i]);
+        counts[q] = c;
+    }
+    return 0;
+}
+
+// iris_resolver_batch_search_masks' top-k sibling, with iris_resolver_batch_matches_masks' dispatch:
+// TILES ranges the batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass
+// of masks_batch_kernel<BATCH_TOPK> ("masks_batch_topk") storing every wave's list per query, a
+// single left-over query one launch_masks_topk on its slab; other TILES ranges one launch_masks_topk
+// per query; LANES the masks kernel into the workspace and the resolver top-k kernel per query.
+int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                   const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base, uint32_t k,
+                                   iris_match_t *out, uint32_t *counts) {
+    IRIS_KEEP_DEVICE();
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");
+    ARG(out, "out is NULL");
+    ARG(counts, "counts is NULL");
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(masks_batch_args(e, db));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const MasksWalk w(e, db, first, n);
+    std::vector<TopkUnit> units;
+    for (MasksUnit u = w.unit(0); n && u.m; u = w.unit(u.q0 + u.m)) {
+        if (u.m > 1) {
+            units.push_back(TopkUnit{u.q0, u.m, masks_batch_topk_units(d->hooks, w.r, u.m), [=](Partial *lists, uint64_t stride) {
+                return timed(d, "masks_batch_topk", n * u.m, [&] {
+                    return launch_masks_batch_topk(d->hooks, d->stream, db->data, u.frags, u.m, w.r, shares_device, parts,
+                                                   u.q0, lists, stride, k);
+                });
+            }});
+        } else {
+            // one query through the single-query forms, on its slab of every part
+            const uint64_t lists = w.tiles ? masks_topk_units(d->hooks, w.r) : resolver_topk_units(n);
+            units.push_back(TopkUnit{u.q0, 1, lists, [=](Partial *buf, uint64_t) {
+                const uint16_t *sl[8];
+                w.slabs(u.q0, shares_device, parts, sl);
+                if (w.tiles)
+                    return timed(d, "masks_topk", n, [&] {
+                        return launch_masks_topk(d->hooks, d->stream, db->data, u.one->qfrag, w.r, sl, parts, topk_sink(buf, k));
+                    });
+                const uint16_t *den = nullptr;
+                CHK(enqueue_masks_denoms(u.one, db, w.r, &den));
+                return timed(d, "resolver_topk", n, [&] {
+                    return launch_resolver_topk(d->stream, sl, parts, den, n, topk_sink(buf, k));
+                });
+            }});
+        }
+    }
+    return topk_run_units(d, n, index_base, k, out, counts, e->nq, units);
+}
+
+// iris_resolver_batch_search_masks' threshold sibling, and that call's dispatch: TILES ranges the
+// batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass of
+// masks_batch_kernel<BATCH_MATCH> ("masks_batch_match") appending to the group's sinks, a single
+// left-over query one launch_masks_match; other TILES ranges one launch_masks_match per query; LANES
+// the masks kernel into the workspace and the resolver match kernel per query.  A launch unit -- a
+// group or a single query -- is what matches_run_units runs again when one of its lists overflows.
+int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                      const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                      double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, counts));
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(masks_batch_args(e, db));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const MasksWalk w(e, db, first, n);
+    std::vector<MatchUnit> units;
+    for (MasksUnit u = w.unit(0); n && u.m; u = w.unit(u.q0 + u.m)) {
+        if (u.m > 1) {
+            units.push_back(MatchUnit{u.q0, u.m, [=](const MatchSink *ms) {
+                return timed(d, "masks_batch_match", n * u.m, [&] {
+                    return launch_masks_batch_match(d->hooks, d->stream, db->data, u.frags, u.m, w.r, shares_device, parts,
+                                                    u.q0, ms);
+                });
+            }});
+        } else {
+            // one query through the single-query forms, on its slab of every part
+            units.push_back(MatchUnit{u.q0, 1, [=](const MatchSink *ms) {
+                const uint16_t *sl[8];
+                w.slabs(u.q0, shares_device, parts, sl);
+                if (w.tiles)
+                    return timed(d, "masks_match", n, [&] {
+                        return launch_masks_match(d->hooks, d->stream, db->data, u.one->qfrag, w.r, sl, parts, ms[0]);
+                    });
+                const uint16_t *den = nullptr;
+                CHK(enqueue_masks_denoms(u.one, db, w.r, &den));
+                return timed(d, "resolver_match", n, [&] {
+                    return launch_resolver_match(d->stream, sl, parts, den, n, ms[0]);
+                });
+            }});
+        }
+    }
+    return matches_run_units(d, n, index_base, threshold, out, cap, counts, e->nq, false, units);
+}
+
+// The bytes the first pass of iris_template_batch_matches gives all queries' regions together (a
+// design constant): 1024 queries with a large cap then ask for 256 MiB, not for
+// cap x 1024 records.
+constexpr uint64_t kBatchMatchBudget = 256ull << 20;
+
+// iris_template_batch_search's threshold sibling, and that call's checks and dispatch.  Engines of
+// up to kBatchStreamMax queries: one single-query match pass per query ("template_match"), all
+// enqueued before the one wait.  The GEMM: one launch of batch_lds_kernel<..., MATCH>
+// ("template_batch_match") over all query groups, every query appending to its own sink of the
+// device array d->match_sinks; what runs again when a list overflows is the aligned block of
+// batch_query_group() queries, independent of the kernel shape, launched on its own query tiles.
+int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                                double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts) {
+    IRIS_KEEP_DEVICE();
+    CHK(matches_args(threshold, out, cap, counts));  // the value arguments first: refused whatever the handles
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
+    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
+    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
+        "batched search of more than 3 queries needs a template database in the TILES layout");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    const LaunchRange r{first, n};
+    const uint64_t base = index_base + first;
+    std::vector<MatchUnit> units;
+    if (!e->sub.empty()) {
+        for (uint32_t q = 0; n && q < nq; ++q) {
+            const iris_engine *c = e->sub[q];
+            units.push_back(MatchUnit{q, 1, [=](const MatchSink *ms) {
+                return timed(d, "template_match", n, [&] {
+                    return db->k.layout == IRIS_LAYOUT_TILES
+                               ? launch_template_mfma_match(d->hooks, d->stream, db->data, c->qfrag, r, ms[0])
+                               : launch_template_match(d->stream, db->data, c->qtab, r, ms[0]);
+                });
+            }});
+        }
+        return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, nullptr, kBatchMatchBudget);
+    }
+    const uint32_t bq = batch_query_group();
+    const uint32_t nqp = (nq + bq - 1) / bq * bq;  // the engine's padded queries (zero tiles)
+    const size_t tile_bytes = (size_t)16 * kPlaneGroups * 64;
+    // the sinks cross to the device from pinned memory, so the copy is a plain asynchronous one on
+    // the stream: the device's pinned result words past the nq counts the call reads back
+    const size_t stage_off = (nq * sizeof(uint64_t) + 63) / 64 * 64;
+    if (n) {
+        CHK(ensure(d, d->match_sinks, nqp * sizeof(MatchSink)));
+        CHK(ensure_host_result(d, stage_off + nqp * sizeof(MatchSink)));
+    }
+    const MatchSink *dsinks = (const MatchSink *)d->match_sinks.p;
+    // the sinks of queries q0 .. q0 + m - 1 and of the padding queries that fill their last block
+    // (host) -> their places in the device array, then the pass over those queries' tiles; every
+    // pass but the first follows a wait, so the staged sinks are never overwritten in flight
+    auto pass = [=](uint32_t q0, uint32_t m, const MatchSink *ms) -> int {
+        const uint32_t mp = (m + bq - 1) / bq * bq;
+        MatchSink *stage = (MatchSink *)((char *)d->host_result + stage_off) + q0;
+        memcpy(stage, ms, mp * sizeof(MatchSink));
+        HIPCHK(hipMemcpyAsync((void *)(dsinks + q0), stage, mp * sizeof(MatchSink), hipMemcpyHostToDevice, d->stream));
+        const BatchGeometry geo = batch_geometry(d->hooks, r, m);
+        return timed(d, "template_batch_match", n * m, [&] {
+            return launch_batch_match(d->hooks, d->stream, db->data, (const char *)e->qfrag + q0 * tile_bytes, r, geo,
+                                      dsinks + q0);
+        });
+    };
+    for (uint32_t q0 = 0; n && q0 < nq; q0 += bq) {
+        const uint32_t m = std::min(bq, nq - q0);
+        units.push_back(MatchUnit{q0, m, [=](const MatchSink *ms) { return pass(q0, m, ms); }, bq - m});
+    }
+    const MatchWhole whole{nqp, [=](const MatchSink *ms) { return pass(0, nq, ms); }};
+    return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, &whole, kBatchMatchBudget);
+}
+
+}  // extern "C"

@@ -84,7 +84,7 @@ __device__ __forceinline__ void store_tile_rows(uint16_t *__restrict__ out, uint
 }
 
 // Writes one 32-record tile's MasksEngine rows in the packed form the read-ahead windows carry over
-// the host link (32 B per record instead of 62, iris_api.hip kPackedRecBytes): record i of the
+// the host link (32 B per record instead of 62, iris_api_engines.hip kPackedRecBytes): record i of the
 // range [first, end) at pk + 32 i holds bytes 0..30 = row[k] - 64 B and byte 31 = B, where
 // B = min_k row[k] >> 6 (den <= 12800, so B <= 200), whenever every row[k] - 64 B fits a byte;
 // otherwise byte 31 is 0xFF and the row is stored in full at esc + 31 i.  Random masks never

@@ -63,6 +63,9 @@ struct DevBuf {
 };
 
 constexpr int kUploadRing = 2;  // pinned upload slots per device (db_write_pinned)
+constexpr size_t kUploadSlot = 64ull << 20;  // bytes per pinned upload slot
+constexpr int kUploadSlots = kUploadRing;                       // slots per device
+constexpr size_t kUploadTuneMin = 8ull << 20;   // writes from this size choose their path by measurement (UploadTune)
 
 // The path of a device's large writes (db_write_locked): the helper threads' pinned slots (0) or the
 // runtime's copy of the pageable source (1).  Which is faster depends on the caller's array -- the
@@ -116,7 +119,7 @@ struct iris_device {
     std::vector<Pending> pending;
     std::vector<hipEvent_t> event_pool;
     DevBuf partials, result, staging, out_a, out_b;
-    DevBuf tempdb;  // the host-slice calls' transient database (TempDb, iris_api.hip)
+    DevBuf tempdb;  // the host-slice calls' transient database (TempDb, iris_api_engines.hip)
     // threshold matching (iris_*_matches): the hits' records and the 8-byte counter a pass appends
     // through (iris::MatchSink); the counter is zeroed on the stream before every launch
     DevBuf matches, match_count;
@@ -272,6 +275,11 @@ constexpr uint32_t kBatchStreamMax = 3;
 
 namespace iris_api {
 
+// An engine's query buffer holds [table | fragments | extra], each part aligned to this
+constexpr size_t kQbufAlign = 256;
+constexpr size_t kTemplateTabBytes = (size_t)iris::kPlaneDwords * iris::kTemplateTabStride * 4;  // a template engine's LANES table
+inline size_t qalign(size_t b) { return (b + kQbufAlign - 1) / kQbufAlign * kQbufAlign; }
+
 inline int set_device(iris_device *d) {
     HIPCHK(hipSetDevice(d->ordinal));
     return 0;
@@ -349,6 +357,12 @@ inline int wait_done(iris_device *d, uint32_t seq) {
         }
         __builtin_ia32_pause();
     }
+}
+
+// The sequence number the next kernel stores into d->host_done (never 0, the word's initial value).
+inline uint32_t next_done_seq(iris_device *d) {
+    if (++d->done_seq == 0) ++d->done_seq;
+    return d->done_seq;
 }
 
 // A pinned host slot for one asynchronous search result (blocks of 256 slots).
@@ -459,6 +473,17 @@ inline int ensure_ticket(iris_device *d) {
     return 0;
 }
 
+// A completion word (iris::DoneSignal) for the blocking device-output call about to enqueue its
+// kernel: the device's ticket block, its coherent host word and the next sequence number.
+inline int done_signal(iris_device *d, iris::DoneSignal *sig) {
+    CHK(ensure_ticket(d));
+    CHK(ensure_host_done(d));
+    sig->ticket = (uint32_t *)d->ticket.p;
+    sig->done = d->host_done;
+    sig->seq = next_done_seq(d);
+    return 0;
+}
+
 inline int ensure_aux(iris_device *d) {
     if (!d->aux) HIPCHK(hipStreamCreateWithFlags(&d->aux, hipStreamNonBlocking));
     if (!d->aux2) HIPCHK(hipStreamCreateWithFlags(&d->aux2, hipStreamNonBlocking));
@@ -472,7 +497,7 @@ inline void side_sync(iris_device *d) {
     if (d->share) (void)hipStreamSynchronize(d->share);
 }
 
-// Shared by the API translation units (defined in iris_api.hip).
+// Shared by the API translation units (iris_api*.hip; each defined in one of them).
 void device_retain(iris_device *d);
 void device_release(iris_device *d);  // tears the device down with its last handle
 void engine_free(iris_engine *e);     // query buffer back to the device's pool (stream-ordered)
@@ -527,7 +552,69 @@ void resident_stats(const iris_device *d, uint64_t *count, uint64_t *bytes, int 
 // Abandoned RCCL communicator inits of device `ordinal` in this process (iris_group.hip): still
 // pending inside RCCL, and all since the process started
 void abandoned_inits(int ordinal, uint64_t *pending, uint64_t *total);
-// Partial (indices offset by base) -> iris_match_t; +inf / UINT64_MAX when none
-void match_from(const iris::Partial &r, bool any, uint64_t base, iris_match_t *out);
+// Partial (indices offset by base) -> iris_match_t; +inf / UINT64_MAX when none.  Inline: a call
+// across files cost the match lists 4 ns a record (profiles/r16_api_split.txt).
+inline void match_from(const iris::Partial &r, bool any, uint64_t base, iris_match_t *out) {
+    if (!any || r.den == 0) {
+        out->distance = INFINITY;
+        out->index = UINT64_MAX;
+        out->num = 0;
+        out->den = 0;
+        out->rotation = 0;
+    } else {
+        out->distance = (double)r.num / (double)r.den;
+        out->index = base + r.idx;
+        out->num = r.num;
+        out->den = r.den;
+        out->rotation = r.rot - IRIS_MAX_ROTATION;
+    }
+    out->reserved = 0;
+}
+
+// Argument checks that entry points of several files share (each defined in the file named); a
+// call sits where its entry point's order of checks, and so the message that wins, stays as it is.
+int range_ok(const iris_db *db, uint64_t first, uint64_t n);  // iris_api.hip
+int template_args(iris_engine *e, const iris_db *db);         // iris_api_search.hip: a single-query template engine
+int masks_batch_args(iris_engine *e, const iris_db *db);      // iris_api_engines.hip: a masks batch engine
+// iris_api_resolver.hip: the resolver calls' share arrays; a single-query masks engine; and the masks
+// kernel of a LANES database into d->out_a, the denominators of the *_masks calls
+int share_args(const uint16_t *const *shares, uint32_t parts, uint64_t n, bool denoms = true);
+int single_masks_args(const iris_engine *e, const iris_db *db, const char *batch_call);
+int enqueue_masks_denoms(const iris_engine *c, const iris_db *db, iris::LaunchRange r, const uint16_t **den);
+int ensure_upin(iris_device *d);  // iris_api.hip: the pinned upload slots (kUploadSlot bytes each), allocated once
+int db_write_locked(iris_db *db, uint64_t index, const void *records, uint64_t n);  // iris_api.hip: iris_db_write's body
+
+// One launch unit of a masks batch call: queries q0 .. q0 + m - 1 (m == 0: past the last query).
+// m > 1: one pass of the batch kernel on the queries' fragments; m == 1: the single-query forms on
+// the query's own engine, `one`.
+struct MasksUnit {
+    uint32_t q0 = 0, m = 0;
+    const void *frags[iris::kMasksBatchG] = {};
+    iris_engine *one = nullptr;
+};
+// How a masks batch call over [first, first + n) of db splits into launch units.  TILES ranges the
+// batch kernel runs (masks_batch_runs): groups of kMasksBatchG queries, the two or three left over
+// a unit of their own, a single one a unit of one.  Other TILES ranges and LANES: one query a unit.
+struct MasksWalk {
+    const iris_engine *e;
+    iris::LaunchRange r;
+    bool tiles, batch;
+    uint64_t slab;  // u16 words of a query's rows over the range: query q's slab of a part starts at q * slab
+    MasksWalk(const iris_engine *eng, const iris_db *db, uint64_t first, uint64_t n)
+        : e(eng), r{first, n}, tiles(db->k.layout == IRIS_LAYOUT_TILES),
+          batch(tiles && iris::masks_batch_runs(eng->dev->hooks, r)), slab(n * (uint64_t)iris::kRot) {}
+    MasksUnit unit(uint32_t q0) const {  // the unit that starts at query q0
+        MasksUnit u;
+        if (q0 >= e->nq) return u;
+        u.q0 = q0;
+        u.m = batch ? std::min<uint32_t>(e->nq - q0, iris::kMasksBatchG) : 1;
+        for (uint32_t s = 0; s < u.m; ++s) u.frags[s] = e->sub[q0 + s]->qfrag;
+        u.one = e->sub[q0];
+        return u;
+    }
+    void slabs(uint32_t q, const uint16_t *const *shares, uint32_t parts, const uint16_t **sl) const {
+        for (uint32_t p = 0; p < parts; ++p) sl[p] = shares[p] + q * slab;  // query q's slab of part p
+    }
+};
 
 }  // namespace iris_api

@@ -338,7 +338,7 @@ void expand_scalar(uint16_t *out, const uint8_t *pk, const uint16_t *esc, size_t
 const bool kHaveAvx512 = __builtin_cpu_supports("avx512bw") && __builtin_cpu_supports("avx512vl");
 
 // Helper threads (one pool per device) for copying an engine call's rows out of pinned memory
-// into the caller's buffer (read-ahead, iris_api.hip) and a large write's records into the pinned
+// into the caller's buffer (read-ahead, iris_api_engines.hip) and a large write's records into the pinned
 // upload slots: one core reads ~25 GB/s from DRAM, so a 1.24-MB participant-sized chunk costs
 // ~45 us on one thread.  A job is split into twice as many parts as there are threads, and parts
 // are claimed from one atomic word (the job's number in the high half, the next part in the low

@@ -1,5 +1,5 @@
 // iris_internal.hpp — device layouts, generator and launch declarations shared
-// by the HIP kernels (iris_kernels.hip) and the C ABI (iris_api.hip).
+// by the HIP kernels (iris_kernels.hip) and the C ABI (iris_api*.hip).
 //
 // Device layout: records are grouped in blocks of 64 — one
 // record per lane of a wavefront — and each block stores, for every 16-byte

@@ -349,10 +349,9 @@ int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <int G>
-int launch_slots(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
-                 uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks = nullptr,
-                 bool topk = false) {
+template <int G>  // mode = BATCH_*: BATCH_OUT writes `out`, the others read rs, BATCH_MATCH and BATCH_TOPK fill sinks
+int launch_slots(int mode, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                 LaunchRange r, uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks) {
     const BatchTiles t = batch_tiles(h, r, batch_big_tiles<G>());
     if (np) *np = t.grid;
     const uint64_t slab = r.n * (uint64_t)kRot;
@@ -361,12 +360,12 @@ int launch_slots(const Hooks &h, void *stream, const void *db, const void *const
     for (uint32_t g = 0; g < (uint32_t)G; ++g) {
         const uint32_t s = g < m ? g : 0;
         a.frag[g] = (const uint4 *)qfrags[s];
-        if (!rs) {
+        if (mode == BATCH_OUT) {
             a.out[g] = out + s * slab;
             continue;
         }
         a.slab[g] = (rs->q0 + s) * slab;
-        if (sinks) {
+        if (mode != BATCH_RESOLVE) {
             a.match[g] = sinks[s];
         } else {
             a.dist[g] = rs->dist_out ? rs->dist_out + (rs->q0 + s) * r.n : nullptr;
@@ -376,12 +375,17 @@ int launch_slots(const Hooks &h, void *stream, const void *db, const void *const
         for (uint32_t p = 0; p < rs->parts; ++p) al &= ((uintptr_t)(rs->shares[p] + a.slab[g]) & 15) == 0;
         a.aligned |= (al ? 1u : 0u) << g;
     }
-    if (!rs) return launch_group<G, BATCH_OUT>(stream, db, a, t, r);
+    if (mode == BATCH_OUT) return launch_group<G, BATCH_OUT>(stream, db, a, t, r);
     a.parts = rs->parts;
     for (uint32_t p = 0; p < rs->parts; ++p) a.shares[p] = rs->shares[p];
-    if (sinks && topk) return launch_group<G, BATCH_TOPK>(stream, db, a, t, r);
-    if (sinks) return launch_group<G, BATCH_MATCH>(stream, db, a, t, r);
+    if (mode == BATCH_TOPK) return launch_group<G, BATCH_TOPK>(stream, db, a, t, r);
+    if (mode == BATCH_MATCH) return launch_group<G, BATCH_MATCH>(stream, db, a, t, r);
     return launch_group<G, BATCH_RESOLVE>(stream, db, a, t, r);
+}
+
+int launch_mode(int mode, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
+                uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks) {
+    return (m == 2 ? launch_slots<2> : launch_slots<kMasksBatchG>)(mode, h, stream, db, qfrags, m, r, out, rs, np, sinks);  // m == 3: a slot unused
 }
 
 }  // namespace
@@ -399,17 +403,15 @@ bool masks_batch_runs(const Hooks &h, LaunchRange r) {
 uint32_t masks_batch_partials(const Hooks &h, LaunchRange r) { return r.n ? batch_tiles(h, r, 1).grid : 0; }
 
 // m = 2 .. kMasksBatchG queries (qfrags[s]: a MasksEngine's compact fragments) over [r.first, r.first +
-// r.n) of a TILES masks database in one pass; two queries run the two-slot kernel, three the
-// four-slot one with an unused slot.  rs == NULL: query s's rows go to out + s * r.n * 31; otherwise
-// the fused resolver step, see MasksBatchResolve; *np = the partials each query's run then holds.
+// r.n) of a TILES masks database in one pass.  rs == NULL: query s's rows go to out + s * r.n * 31;
+// otherwise the fused resolver step, see MasksBatchResolve; *np = the partials each query's run then holds.
 int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
                        uint16_t *out, const MasksBatchResolve *rs, uint32_t *np) {
     if (np) *np = 0;
     if (r.n == 0) return 0;
     if (m < 2 || m > (uint32_t)kMasksBatchG) return -1;
     if (rs && (rs->parts == 0 || rs->parts > 8)) return -1;
-    if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, out, rs, np);
-    return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, out, rs, np);
+    return launch_mode(rs ? BATCH_RESOLVE : BATCH_OUT, h, stream, db, qfrags, m, r, out, rs, np, nullptr);
 }
 
 // The threshold-match form of the same pass (launch_masks_batch's slots, tiles per wave and grid):
@@ -421,8 +423,7 @@ int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const
     if (r.n == 0) return 0;
     if (m < 2 || m > (uint32_t)kMasksBatchG || parts == 0 || parts > 8 || !sinks) return -1;
     const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
-    if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
-    return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
+    return launch_mode(BATCH_MATCH, h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
 }
 
 // the lists each query of a top-k pass over r writes: one per wave of the grid (launch_slots')
@@ -442,8 +443,7 @@ int launch_masks_batch_topk(const Hooks &h, void *stream, const void *db, const 
     const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
     MatchSink sinks[kMasksBatchG];
     for (uint32_t s = 0; s < m; ++s) sinks[s] = topk_sink(lists + s * stride, k);
-    if (m == 2) return launch_slots<2>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks, true);
-    return launch_slots<kMasksBatchG>(h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks, true);
+    return launch_mode(BATCH_TOPK, h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
 }
 
 }  // namespace iris

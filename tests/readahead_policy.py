@@ -1,4 +1,4 @@
-"""The read-ahead's window sizes (csrc/iris_api.hip, window_records), restated for the tests: a
+"""The read-ahead's window sizes (csrc/iris_api_engines.hip, window_records), restated for the tests: a
 walk from record 0 over `total` records in chunks of `chunk` computes its first chunk alone, then
 windows of 2, 4, 8, ... chunks, at most 160 000 records (at least one chunk) and 64 MB of
 [u16; 31] rows (window_chunks_max)."""

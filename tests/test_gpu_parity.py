@@ -187,6 +187,23 @@ def test_template_edge_cases(device, golden, layout):
             empty_pos = int(np.where(np.isinf(d))[0][0])
             z = eng.search(db, first=empty_pos, n=1)
             assert z.index == 2**64 - 1 and z.distance == np.inf
+    # no candidate -- an empty range, or only records whose mask is empty -- through every search
+    # that turns a partial into a Match: the single query, a streamed batch of 2 and (the GEMM reads
+    # TILES) a batch of 4 give +inf, no index, zero counts and rotation
+    none = (np.inf, 2**64 - 1, 0, 0, 0)
+
+    def fields(m):
+        return (m.distance, m.index, m.num, m.den, m.rotation)
+
+    assert fields(e) == none and fields(z) == none
+    with ih.Database(device, ih.KIND_TEMPLATES, 64, layout) as zdb:
+        zdb.append(np.zeros((64, 400), np.uint64))
+        with ih.TemplateEngine(device, q) as eng:
+            assert fields(eng.search(zdb)) == none and fields(eng.search(zdb, first=3, n=0)) == none
+        for nq in (2, 4) if layout == ih.LAYOUT_TILES else (2,):
+            with ih.TemplateBatchEngine(device, np.stack([q] * nq)) as be:
+                for got in (be.search(zdb), be.search(zdb, first=3, n=0)):
+                    assert [fields(m) for m in got] == [none] * nq
 
 
 def test_template_all_invalid_db(device, layout):

@@ -101,9 +101,14 @@ def test_value_arguments_are_refused_before_the_handles():
 
 def test_single_query_call_names_the_batch_call():
     """iris_resolver_matches_masks keeps refusing a masks batch engine; its message names this call."""
-    src = (ROOT / "mpc-iris-code_amd" / "csrc" / "iris_api.hip").read_text()
+    csrc = ROOT / "mpc-iris-code_amd" / "csrc"
+    src = (csrc / "iris_api_select.hip").read_text()
     body = src[src.index("int iris_resolver_matches_masks("):src.index("int iris_resolver_batch_matches_masks(")]
-    assert re.search(r'ARG\(e->nq == 0, "[^"]*' + NAME, body)
+    assert 'CHK(single_masks_args(e, db, "' + NAME + '"));' in body
+    # the shared check holds the refusal; its message ends with the name the call passes
+    args = (csrc / "iris_api_resolver.hip").read_text()
+    args = args[args.index("int iris_api::single_masks_args("):]
+    assert 'ARG(e->nq == 0, std::string("a masks batch engine runs through ") + batch_call);' in args[:args.index("}")]
 
 
 def test_cpp_program_compiles(tmp_path):

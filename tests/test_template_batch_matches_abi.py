@@ -94,10 +94,12 @@ def test_value_arguments_are_refused_before_the_handles():
 
 def test_single_query_call_still_refuses_a_batch_engine():
     """iris_template_matches goes through template_args, which refuses an engine with nq > 0."""
-    src = (ROOT / "mpc-iris-code_amd" / "csrc" / "iris_api.hip").read_text()
+    csrc = ROOT / "mpc-iris-code_amd" / "csrc"
+    src = (csrc / "iris_api_select.hip").read_text()
     body = src[src.index("int iris_template_matches("):src.index("int iris_resolver_matches(")]
     assert "CHK(template_args(e, db));" in body
-    args = src[src.index("static int template_args("):]
+    args = (csrc / "iris_api_search.hip").read_text()
+    args = args[args.index("int iris_api::template_args("):]
     assert re.search(r"ARG\(e->kind == IRIS_KIND_TEMPLATES && e->nq == 0,", args[:args.index("}")])
 
 

@@ -9,7 +9,7 @@ W=$(mktemp -d)
 mkdir -p $W/mpc-iris-code_amd
 cp -r $ROOT/mpc-iris-code_amd/Makefile $ROOT/mpc-iris-code_amd/csrc $W/mpc-iris-code_amd/
 cp -r $ROOT/include $W/
-python3 - $W/mpc-iris-code_amd/csrc/iris_api.hip <<'PY'
+python3 - $W/mpc-iris-code_amd/csrc/iris_api_engines.hip <<'PY'
 import sys
 p = sys.argv[1]; s = open(p).read()
 hdr = '''
@@ -73,7 +73,7 @@ sub('    ra.win[b].live = false;\n    ra.on[b] = side;\n    CHK(enqueue_u16_engi
 sub('    g_t0 = nowus();\n    IRIS_KEEP_DEVICE();', '    g_t0 = nowus();\n    g_cur[6] = g_cur[7] = 0;\n    IRIS_KEEP_DEVICE();')
 open(p, 'w').write(s)
 # IRIS_DIAG_PLAIN=1: the copy-out's expansion with plain stores instead of non-temporal blocks
-h = p.replace('iris_api.hip', 'iris_host.cpp'); t = open(h).read()
+h = p.replace('iris_api_engines.hip', 'iris_host.cpp'); t = open(h).read()
 old = '    if (kHaveAvx512)\n        expand_avx512(out, pk, esc, n);'
 assert t.count(old) == 1
 t = t.replace(old, '    static const bool plain = getenv("IRIS_DIAG_PLAIN") != nullptr;\n    if (kHaveAvx512)\n        (plain ? expand_plain : expand_avx512)(out, pk, esc, n);')
