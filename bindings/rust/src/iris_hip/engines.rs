@@ -658,6 +658,40 @@ impl TemplateBatchEngine {
             })
             .collect())
     }
+
+    /// Every query's k closest records of [first, first + n), best first, in one pass over the
+    /// templates (iris_template_batch_topk; k = 1..=ffi::IRIS_TOPK_MAX has no reference
+    /// counterpart): entry q is what `TemplateEngine::topk` gives for query q; indices are
+    /// `index_base + first + i`.
+    pub fn batch_topk(
+        &self,
+        db: &Database,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        k: u32,
+    ) -> Result<Vec<Vec<(f64, usize)>>> {
+        let room = k.clamp(1, ffi::IRIS_TOPK_MAX) as usize;
+        let mut buf = vec![ffi::IrisMatch::default(); self.nq * room];
+        let mut counts = vec![0u32; self.nq];
+        check(unsafe {
+            ffi::iris_template_batch_topk(
+                self.h.raw,
+                db.raw(),
+                first,
+                n,
+                index_base,
+                k,
+                buf.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        })?;
+        Ok(counts
+            .iter()
+            .enumerate()
+            .map(|(q, &c)| buf[q * room..q * room + c as usize].iter().map(match_to_pair).collect())
+            .collect())
+    }
 }
 
 #[cfg(test)]

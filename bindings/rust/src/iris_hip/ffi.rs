@@ -370,6 +370,16 @@ extern "C" {
         out: *mut IrisMatch,
         counts: *mut u32,
     ) -> c_int;
+    pub fn iris_template_batch_topk(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        k: u32,
+        out: *mut IrisMatch,
+        counts: *mut u32,
+    ) -> c_int;
     pub fn iris_topk_merge(
         records: *const IrisMatch,
         nrecords: u64,

@@ -548,12 +548,13 @@ int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint
  *
  * The value arguments (k, out, count) are checked before the handles; engine-kind, database,
  * layout and range checks and the locking are the sibling search's; the single-query calls refuse
- * a batch engine (a masks batch engine has iris_resolver_batch_topk_masks below).  There is no
- * dist_out_device.  The bytes copied back per call are 24 k per query, whatever n is.
+ * a batch engine (a masks batch engine has iris_resolver_batch_topk_masks and a template batch
+ * engine iris_template_batch_topk, both below).  There is no dist_out_device.  The bytes copied
+ * back per call are 24 k per query, whatever n is.
  *
  * Out of scope: of the batch engines, the distance batch engine (its rows are shares, no
- * distances) and the template batch engine (a follow-up; the masks batch engine has
- * iris_resolver_batch_topk_masks); the host-array forms (*_host), the asynchronous pipeline,
+ * distances; the masks batch engine has iris_resolver_batch_topk_masks and the template batch
+ * engine iris_template_batch_topk); the host-array forms (*_host), the asynchronous pipeline,
  * device groups (iris_topk_merge below is the hand-sharding answer) and k > 64. */
 #define IRIS_TOPK_MAX 64
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
@@ -597,6 +598,35 @@ int iris_resolver_topk_masks(iris_engine_t *engine, const iris_db_t *masks_db, u
 int iris_resolver_batch_topk_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
                                    const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
                                    uint32_t k, iris_match_t *out, uint32_t *counts);
+/* iris_template_batch_search's sibling, for a template batch engine (iris_template_batch_engine_new,
+ * any nq it accepts): the k closest records of every query in one pass over template records
+ * [first, first+n) (src/template.rs:43-47 per record, src/main.rs:616-621 over records, per query;
+ * k has no reference counterpart) -- many probes against one enrolled database, each probe's ranked
+ * candidates instead of its minimum alone.  One k (1..IRIS_TOPK_MAX) for the whole batch.
+ *
+ * out: host array of nq*k iris_match_t, query-major; counts (required): host array of nq uint32_t,
+ * counts[q] = min(k, records of the range with a valid rotation for query q).  out[q*k + j],
+ * j < counts[q], are the first records of the search order, best first, each filled as
+ * iris_template_topk fills it (index = index_base + first + i, reserved = 0); entries past a
+ * query's count are left untouched.  n == 0 sets every count to 0 and writes nothing else.
+ *
+ * Contract: query q's list and count are byte for byte what iris_template_topk returns for
+ * TemplateEngine(queries[q]) over the same range and index_base.  It follows that, where
+ * counts[q] > 0, out[q*k] is iris_template_batch_search's result for q, that a smaller k returns
+ * per-query prefixes and that identical calls return identical bytes.  The value arguments (k, out,
+ * counts) are checked before the handles; engine, database, layout and range checks are
+ * iris_template_batch_search's (more than 3 queries need a TILES database).  There is no
+ * dist_out_device.
+ *
+ * More than 3 queries run one pass of the batched GEMM for all of them: a workgroup of 8 waves holds
+ * 2 queries x 16 tiles (2 x 2 per wave), G workgroups share a query group, and every wave keeps one
+ * resident sorted list per query of its own across its N-groups -- 8 G lists of k records a query,
+ * folded 64 lists at a time by the merge levels for all queries together.  The lists take
+ * nqp (8 G + ceil(8 G / 64)) k records of the device's match buffer (nqp: nq padded to 4); top-k
+ * always fits, so no pass runs twice.  Up to 3 queries run iris_template_topk's own pass each.  The
+ * call waits once and copies back 24 k bytes per query. */
+int iris_template_batch_topk(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                             uint64_t index_base, uint32_t k, iris_match_t *out, uint32_t *counts);
 /* Host only, no device: merges top-k lists (of shards, chunks, GPUs) that carry global indices
  * into one -- the top-k counterpart of iris_match_merge, src/main.rs:616-621 generalised to k.
  * The same order over nrecords records; records with den == 0 or index == UINT64_MAX are

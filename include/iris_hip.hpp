@@ -780,6 +780,19 @@ public:
         }
         return res;
     }
+    // Every query's k closest records, best first, in one pass over the templates
+    // (iris_template_batch_topk; k = 1..IRIS_TOPK_MAX has no reference counterpart): result[q] is what
+    // TemplateEngine(queries[q]).topk gives over the same range; indices are index_base + first + i.
+    std::vector<std::vector<Match>> topk(const Database &db, uint32_t k, uint64_t first, uint64_t n,
+                                         uint64_t index_base = 0) const {
+        const uint32_t room = k && k <= IRIS_TOPK_MAX ? k : 1;
+        std::vector<Match> flat((size_t)nq_ * room);
+        std::vector<uint32_t> counts(nq_);
+        check(iris_template_batch_topk(h_, db.handle(), first, n, index_base, k, flat.data(), counts.data()));
+        std::vector<std::vector<Match>> res(nq_);
+        for (uint32_t q = 0; q < nq_; ++q) res[q].assign(flat.begin() + (size_t)q * room, flat.begin() + (size_t)q * room + counts[q]);
+        return res;
+    }
 
 private:
     uint32_t nq_ = 0;

@@ -307,20 +307,27 @@ int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     });
 }
 
-// A launch unit of a batched top-k call: m queries from q0 on (m <= kMasksBatchG) whose pass writes
-// `lists` lists of k records per query; launch(base, stride) enqueues the pass(es), query q0 + s
-// storing its lists at base + s * stride.
+// A launch unit of a batched top-k call: m queries from q0 on (a masks pass: m <= kMasksBatchG; the
+// template batch GEMM: all of them) whose pass writes `lists` lists of k records per query;
+// launch(base, stride) enqueues the pass(es), query q0 + s storing its lists at base + s * stride.
+// A pass whose kernel writes lists for more queries than the unit has (the GEMM's padding queries)
+// asks for `pad` more regions after them; nobody reads those.
 struct TopkUnit {
     uint32_t q0, m;
     uint64_t lists;
     std::function<int(Partial *, uint64_t)> launch;
+    uint32_t pad = 0;
 };
 
+// A merge launch takes at most this many queries (blockIdx.y, launch_topk_merge_level)
+constexpr uint32_t kTopkMergeSlots = 65535;
+
 // topk_run for the nq queries of a batch engine.  One lists region of the device's match buffer
-// -- per query of a unit its lists and then the merge's spare lists, (lists + spare) * k records,
-// at most kMasksBatchG queries -- serves every unit in stream order: a unit's merge has consumed the
+// -- per query of a unit its lists and then the merge's spare lists, (lists + spare) * k records
+// -- serves every unit in stream order: a unit's merge has consumed the
 // region before the next unit's pass writes it.  Each unit's pass is followed by its merge levels,
-// one launch per level for the unit's queries together (launch_topk_merge_level); the last level
+// one launch per level for the unit's queries together (launch_topk_merge_level; a unit of more
+// than kTopkMergeSlots queries: one launch per kTopkMergeSlots of them); the last level
 // writes query q's k records at q * k of the pinned host result.  The call waits once; every
 // query's count is the length of its list's valid prefix.
 static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k, iris_match_t *out, uint32_t *counts,
@@ -328,7 +335,7 @@ static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k,
     for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
     if (n == 0) return 0;
     uint64_t room = 0;
-    for (const TopkUnit &u : units) room = std::max(room, u.m * (u.lists + topk_spare_lists(u.lists)) * k);
+    for (const TopkUnit &u : units) room = std::max(room, (uint64_t)(u.m + u.pad) * (u.lists + topk_spare_lists(u.lists)) * k);
     CHK(ensure(d, d->matches, room * sizeof(Partial)));
     CHK(ensure_host_result(d, (size_t)nq * k * sizeof(Partial)));
     Partial *region = (Partial *)d->matches.p, *res = (Partial *)d->host_result;
@@ -339,10 +346,14 @@ static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k,
         for (uint64_t left = u.lists;;) {
             const uint64_t groups = topk_spare_lists(left);
             const bool last = groups == 1;
-            CHK(timed(d, "topk_merge", left * u.m, [&] {
-                return launch_topk_merge_level(d->stream, src, left, k, last ? res + (size_t)u.q0 * k : dst, u.m, stride,
-                                               last ? k : stride);
-            }));
+            for (uint32_t s0 = 0; s0 < u.m; s0 += kTopkMergeSlots) {
+                const uint32_t slots = std::min(kTopkMergeSlots, u.m - s0);
+                CHK(timed(d, "topk_merge", left * slots, [&] {
+                    return launch_topk_merge_level(d->stream, src + s0 * stride, left, k,
+                                                   last ? res + ((size_t)u.q0 + s0) * k : dst + s0 * stride, slots, stride,
+                                                   last ? k : stride);
+                }));
+            }
             if (last) break;
             left = groups;
             std::swap(src, dst);
@@ -464,7 +475,7 @@ constexpr uint64_t kBatchMatchBudget = 256ull << 20;
 
 // iris_template_batch_search's threshold sibling, and that call's checks and dispatch.  Engines of
 // up to kBatchStreamMax queries: one single-query match pass per query ("template_match"), all
-// enqueued before the one wait.  The GEMM: one launch of batch_lds_kernel<..., MATCH>
+// enqueued before the one wait.  The GEMM: one launch of batch_lds_kernel<..., BL_MATCH>
 // ("template_batch_match") over all query groups, every query appending to its own sink of the
 // device array d->match_sinks; what runs again when a list overflows is the aligned block of
 // batch_query_group() queries, independent of the kernel shape, launched on its own query tiles.
@@ -530,6 +541,58 @@ int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t 
     }
     const MatchWhole whole{nqp, [=](const MatchSink *ms) { return pass(0, nq, ms); }};
     return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, &whole, kBatchMatchBudget);
+}
+
+// iris_template_batch_search's top-k sibling, with iris_template_batch_matches' checks and dispatch.
+// Engines of up to kBatchStreamMax queries: one single-query top-k pass per query ("template_topk")
+// and its merge, all enqueued before the one wait.  The GEMM: one launch of
+// batch_lds_kernel<..., BL_TOPK> ("template_batch_topk") over all query groups, every wave storing
+// one list per query of its own -- 8 G lists a query in both kernel shapes -- and then the merge
+// levels for all queries together.  The lists region holds nqp (8 G + ceil(8 G / 64)) k records
+// (DESIGN.md 4.14); top-k always fits, so there is no overflow rule and no second pass.
+int iris_template_batch_topk(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                             uint32_t k, iris_match_t *out, uint32_t *counts) {
+    IRIS_KEEP_DEVICE();
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");  // the value arguments first
+    ARG(out, "out is NULL");
+    ARG(counts, "counts is NULL");
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
+    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
+    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
+        "batched search of more than 3 queries needs a template database in the TILES layout");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    const LaunchRange r{first, n};
+    const uint64_t base = index_base + first;
+    std::vector<TopkUnit> units;
+    if (!e->sub.empty()) {
+        const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+        const uint64_t lists = n ? (tiles ? mfma_topk_units(d->hooks, r) : template_topk_units(r)) : 0;
+        for (uint32_t q = 0; n && q < nq; ++q) {
+            const iris_engine *c = e->sub[q];
+            units.push_back(TopkUnit{q, 1, lists, [=](Partial *buf, uint64_t) {
+                return timed(d, "template_topk", n, [&] {
+                    return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, c->qfrag, r, topk_sink(buf, k))
+                                 : launch_template_topk(d->stream, db->data, c->qtab, r, topk_sink(buf, k));
+                });
+            }});
+        }
+        return topk_run_units(d, n, base, k, out, counts, nq, units);
+    }
+    if (n) {
+        const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
+        units.push_back(TopkUnit{0, nq, batch_topk_units(geo), [=](Partial *lists, uint64_t stride) {
+            return timed(d, "template_batch_topk", n * nq, [&] {
+                return launch_batch_topk(d->hooks, d->stream, db->data, e->qfrag, r, geo, lists, stride, k);
+            });
+        }, geo.nqg * geo.qper - nq});
+    }
+    return topk_run_units(d, n, base, k, out, counts, nq, units);
 }
 
 }  // extern "C"

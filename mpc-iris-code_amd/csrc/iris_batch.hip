@@ -13,11 +13,10 @@
 // groups.  Per query the kernel keeps a running best (exact fraction, lowest
 // index), one partial per (query, workgroup), reduced by batch_reduce_kernel.  The threshold-match
 // form (iris_template_batch_matches) keeps the walk and appends, per query, the records below the
-// threshold to the query's own MatchSink instead.
+// threshold to the query's own MatchSink instead.  The top-k form (iris_template_batch_topk) keeps
+// the walk too and holds, per wave and query, a sorted list of the k closest records so far.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
-
-#include <type_traits>
 
 #include "iris_device.hpp"
 
@@ -87,16 +86,45 @@ __global__ void __launch_bounds__(256) batch_reduce_kernel(const Partial *__rest
 // IRIS_BATCH_KERNEL=2 test hook): BQL = 4, WQL = 4, WT = 1 (8 tiles per N-group, the round-2
 // shape), whose SIMD partners run their N-groups half a group apart (kStagger).
 //
-// MATCH (iris_template_batch_matches): the same walk with another end of an N-group.  outp is then
+// MODE: BL_SEARCH is the form described so far.
+//
+// BL_MATCH (iris_template_batch_matches): the same walk with another end of an N-group.  outp is then
 // the device array of the launch's MatchSinks, one per padded query (qtiles' order); a wave reads
 // its WQL sinks once before the walk and, per tile and query, appends the records whose best
 // rotation lies below the threshold (best_rotation + match_hit, then append_matches<WT> per query).  No running
 // best, no reduction and no partials: the kernel ends with the walk.
-template <int NW, int WT, int WQL, int BQL, bool MATCH = false, int GPL = 4>
+//
+// BL_TOPK (iris_template_batch_topk): the match form up to each (query, tile)'s best rotation; the
+// candidates of half 0 then go into the wave's sorted list of that query (topk_insert, one list per
+// query of the wave, in the registers of the search form's running best, resident across the wave's
+// N-groups).  After the walk EVERY wave of the grid -- one whose tiles were all clamped and a
+// workgroup without an N-group too, the merge reads every list -- stores its lists with plain vector
+// stores: query q's at outp.lists + q * outp.stride + unit * outp.k, unit = gi * (NW / QW) + tset,
+// (NW / QW) * G lists per query.  A padding query's zero tile gives den = 0 in every row, so its
+// lists stay empty.  No shuffle reduction, no LDS hand-off, no partials and no reduce.
+enum { BL_SEARCH = 0, BL_MATCH = 1, BL_TOPK = 2 };
+struct BatchTopkLists {
+    Partial *lists;   // [query of the launch][units + spare][k]
+    uint64_t stride;  // records between two queries' lists
+    uint32_t k;       // 1..kTopkMax
+};
+template <int MODE>
+struct BatchOut {
+    typedef Partial *__restrict__ type;  // one partial per (query, workgroup)
+};
+template <>
+struct BatchOut<BL_MATCH> {
+    typedef const MatchSink *__restrict__ type;
+};
+template <>
+struct BatchOut<BL_TOPK> {
+    typedef BatchTopkLists type;
+};
+template <int NW, int WT, int WQL, int BQL, int MODE = BL_SEARCH, int GPL = 4>
 __global__ void __launch_bounds__(64 * NW, 1)
     batch_lds_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qtiles, uint64_t tile0, uint64_t ntiles,
-                     uint64_t first, uint64_t end, uint32_t nqg, uint32_t G,
-                     typename std::conditional<MATCH, const MatchSink, Partial>::type *__restrict__ outp) {
+                     uint64_t first, uint64_t end, uint32_t nqg, uint32_t G, typename BatchOut<MODE>::type outp) {
+    constexpr bool MATCH = MODE == BL_MATCH;
     constexpr int kGP = GPL;                        // chunk pairs per K-step
     constexpr int kSteps = kPlaneGroups / kGP;
     static_assert(kPlaneGroups % kGP == 0, "K-step must tile the 100 chunk pairs");
@@ -187,6 +215,12 @@ __global__ void __launch_bounds__(64 * NW, 1)
         const int qs = __builtin_amdgcn_readfirstlane(w) % QW;
 #pragma unroll
         for (int qi = 0; qi < WQL; ++qi) sink[qi] = outp[qg * kBQ + qs * WQL + qi];
+    }
+    // BL_TOPK: this lane's entry of the wave's list of each of its queries (topk_insert)
+    Partial list[WQL];
+    if constexpr (MODE == BL_TOPK) {
+#pragma unroll
+        for (int qi = 0; qi < WQL; ++qi) list[qi] = partial_none();
     }
     v16f den[WQL][WT], sacc[WQL][WT];
     auto zero = [&] {
@@ -310,6 +344,30 @@ __global__ void __launch_bounds__(64 * NW, 1)
                 }
 #pragma unroll
                 for (int qi = 0; qi < WQL; ++qi) append_matches<WT>(sink[qi], lane, hit[qi], bn[qi], bd[qi], br[qi], idx);
+            } else if constexpr (MODE == BL_TOPK) {
+                // the match form's decision (best_rotation, the same `valid`, half 0 proposes), one
+                // (query, tile) at a time: each candidate set goes into its query's list before the
+                // next is computed, so no decision is held beside the accumulators
+#pragma unroll
+                for (int t = 0; t < WT; ++t) {
+                    const uint64_t trel = (gi + (uint64_t)j * G) * kTilesPerGroup + tset * WT + t;
+                    const uint64_t tg = (tile0 + trel) * 32 + (lane & 31);
+                    const bool valid = live && trel < ntiles && tg >= first && tg < end;
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) {
+                        Partial c;
+                        c.pad = 0;
+                        c.idx = tg - first;
+                        best_rotation(
+                            lane,
+                            [&](int r, uint32_t &nn, uint32_t &dd) {
+                                dd = (uint32_t)den[qi][t][r];
+                                nn = (uint32_t)(((int)dd - (int)sacc[qi][t][r]) >> 1);
+                            },
+                            c.num, c.den, c.rot);
+                        topk_insert(list[qi], outp.k, lane, c, valid && h == 0);
+                    }
+                }
             } else {
                 // per lane and query: the best of the lane's 16 rotation rows, folded into the
                 // lane's running best (no cross-lane work until the end of the walk)
@@ -352,7 +410,15 @@ __global__ void __launch_bounds__(64 * NW, 1)
         barrier();
     }
 
-    if constexpr (!MATCH) {
+    if constexpr (MODE == BL_TOPK) {
+        const uint64_t unit = (uint64_t)gi * (NW / QW) + tset;
+#pragma unroll
+        for (int qi = 0; qi < WQL; ++qi) {
+            const uint64_t q = (uint64_t)qg * kBQ + qset * WQL + qi;
+            topk_store(MatchSink{outp.lists + q * outp.stride, outp.k, nullptr, 0.0}, unit, lane, list[qi]);
+        }
+    }
+    if constexpr (MODE == BL_SEARCH) {
         // the lanes' running bests -> one Partial per query (lane qi holds query qi's): exact
         // fraction, then the lowest index, then the lowest rotation (the two halves of a
         // template's rotations live in lanes l and l ^ 32)
@@ -436,9 +502,25 @@ int launch_batch(const Hooks &h, void *stream, const void *db, const void *qtile
 int launch_batch_match(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
                        const BatchGeometry &g, const MatchSink *sinks) {
     if (r.n == 0) return 0;
-    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, true> : batch_lds_kernel<8, 2, 2, 2, true>;
+    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_MATCH> : batch_lds_kernel<8, 2, 2, 2, BL_MATCH>;
     hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
                        (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G, sinks);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The top-k form of that pass: every wave of the grid stores its k best records of query q of g
+// (g.nqg * g.qper queries, in qtiles' order) at lists + q * stride + unit * k;
+// batch_topk_units = the lists per query.  One launch, no reduce; nothing needs zeroing.
+uint64_t batch_topk_units(const BatchGeometry &g) { return (uint64_t)g.G * 8; }
+
+int launch_batch_topk(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                      const BatchGeometry &g, Partial *lists, uint64_t stride, uint32_t k) {
+    if (r.n == 0) return 0;
+    if (k == 0 || k > kTopkMax || stride < batch_topk_units(g) * k) return -1;
+    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_TOPK> : batch_lds_kernel<8, 2, 2, 2, BL_TOPK>;
+    hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
+                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G,
+                       BatchTopkLists{lists, stride, k});
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

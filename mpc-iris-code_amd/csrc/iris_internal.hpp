@@ -368,10 +368,16 @@ BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq);
 uint32_t batch_query_group();  // padding unit of a batched engine's queries
 int launch_batch(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r, const BatchGeometry &g,
                  Partial *partials, Partial *out, uint64_t idx_base = 0);
-// the threshold-match form of that pass (batch_lds_kernel<..., MATCH>): sinks = DEVICE array of one
+// the threshold-match form of that pass (batch_lds_kernel<..., BL_MATCH>): sinks = DEVICE array of one
 // MatchSink per query of g (g.nqg * g.qper, in qtiles' order; a padding query's has cap 0)
 int launch_batch_match(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
                        const BatchGeometry &g, const MatchSink *sinks);
+// the top-k form of that pass (batch_lds_kernel<..., BL_TOPK>): every wave of the grid stores its k
+// best records of query q of g (g.nqg * g.qper queries, in qtiles' order; a padding query's lists
+// stay empty) at lists + q * stride + unit * k; batch_topk_units = the lists per query
+uint64_t batch_topk_units(const BatchGeometry &g);
+int launch_batch_topk(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                      const BatchGeometry &g, Partial *lists, uint64_t stride, uint32_t k);
 int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
                     double *dist_out, Partial *partials);
 int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,

@@ -200,6 +200,8 @@ def load_library(path=None):
                                           ctypes.POINTER(Match), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_resolver_batch_topk_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_uint32,
                                                 ctypes.POINTER(Match), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "iris_template_batch_topk": ([P, P, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(Match),
+                                          ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_topk_merge": ([ctypes.POINTER(Match), u64, ctypes.c_uint32, ctypes.POINTER(Match),
                                  ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
@@ -272,7 +274,7 @@ def exported_symbols():
         "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
         "iris_resolver_batch_matches_masks", "iris_template_batch_matches",
         "iris_template_topk", "iris_resolver_topk", "iris_resolver_topk_masks", "iris_topk_merge",
-        "iris_resolver_batch_topk_masks",
+        "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
     ]
 
 
@@ -1204,6 +1206,19 @@ class TemplateBatchEngine(_Engine):
             call(buf, cap)
         totals = [int(c) for c in counts]
         return [[buf[q * cap + j] for j in range(min(cap, totals[q]))] for q in range(self.nq)], totals
+
+    def topk(self, db, k, first=0, n=None, index_base=0):
+        """Every query's k closest records, best first, in one pass over the templates
+        (iris_template_batch_topk; k = 1..TOPK_MAX has no reference counterpart).  -> list of nq
+        lists: entry q is the list[Match] TemplateEngine(queries[q]).topk gives over the same range
+        (indices index_base + first + i)."""
+        n = (len(db) - first) if n is None else n
+        room = max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1
+        out = (Match * (self.nq * room))()
+        counts = (ctypes.c_uint32 * self.nq)()
+        _check(load_library().iris_template_batch_topk(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                       int(k), out, counts))
+        return [[_copy_match(out[q * room + j]) for j in range(counts[q])] for q in range(self.nq)]
 
 
 class DistanceBatchEngine(_Engine):
