@@ -445,6 +445,35 @@ __device__ __forceinline__ uint4 frag_load(GlobalFrag p) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// A round's epilogue: each query's best rotation per record of the T tiles from tw, folded into
+// best[].  Tiles past the range (tw + t >= ntiles: the loop streamed a clamped one) give no candidate.
+template <int NQ, int T>
+__device__ __forceinline__ void round_candidates(const v16f (&den)[NQ][T], const v16f (&s)[NQ][T], uint64_t tile0,
+                                                 uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
+                                                 Partial (&best)[NQ]) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+        const bool valid = (tw + t < ntiles) && tg >= first && tg < end;
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) {
+            uint32_t bn, bd;
+            int br;
+            best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
+                dd = (uint32_t)den[qi][t][r];
+                nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);  // num = (den - S) / 2
+            }, bn, bd, br);
+            Partial c;
+            c.num = bn;
+            c.den = valid ? bd : 0;
+            c.rot = br;
+            c.pad = 0;
+            c.idx = tg - first;
+            if (partial_better_dev(c, best[qi])) best[qi] = c;
+        }
+    }
+}
+
 template <int NQ, int T>
 __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[NQ], uint64_t tile0,
                                             uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
@@ -510,28 +539,108 @@ __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const 
         if constexpr (kPlaneGroups % 3 >= 1) compute(sa);
         if constexpr (kPlaneGroups % 3 == 2) compute(sb);
     }
+    round_candidates<NQ, T>(den, s, tile0, ntiles, tw, first, end, lane, best);
+}
 
+// The two-query round (2 queries x 2 tiles per wave) with the query operands staged once per
+// workgroup.  Through registers every wave pulls the same 4 KB of fragments per step out of L2 --
+// twice its 2 KB of templates -- and derives the den operand from each of them again.  Here the
+// 256 threads fetch a step's 4 KB with one 16-B load each: wave w fetches fragment 2 g + (w & 1) of
+// query w >> 1, applies qfrag_of once and writes both operands to a two-slot LDS ring
+// [slot][query][chunk of the step][am, ae][lane] (lane-linear 1-KB rows: ds_read_b128 without
+// conflicts); every wave reads the step's 8 operands from there.
+//   The fetch rides in the register stage of its step, behind the stage's two template loads, so
+// the stage is 12 VGPRs instead of 24 and the ring is DEPTH deep: loads retire in order, and the
+// wait for step g + 1's fragment ahead of its LDS write leaves the template loads of steps
+// g + 2 .. g + DEPTH - 1 in flight.  One barrier per step: slot (g + 1) & 1 was last read in step
+// g - 1, before that step's barrier.
+//   Every wave of the workgroup walks all 100 steps -- the barriers and the fetch duty do not
+// depend on ntiles.  A wave whose tiles lie past the range streams the clamped last tile, as
+// partial waves do, and `valid` drops its candidates.  Nothing in the walk branches on anything
+// that is not workgroup-uniform.
+constexpr int kStagedDepth = 4;  // 242 VGPRs; 5: 255, no faster; 6 spills
+typedef uint4 FragRing[2][2][2][2][64];
+
+template <int DEPTH>
+__device__ __forceinline__ void staged_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[2], uint64_t tile0,
+                                             uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
+                                             int wslot, FragRing &ring, Partial (&best)[2]) {
+    constexpr int T = 2;
+    static_assert(kWaveSlots == 4 && DEPTH >= 3, "one fetch per wave: 2 queries x 2 chunks of a step");
+    v16f den[2][T], s[2][T];
+#pragma unroll
+    for (int qi = 0; qi < 2; ++qi)
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                den[qi][t][i] = 0.f;
+                s[qi][t][i] = 0.f;
+            }
+
+    const uint4 *dp[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
-        const bool valid = active && (tw + t < ntiles) && tg >= first && tg < end;
-#pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) {
-            uint32_t bn, bd;
-            int br;
-            best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
-                dd = (uint32_t)den[qi][t][r];
-                nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);  // num = (den - S) / 2
-            }, bn, bd, br);
-            Partial c;
-            c.num = bn;
-            c.den = valid ? bd : 0;
-            c.rot = br;
-            c.pad = 0;
-            c.idx = tg - first;
-            if (partial_better_dev(c, best[qi])) best[qi] = c;
-        }
+        const uint64_t rel = (tw + t < ntiles) ? tw + t : ntiles - 1;  // clamp: extra tiles re-read a valid one
+        dp[t] = db + (tile0 + rel) * (uint64_t)kTileUint4 + lane;
     }
+    const int fq = wslot >> 1, fc = wslot & 1;  // this wave's fetch duty (wave-uniform)
+    const GlobalFrag fp = (fq ? qf[1] : qf[0]) + fc * 64 + lane;
+    struct Stage {
+        uint4 d[T];
+        uint4 f;
+    };
+    auto load = [&](Stage &st, int g) {
+        g = g < kPlaneGroups ? g : kPlaneGroups - 1;
+#pragma unroll
+        for (int t = 0; t < T; ++t) st.d[t] = stream_load(dp[t] + g * 64);
+        st.f = frag_load(fp + (2 * g) * 64);
+        __builtin_amdgcn_sched_barrier(0);  // as in template_mfma_kernel: the stage's loads stay together
+    };
+    auto stage_frag = [&](const Stage &st, int slot) {
+        const QFrag f = qfrag_of(st.f);
+        ring[slot][fq][fc][0][lane] = make_uint4(f.am[0], f.am[1], f.am[2], f.am[3]);
+        ring[slot][fq][fc][1][lane] = st.f;
+    };
+    auto operand = [&](int slot, int qi, int c, int e) {
+        const uint4 v = ring[slot][qi][c][e][lane];
+        return v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+    };
+    auto compute = [&](const Stage &st, int slot) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int qi = 0; qi < 2; ++qi) {
+                QFrag f;
+                f.am = operand(slot, qi, c, 0);
+                f.ae = operand(slot, qi, c, 1);
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    chunk_step(c ? st.d[t].z : st.d[t].x, c ? st.d[t].w : st.d[t].y, f, den[qi][t], s[qi][t]);
+            }
+    };
+    // step g: the loads of step g + DEPTH - 1, the step's MFMAs from slot g & 1, then step g + 1's
+    // operands into the other slot (past the last step: the clamped fragment, never read)
+    auto step = [&](Stage &free_, const Stage &cur, const Stage &next, int g) {
+        load(free_, g + DEPTH - 1);
+        compute(cur, g & 1);
+        stage_frag(next, (g + 1) & 1);
+        __syncthreads();
+    };
+    Stage st[DEPTH];
+#pragma unroll
+    for (int i = 0; i < DEPTH - 1; ++i) load(st[i], i);
+    stage_frag(st[0], 0);
+    __syncthreads();
+    int g = 0;
+#pragma unroll 1
+    for (; g + DEPTH <= kPlaneGroups; g += DEPTH) {
+#pragma unroll
+        for (int i = 0; i < DEPTH; ++i) step(st[(i + DEPTH - 1) % DEPTH], st[i], st[(i + 1) % DEPTH], g + i);
+    }
+#pragma unroll
+    for (int i = 0; i < kPlaneGroups % DEPTH; ++i) step(st[(i + DEPTH - 1) % DEPTH], st[i], st[(i + 1) % DEPTH], g + i);
+    round_candidates<2, T>(den, s, tile0, ntiles, tw, first, end, lane, best);
 }
 
 // A round's bests of NQ queries -> the wave's entries sh[qi * N + pos] (LDS: nothing of a round
@@ -620,6 +729,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     };
     constexpr int kRounds = kMfmaTiles / 2;
     __shared__ Partial sh_best[2 * kRounds * kWaveSlots];
+    __shared__ FragRing sh_ring;  // the two-query rounds' operands (static: a solo workgroup holds it too)
     if (!shared) {
         Partial best[1] = {partial_none()};
         const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
@@ -633,7 +743,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
 #pragma unroll  // two copies of the loop: kept as a loop, the round counter and tile numbers spill
     for (int rd = 0; rd < kRounds; ++rd) {
         Partial best[2] = {partial_none(), partial_none()};
-        share_round<2, 2>(db, qf, tile0, ntiles, tw + 2 * rd, first, end, lane, best);
+        staged_round<kStagedDepth>(db, qf, tile0, ntiles, tw + 2 * rd, first, end, lane, wslot, sh_ring, best);
         share_stash<2, kRounds * kWaveSlots>(best, lane, rd * kWaveSlots + wslot, sh_best);
     }
     const GlobalPartial out[2] = {(GlobalPartial)partials, (GlobalPartial)uniform64(sh_guest[1])};
