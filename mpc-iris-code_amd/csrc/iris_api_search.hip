@@ -33,7 +33,16 @@ int share_take(iris_device *d, uint32_t np, SharePass **out) {
         if (hipEventQuery(s.ended) != hipSuccess) return 0;
         if (s.guest >= 0 && hipEventQuery(d->share_ring[s.guest].ended) != hipSuccess) return 0;
     }
-    if (!d->share) HIPCHK(hipStreamCreateWithFlags(&d->share, hipStreamNonBlocking));
+    if (!d->share) {
+        // at the highest priority, for the hardware queue: the runtime keeps its hardware queues per
+        // priority and, once a process holds GPU_MAX_HW_QUEUES streams of one priority (4 by default;
+        // a device with asynchronous searches has four itself), maps further streams onto the queues
+        // in use.  A registration on the device stream's queue waits behind the pass that should
+        // host it, and no search is ever carried (tests/test_gpu_seams.py met that).
+        int least = 0, greatest = 0;
+        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(hipStreamCreateWithPriority(&d->share, hipStreamNonBlocking, greatest));
+    }
     if (!d->share_reg) HIPCHK(hipEventCreateWithFlags(&d->share_reg, hipEventDisableTiming));
     if (!d->share_count) {
         void *p = nullptr;
