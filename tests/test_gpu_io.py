@@ -64,18 +64,26 @@ def test_capacity_checked(device, tmp_path):
         assert db.load_file(path, count=cap) == cap
 
 
-@pytest.fixture(params=["slots", "windows", "pread"])
-def load_device(request, device, hooked_device):
-    """The loader's three paths: reader threads pread into the two pinned upload slots (the
-    default for a load with no other in flight), DMA from registered page-cache windows of the
-    mapping (a concurrent per-device load in a group; forced by the IRIS_LOAD_WINDOWS test
-    hook), and pread into the loader's own pinned buffers (the fallback when the pages cannot
-    be registered; forced by IRIS_LOAD_PREAD)."""
-    if request.param == "pread":
+LOAD_PATHS = ["slots", "windows", "pread"]
+
+
+def open_load_path(path, device, hooked_device):
+    """A device whose loads take one of the loader's three paths: reader threads pread into the
+    two pinned upload slots (the default for a load with no other in flight), DMA from registered
+    page-cache windows of the mapping (a concurrent per-device load in a group; forced by the
+    IRIS_LOAD_WINDOWS test hook), and pread into the loader's own pinned buffers (the fallback
+    when the pages cannot be registered; forced by IRIS_LOAD_PREAD)."""
+    if path == "pread":
         return hooked_device(IRIS_LOAD_PREAD="1")
-    if request.param == "windows":
+    if path == "windows":
         return hooked_device(IRIS_LOAD_WINDOWS="1")
+    assert path == "slots"
     return device
+
+
+@pytest.fixture(params=LOAD_PATHS)
+def load_device(request, device, hooked_device):
+    return open_load_path(request.param, device, hooked_device)
 
 
 def test_multi_chunk_unaligned_templates(load_device, tmp_path):

@@ -945,13 +945,11 @@ def test_large_write_paths(hooked_device, path):
     with ih.Database(dev, ih.KIND_MASKS, n + 100) as db:
         db.append(masks[:3])
         db.append(masks[3:])
-        for lo in (0, 40_000, n - 50):
-            assert (db.read(lo, 50) == masks[lo:lo + 50]).all(), lo
+        assert (db.read(0, n) == masks).all()  # in full: every slot seam (tests/test_gpu_db_io.py has the small forms)
         shares = rng.integers(0, 2**16, (5_300, 12800), dtype=np.uint16)  # 136 MB, three slots
         with ih.Database(dev, ih.KIND_SHARES, 5_300) as sdb:
             sdb.append(shares)
-            for lo in (0, 2_559, 2_560, 5_250):
-                assert (sdb.read(lo, 50) == shares[lo:lo + 50]).all(), lo
+            assert (sdb.read(0, 5_300) == shares).all()
 
 
 def test_upload_path_tuning(hooked_device):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import iris_hip as ih
+import packed_boundary as pb
 import readahead_policy as ra_policy
 from oracle import oracle_c as oc
 
@@ -500,6 +501,44 @@ def test_packed_rows_escape_path(device, hooked_device, tmp_path):
     with ih.MasksEngine(unpacked, q) as eng:
         assert (walk(eng, recs) == want).all()
         assert (walk(eng, recs, chunk=7_777) == want).all()
+    del recs
+
+
+def test_packed_rows_boundary(device, hooked_device, tmp_path):
+    """The packing boundary itself (packed_boundary.py; the fixture's facts are checked on the CPU
+    by test_packed_boundary.py): records whose rows span exactly 255 (packed, an offset byte of
+    255) and exactly 256 (escaped) above a base with min % 64 = 63 and = 0, with the extremes in
+    either half of the MFMA C layout and swapped (the mirrors), the all-zero row, and -- under the
+    all-ones query -- the all-ones mask, whose base byte is 200, the largest.  They sit at the
+    first, a middle and the 32nd record of the first and last tile of a chunk and in the file's
+    last, partial tile, among random masks.  The file is 10 chunks of 3 tiles and 29 records, the
+    smallest that has all those places: a walk of it with a fresh engine is served by growing
+    read-ahead windows (counted as in test_long_walk_windows_grow).  Every row equals the
+    oracle's, in chunks of 96 (windows on tile boundaries) and of 100 (not), and with the packing
+    off (IRIS_READAHEAD_PACKED=0)."""
+    host, where = pb.planted_file()
+    n, chunk = host.shape[0], pb.CHUNK
+    path = tmp_path / "b.masks"
+    host.tofile(path)
+    recs = mapped(path, ih.KIND_MASKS, n)
+    want_windows = ra_policy.windows(n, chunk)
+    assert len(want_windows) >= 4 and max(want_windows) >= 4 * chunk  # the windows grow
+    unpacked = hooked_device(IRIS_READAHEAD_PACKED="0")
+    for q in (pb.QUERY, pb.ONES):
+        want = oc.masks_batch(q, host)
+        with ih.MasksEngine(device, q) as eng:
+            assert (walk(eng, recs, chunk) == want).all()  # fills the copy
+        for ch in (chunk, 100):
+            with ih.MasksEngine(device, q) as eng:
+                out, (launches, records, largest) = walk_counted(device, eng, recs, ch)
+            bad = np.flatnonzero((out != want).any(axis=1))
+            assert bad.size == 0, [(int(i), where.get(int(i))) for i in bad[:8]]
+            assert records == n, (records, n)  # every record from a window, once
+            if ch == chunk:
+                assert (launches, largest) == (len(want_windows), max(want_windows)), (launches, largest)
+        with ih.MasksEngine(unpacked, q) as eng:
+            for ch in (chunk, 100):
+                assert (walk(eng, recs, ch) == want).all()
     del recs
 
 
