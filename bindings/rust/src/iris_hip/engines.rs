@@ -509,6 +509,33 @@ impl Drop for PendingSearch {
     }
 }
 
+/// An enqueued threshold-match pass (`iris_template_matches_async`); `wait` blocks for it alone
+/// and returns what `TemplateEngine::matches` with `Some(cap)` returns.
+pub struct PendingMatches {
+    raw: *mut ffi::IrisPendingMatches,
+    cap: u64,
+}
+
+unsafe impl Send for PendingMatches {}
+
+impl PendingMatches {
+    pub fn wait(mut self) -> Result<(Vec<(f64, usize)>, u64)> {
+        let raw = std::mem::replace(&mut self.raw, ptr::null_mut());
+        collect_matches(Some(self.cap), |out, _room, count| unsafe { ffi::iris_pending_matches_wait(raw, out, count) })
+    }
+}
+
+impl Drop for PendingMatches {
+    fn drop(&mut self) {
+        if !self.raw.is_null() {
+            let mut count = 0u64;
+            unsafe {
+                ffi::iris_pending_matches_wait(self.raw, ptr::null_mut(), &mut count);
+            }
+        }
+    }
+}
+
 impl TemplateEngine {
     pub fn new(query: &Template) -> Self {
         Self::new_on(default_device(), query).unwrap_or_else(|e| panic!("TemplateEngine::new: {e}"))
@@ -556,6 +583,25 @@ impl TemplateEngine {
         collect_matches(cap, |out, room, count| unsafe {
             ffi::iris_template_matches(self.h.raw, db.raw(), first, n, index_base, threshold, out, room, count)
         })
+    }
+
+    /// Enqueues `matches` with `Some(cap)` and returns at once (iris_template_matches_async): a pass
+    /// still running may compute the next one submitted.  The engine may be dropped before the
+    /// wait; the database must outlive it, unmodified.
+    pub fn matches_async(
+        &self,
+        db: &Database,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        cap: u64,
+    ) -> Result<PendingMatches> {
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            ffi::iris_template_matches_async(self.h.raw, db.raw(), first, n, index_base, threshold, cap, &mut raw)
+        })?;
+        Ok(PendingMatches { raw, cap })
     }
 
     /// The k closest records of [first, first + n), best first, in one database pass

@@ -61,6 +61,8 @@ pub struct IrisEngine {
 pub struct IrisPending {
     _private: [u8; 0],
 }
+/// `iris_pending_matches_t`: the same opaque struct (each wait refuses the other's handles).
+pub type IrisPendingMatches = IrisPending;
 /// Device groups (`iris_group_t`, `iris_group_db_t`, `iris_group_pending_t`).
 #[repr(C)]
 pub struct IrisGroup {
@@ -399,6 +401,17 @@ extern "C" {
         cap: u64,
         count: *mut u64,
     ) -> c_int;
+    pub fn iris_template_matches_async(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        threshold: f64,
+        cap: u64,
+        out: *mut *mut IrisPending,
+    ) -> c_int;
+    pub fn iris_pending_matches_wait(pending: *mut IrisPending, out: *mut IrisMatch, count: *mut u64) -> c_int;
     pub fn iris_resolver_matches(
         dev: *mut IrisDevice,
         shares_device: *const *const u16,

@@ -86,6 +86,9 @@ typedef struct iris_device iris_device_t;
 typedef struct iris_db iris_db_t;
 typedef struct iris_engine iris_engine_t;
 typedef struct iris_pending iris_pending_t;
+/* The handle of iris_template_matches_async: the same opaque struct under a name of its own.  Each
+ * of the two waits refuses (IRIS_E_ARG) and leaves alone a handle the other submission made. */
+typedef iris_pending_t iris_pending_matches_t;
 
 /* ---------------------------------------------------------------- errors */
 const char *iris_last_error(void);
@@ -446,9 +449,10 @@ int iris_resolver_search_host(iris_device_t *dev, const uint16_t *const *shares,
  *
  * Out of scope: of the batch engines, the distance batch engine (its rows are shares, no
  * distances; the masks batch engine has iris_resolver_batch_matches_masks and the template batch
- * engine iris_template_batch_matches, both below); the host-array forms (*_host), the
- * asynchronous pipeline, and device groups (a variable-length exchange;
- * iris_group_template_batch_search's sibling included). */
+ * engine iris_template_batch_matches, both below); the host-array forms (*_host); device groups (a
+ * variable-length exchange; iris_group_template_batch_search's sibling included); and, of the
+ * asynchronous pipeline, every form but the single-query template one
+ * (iris_template_matches_async, below: no resolver, batch-engine or group form). */
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
  * index_base + first + i. */
 int iris_template_matches(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
@@ -522,6 +526,32 @@ int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint
                                 uint64_t index_base, double threshold,
                                 iris_match_t *out, uint64_t cap, uint64_t *counts);
 
+/* Pipelined form of iris_template_matches, as iris_template_search_async is of
+ * iris_template_search (no reference counterpart: the reference's calls block, src/lib.rs:42-53;
+ * the loops generalised are src/template.rs:43-47 + src/main.rs:616-621).  The submission
+ * enqueues the pass and returns at once; iris_pending_matches_wait blocks for THAT pass only,
+ * fills out (cap entries, the submission's cap; NULL only if cap == 0) and *count (required), and
+ * frees the handle whatever it returns (but a search's handle: see iris_pending_matches_t).
+ *
+ * Contract: out and *count are byte for byte what iris_template_matches(engine, db, first, n,
+ * index_base, threshold, out, cap, count) would have returned at the submission: the exact total
+ * even above cap, the min(*count, cap) matches of lowest index in ascending order, entries past
+ * them untouched, n == 0 gives 0.  A pass that is still streaming the database may compute the
+ * match pass submitted after it (same records of the same database, unwritten since; thresholds
+ * may differ); the result does not depend on it.  A search never computes a match pass, nor the
+ * reverse.
+ *
+ * Argument, engine-kind, range and NaN checks are iris_template_matches', made at the submission
+ * (out and count at the wait); a batch engine is refused.  The engine may be destroyed before the
+ * wait; the database must stay alive and unmodified until it.  Every pending holds device room
+ * for min(n, max(cap, 1024)) records until its wait; a list longer than that room (cap > 0 only)
+ * makes the wait run the pass once more, blocking. */
+int iris_template_matches_async(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                                uint64_t index_base, double threshold, uint64_t cap,
+                                iris_pending_t **out /* an iris_pending_matches_t */);
+int iris_pending_matches_wait(iris_pending_t *pending /* an iris_pending_matches_t */, iris_match_t *out,
+                              uint64_t *count);
+
 /* ------------------------------------------------------------------- top-k
  * The k closest records of a range, best first, in one database pass -- the ranked candidate
  * list of rank-k identification, a review queue or threshold calibration, with no threshold
@@ -554,7 +584,8 @@ int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint
  *
  * Out of scope: of the batch engines, the distance batch engine (its rows are shares, no
  * distances; the masks batch engine has iris_resolver_batch_topk_masks and the template batch
- * engine iris_template_batch_topk); the host-array forms (*_host), the asynchronous pipeline,
+ * engine iris_template_batch_topk); the host-array forms (*_host), the asynchronous pipeline
+ * (threshold matching alone has one, iris_template_matches_async),
  * device groups (iris_topk_merge below is the hand-sharding answer) and k > 64. */
 #define IRIS_TOPK_MAX 64
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are

@@ -693,6 +693,34 @@ private:
     iris_pending_t *p_;
 };
 
+// An enqueued threshold-match pass (TemplateEngine::matches_async): wait() once for what
+// matches() with the same arguments returns; destroying it unwaited waits and discards the result.
+class PendingMatches {
+public:
+    PendingMatches(iris_pending_matches_t *p, uint64_t cap) : p_(p), cap_(cap) {}
+    PendingMatches(PendingMatches &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; }
+    PendingMatches(const PendingMatches &) = delete;
+    PendingMatches &operator=(const PendingMatches &) = delete;
+    ~PendingMatches() {
+        uint64_t count = 0;
+        if (p_) (void)iris_pending_matches_wait(p_, nullptr, &count);
+    }
+    Matches wait() {
+        if (!p_) throw Error(IRIS_E_ARG, "PendingMatches::wait called twice");
+        Matches m;
+        m.list.resize(cap_);
+        iris_pending_matches_t *p = p_;
+        p_ = nullptr;
+        check(iris_pending_matches_wait(p, cap_ ? m.list.data() : nullptr, &m.count));
+        m.list.resize(std::min<uint64_t>(cap_, m.count));
+        return m;
+    }
+
+private:
+    iris_pending_matches_t *p_;
+    uint64_t cap_;
+};
+
 // Template vs Template database (src/template.rs:43-64) with the resolver's argmin.
 class TemplateEngine : public detail::Engine {
 public:
@@ -724,6 +752,15 @@ public:
         iris_pending_t *p = nullptr;
         check(iris_template_search_async(h_, db.handle(), first, n, index_base, &p));
         return PendingSearch(p);
+    }
+    // pipelined form of matches() with an explicit cap (the list holds the min(count, cap) lowest
+    // indices, count is the total): returns once the pass is enqueued; a pass still running may
+    // compute the next one submitted (iris_template_matches_async)
+    PendingMatches matches_async(const Database &db, double threshold, uint64_t first, uint64_t n, uint64_t index_base,
+                                 uint64_t cap) const {
+        iris_pending_matches_t *p = nullptr;
+        check(iris_template_matches_async(h_, db.handle(), first, n, index_base, threshold, cap, &p));
+        return PendingMatches(p, cap);
     }
     std::vector<double> distances(const Database &db, uint64_t first, uint64_t n) const {
         std::vector<double> out(n);

@@ -192,6 +192,8 @@ void device_teardown(iris_device *d) {
                           &d->matches, &d->match_count, &d->match_sinks})
             if (b->p) (void)hipFree(b->p);
         side_sync(d);
+        for (MatchBufs &m : d->match_free)
+            if (m.dev.p) (void)hipFree(m.dev.p);
         for (int b = 0; b < 2; ++b) {
             if (d->apart[b].p) (void)hipFree(d->apart[b].p);
             if (d->apart_read[b]) (void)hipEventDestroy(d->apart_read[b]);
@@ -389,16 +391,18 @@ int iris_device_kernel_stats(iris_device_t *d, const char *kernel, uint64_t *lau
     IRIS_KEEP_DEVICE();
     ARG(d && kernel, "NULL argument");
     std::lock_guard<std::recursive_mutex> g(d->mu);
-    if (!strcmp(kernel, "search_shared")) {
-        // shared passes: launches = searches registered as guests, items = tile groups carried for
-        // them (a device counter, read behind whatever the device stream holds); no time of its own
+    const int shared = !strcmp(kernel, "search_shared") ? 0 : !strcmp(kernel, "match_shared") ? 1 : -1;
+    if (shared >= 0) {
+        // shared passes: launches = searches (match passes) registered as guests, items = tile groups
+        // carried for them (a device counter, read behind whatever the device stream holds); no time
+        // of its own
         unsigned long long carried = 0;
         if (d->share_count) {
             CHK(set_device(d));
-            HIPCHK(hipMemcpyAsync(&carried, d->share_count, sizeof(carried), hipMemcpyDeviceToHost, d->stream));
+            HIPCHK(hipMemcpyAsync(&carried, d->share_count + shared, sizeof(carried), hipMemcpyDeviceToHost, d->stream));
             HIPCHK(hipStreamSynchronize(d->stream));
         }
-        if (launches) *launches = d->share_regs;
+        if (launches) *launches = d->share_regs[shared];
         if (total_ms) *total_ms = 0;
         if (items) *items = carried;
         return 0;
@@ -429,10 +433,10 @@ int iris_device_reset_stats(iris_device_t *d) {
     std::lock_guard<std::recursive_mutex> g(d->mu);
     d->stats.clear();
     d->ra_launches = d->ra_records = d->ra_window_max = 0;
-    d->share_regs = 0;
+    d->share_regs[0] = d->share_regs[1] = 0;
     if (d->share_count) {
         CHK(set_device(d));
-        HIPCHK(hipMemsetAsync(d->share_count, 0, sizeof(*d->share_count), d->stream));
+        HIPCHK(hipMemsetAsync(d->share_count, 0, 2 * sizeof(*d->share_count), d->stream));
     }
     return 0;
 }

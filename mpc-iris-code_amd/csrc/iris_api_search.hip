@@ -68,6 +68,66 @@ int share_take(iris_device *d, uint32_t np, SharePass **out) {
 
 }  // namespace
 
+int iris_api::share_join(iris_device *d, int share_host, const iris_db *db, uint64_t first, uint64_t n, uint32_t np,
+                         const iris_template_t *query, hipEvent_t after, Partial *partials, const MatchSink *sink,
+                         ShareJoin *out) {
+    *out = ShareJoin{};
+    SharePass *sp = nullptr;
+    if (d->hooks.search_share) CHK(share_take(d, np, &sp));
+    if (!sp) return 0;
+    const bool match = sink != nullptr;
+    sp->db = db;
+    sp->writes = db->writes;
+    sp->first = first;
+    sp->n = n;
+    sp->match = match;
+    // the pass before this one hosts it if it came from the same entry point and covers the same
+    // records of the same database, unwritten since, has no guest yet and has not ended
+    SharePass *host = share_host >= 0 ? &d->share_ring[share_host] : nullptr;
+    const bool guest = host && host != sp && host->guest < 0 && host->match == match && host->db == db &&
+                       host->writes == db->writes && host->first == first && host->n == n &&
+                       hipEventQuery(host->ended) == hipErrorNotReady;
+    // on the sharing stream: behind `after` (a search: the reduce that last read its partials
+    // buffer), the slot (and done words) zeroed -- and a match pass's counter: on the device stream,
+    // ahead of the pass's own launch, the zeroing would land after the hosting pass and wipe what it
+    // counted for this one -- then, for a guest, its fragments built from the host copy of the query
+    // (the engine's own buffer is built in device-stream order, behind the running pass) and the slot
+    // of the hosting pass published
+    if (after) HIPCHK(hipStreamWaitEvent(d->share, after, 0));
+    if (launch_share_prepare(d->share, sp->slot, guest ? (uint32_t *)sp->done.p : nullptr, np) != 0)
+        return fail(IRIS_E_HIP, "kernel launch failed: share_prepare");
+    if (match) HIPCHK(hipMemsetAsync(sink->count, 0, sizeof(uint64_t), d->share));
+    if (guest) {
+        uint32_t *tab = (uint32_t *)sp->qbuf;
+        uint32_t *frag = (uint32_t *)((char *)sp->qbuf + qalign(kTemplateTabBytes));
+        if (launch_query_template(d->share, query, tab, frag) != 0 ||
+            (match ? launch_share_publish_match(d->share, host->slot, frag, *sink, (uint32_t *)sp->done.p)
+                   : launch_share_publish(d->share, host->slot, frag, partials, (uint32_t *)sp->done.p)) != 0)
+            return fail(IRIS_E_HIP, "kernel launch failed: share_publish");
+        host->guest = (int)(sp - d->share_ring);
+        d->share_regs[match] += 1;
+    }
+    HIPCHK(hipEventRecord(d->share_reg, d->share));
+    HIPCHK(hipStreamWaitEvent(d->stream, d->share_reg, 0));
+    if (d->hooks.search_share_delay_us) {  // test hook: the next registration lands before this pass starts
+        int khz = 0;
+        HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d->ordinal));
+        if (launch_share_delay(d->stream, (uint64_t)d->hooks.search_share_delay_us * khz / 1000) != 0)
+            return fail(IRIS_E_HIP, "kernel launch failed: share_delay");
+    }
+    out->sp = sp;
+    out->own_done = guest ? (const uint32_t *)sp->done.p : nullptr;
+    out->count = d->share_count + match;
+    return 0;
+}
+
+int iris_api::share_launched(iris_device *d, const ShareJoin &j) {
+    if (!j.sp) return 0;
+    HIPCHK(hipEventRecord(j.sp->ended, d->stream));
+    d->share_last = (int)(j.sp - d->share_ring);
+    return 0;
+}
+
 // Enqueues the search of [first, first+n) and its reduce, whose winner lands in
 // `dst` (pinned host memory); nothing waits.  side = true (asynchronous
 // searches): the reduce runs on the side stream over one of two alternating
@@ -127,53 +187,13 @@ int iris_api::search_enqueue(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     const bool share_form = share && side && layout == IRIS_LAYOUT_TILES && !dist_dev && e->host_query &&
                             share_search_ok(d->hooks, r);
     if (share_form) {
-        SharePass *sp = nullptr;
-        if (d->hooks.search_share) CHK(share_take(d, np, &sp));
-        bool guest = false;
-        if (sp) {
-            sp->db = db;
-            sp->writes = db->writes;
-            sp->first = first;
-            sp->n = n;
-            // the pass before this one hosts it if it searches the same records of the same
-            // database, unwritten since, has no guest yet and has not ended
-            SharePass *host = share_host >= 0 ? &d->share_ring[share_host] : nullptr;
-            guest = host && host != sp && host->guest < 0 && host->db == db && host->writes == db->writes &&
-                    host->first == first && host->n == n && hipEventQuery(host->ended) == hipErrorNotReady;
-            // on the sharing stream: behind the reduce that last read this search's partials buffer,
-            // the slot (and done words) zeroed, then, for a guest, its fragments built from the
-            // engine's host copy of the query (the engine's own buffer is built in device-stream
-            // order, behind the running pass) and the slot of the hosting pass published
-            HIPCHK(hipStreamWaitEvent(d->share, d->apart_read[b], 0));
-            if (launch_share_prepare(d->share, sp->slot, guest ? (uint32_t *)sp->done.p : nullptr, np) != 0)
-                return fail(IRIS_E_HIP, "kernel launch failed: share_prepare");
-            if (guest) {
-                uint32_t *tab = (uint32_t *)sp->qbuf;
-                uint32_t *frag = (uint32_t *)((char *)sp->qbuf + qalign(kTemplateTabBytes));
-                if (launch_query_template(d->share, e->host_query, tab, frag) != 0 ||
-                    launch_share_publish(d->share, host->slot, frag, part, (uint32_t *)sp->done.p) != 0)
-                    return fail(IRIS_E_HIP, "kernel launch failed: share_publish");
-                host->guest = (int)(sp - d->share_ring);
-                d->share_regs += 1;
-            }
-            HIPCHK(hipEventRecord(d->share_reg, d->share));
-            HIPCHK(hipStreamWaitEvent(d->stream, d->share_reg, 0));
-            if (d->hooks.search_share_delay_us) {  // test hook: the next registration lands before this pass starts
-                int khz = 0;
-                HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d->ordinal));
-                if (launch_share_delay(d->stream, (uint64_t)d->hooks.search_share_delay_us * khz / 1000) != 0)
-                    return fail(IRIS_E_HIP, "kernel launch failed: share_delay");
-            }
-        }
+        ShareJoin j;
+        CHK(share_join(d, share_host, db, first, n, np, e->host_query, d->apart_read[b], part, nullptr, &j));
         CHK(timed(d, "template_search", n, [&] {
             return launch_template_share_search(d->hooks, d->stream, db->data, e->qfrag, r, part, &written,
-                                                sp ? sp->slot : nullptr, guest ? (const uint32_t *)sp->done.p : nullptr,
-                                                sp ? d->share_count : nullptr);
+                                                j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
         }));
-        if (sp) {
-            HIPCHK(hipEventRecord(sp->ended, d->stream));
-            d->share_last = (int)(sp - d->share_ring);
-        }
+        CHK(share_launched(d, j));
     } else {
         CHK(timed(d, "template_search", n, [&] {
             if (layout == IRIS_LAYOUT_TILES)
@@ -295,13 +315,6 @@ int iris_template_search(iris_engine_t *e, const iris_db_t *db, uint64_t first, 
     return search_locked(e, db, first, n, index_base, dist_out_device, out);
 }
 
-struct iris_pending {
-    iris_device *dev = nullptr;
-    hipEvent_t ev = nullptr;    // recorded after the reduce (null for an empty range)
-    Partial *slot = nullptr;    // pinned host slot the reduce writes
-    uint64_t n = 0, base = 0;   // range size; index_base + first
-};
-
 int iris_template_search_async(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
                                uint64_t index_base, iris_pending_t **out) {
     IRIS_KEEP_DEVICE();
@@ -336,6 +349,7 @@ int iris_template_search_async(iris_engine_t *e, const iris_db_t *db, uint64_t f
 int iris_pending_wait(iris_pending_t *p, iris_match_t *out) {
     IRIS_KEEP_DEVICE();
     ARG(p, "pending is NULL");
+    ARG(!p->matches, "pending of iris_template_matches_async: iris_pending_matches_wait waits for it");
     iris_device *d = p->dev;
     hipError_t err = hipSuccess;
     if (p->ev) err = hipEventSynchronize(p->ev);  // this search only: later enqueued work keeps running

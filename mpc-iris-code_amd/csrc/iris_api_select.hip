@@ -1,6 +1,6 @@
 // iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
-// and batched, with the runners that turn launch units into match lists.  Calls, locking and
-// errors: see iris_api.hip.
+// and batched, with the runners that turn launch units into match lists, and the pipelined form of
+// the single-query template match.  Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
 #include <new>
@@ -109,10 +109,7 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
         }
         HIPCHK(hipMemcpyAsync(recs.data(), src, total[q] * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
         CHK(sync(d));
-        const auto by_index = [](const Partial &a, const Partial &b) { return a.idx < b.idx; };
-        if (take < total[q]) std::nth_element(recs.begin(), recs.begin() + take, recs.end(), by_index);
-        std::sort(recs.begin(), recs.begin() + take, by_index);
-        for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[q * cap + i]);
+        match_list(recs.data(), total[q], take, base, out + q * cap);
         return 0;
     };
     auto overflows = [&](const MatchUnit &u) {
@@ -169,6 +166,215 @@ int iris_template_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first,
                    ? launch_template_mfma_match(d->hooks, d->stream, db->data, e->qfrag, r, ms)
                    : launch_template_match(d->stream, db->data, e->qtab, r, ms);
     });
+}
+
+// ------------------------------------------------------------------ pipelined threshold matching
+
+// iris_template_matches_async .. iris_pending_matches_wait.  The pass appends
+// into buffers of the pending's own; behind it, on the side stream, the counter and the first
+// kMatchInline records go to the pending's pinned slot, and `ev` is recorded there.
+struct iris_pending_matches : iris_pending {  // dev, ev (null for an empty range), n, base: as the search's
+    const iris_db *db = nullptr;  // the caller keeps it alive and unmodified until the wait
+    MatchBufs bufs;
+    uint64_t first = 0, cap = 0, room = 0;
+    double threshold = 0;
+    iris_template_t query;  // an overflowing list runs the pass again after the engine may be gone
+};
+
+static uint64_t *match_counter(const MatchBufs &b) { return (uint64_t *)b.dev.p; }
+static Partial *match_records(const MatchBufs &b) { return (Partial *)((char *)b.dev.p + kMatchRecOff); }
+
+// buffers for a pending with room for `room` records (caller holds the device lock)
+static int match_bufs_take(iris_device *d, uint64_t room, MatchBufs *out) {
+    if (d->match_free.empty()) {  // pinned slots in blocks, as take_result_slot's; device buffers on first use
+        constexpr int kSlots = 64;
+        void *blk = nullptr;
+        hipError_t e = hipHostMalloc(&blk, kSlots * kMatchSlotBytes, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(IRIS_E_NOMEM, std::string("hipHostMalloc match slots: ") + hipGetErrorString(e));
+        d->slot_blocks.push_back(blk);
+        for (int i = kSlots - 1; i >= 0; --i)
+            d->match_free.push_back(MatchBufs{DevBuf{}, (char *)blk + (size_t)i * kMatchSlotBytes});
+    }
+    MatchBufs b = d->match_free.back();  // the one returned last: a steady pipeline keeps to a few
+    d->match_free.pop_back();
+    const int rc = ensure(d, b.dev, kMatchRecOff + room * sizeof(Partial));
+    if (rc != 0) {
+        d->match_free.push_back(b);
+        return rc;
+    }
+    *out = b;
+    return 0;
+}
+
+// The pass of a pending over its range into its buffers, on the device stream; shared: it may take
+// a place in the sharing ring (the submission; the rerun of an overflowing list never does).
+static int match_pass_enqueue(iris_device *d, const iris_pending_matches *p, const void *qtab, const void *qfrag,
+                              bool shared) {
+    const LaunchRange r{p->first, p->n};
+    const MatchSink ms{match_records(p->bufs), p->room, match_counter(p->bufs), p->threshold};
+    const bool tiles = p->db->k.layout == IRIS_LAYOUT_TILES;
+    if (shared && tiles && share_search_ok(d->hooks, r)) {
+        // the sharing form (§4.1): the range the asynchronous search shares on, the hooks included
+        ShareJoin j;
+        CHK(share_join(d, d->share_last, p->db, p->first, p->n, mfma_search_partials(d->hooks, r), &p->query, nullptr,
+                       nullptr, &ms, &j));
+        d->share_last = -1;
+        if (!j.sp) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
+        CHK(timed(d, "template_match", p->n, [&] {
+            return launch_template_share_match(d->hooks, d->stream, p->db->data, qfrag, r, ms, j.sp ? j.sp->slot : nullptr,
+                                               j.own_done, j.count);
+        }));
+        return share_launched(d, j);
+    }
+    d->share_last = -1;  // only the device's latest pass can host
+    HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
+    return timed(d, "template_match", p->n, [&] {
+        return tiles ? launch_template_mfma_match(d->hooks, d->stream, p->db->data, qfrag, r, ms)
+                     : launch_template_match(d->stream, p->db->data, qtab, r, ms);
+    });
+}
+
+int iris_template_matches_async(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                                double threshold, uint64_t cap, iris_pending_t **out) {
+    IRIS_KEEP_DEVICE();
+    ARG(threshold == threshold, "threshold is NaN");  // the value arguments first, as iris_template_matches
+    ARG(out, "out is NULL");
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (!e->host_query) return fail(IRIS_E_ARG, "engine keeps no host copy of its query");
+    iris_pending_matches *p = new (std::nothrow) iris_pending_matches();
+    if (!p) return fail(IRIS_E_NOMEM, "out of host memory");
+    p->matches = true;
+    p->dev = d;
+    p->db = db;
+    p->first = first;
+    p->n = n;
+    p->base = index_base + first;
+    p->cap = cap;
+    p->threshold = threshold;
+    p->query = *e->host_query;
+    if (n == 0) {
+        device_retain(d);
+        *out = p;
+        return 0;
+    }
+    p->room = std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom));
+    int rc = match_bufs_take(d, p->room, &p->bufs);
+    bool taken = rc == 0;
+    if (rc == 0) {
+        p->ev = take_event(d);
+        if (!p->ev) rc = fail(IRIS_E_HIP, "hipEventCreate failed");
+    }
+    if (rc == 0) rc = ensure_aux(d);
+    if (rc == 0) rc = match_pass_enqueue(d, p, e->qtab, e->qfrag, true);
+    if (rc == 0) {
+        // behind the pass, on the side stream (the next pass is not held up): the counter and the
+        // first records to the pinned slot, then the pending's event
+        hipError_t err = hipEventRecord(p->ev, d->stream);
+        if (err == hipSuccess) err = hipStreamWaitEvent(d->aux, p->ev, 0);
+        const size_t bytes = kMatchRecOff + std::min<uint64_t>(p->room, kMatchInline) * sizeof(Partial);
+        if (err == hipSuccess) err = hipMemcpyAsync(p->bufs.host, p->bufs.dev.p, bytes, hipMemcpyDeviceToHost, d->aux);
+        if (err == hipSuccess) err = hipEventRecord(p->ev, d->aux);
+        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("enqueue match copy: ") + hipGetErrorString(err));
+    }
+    if (rc != 0) {
+        if (taken) {
+            (void)hipStreamSynchronize(d->stream);  // whatever was enqueued no longer writes the buffers
+            side_sync(d);
+            d->match_free.push_back(p->bufs);
+        }
+        if (p->ev) d->event_pool.push_back(p->ev);
+        delete p;
+        return rc;
+    }
+    device_retain(d);
+    *out = p;
+    return 0;
+}
+
+// The list of a pending whose pass has ended (caller holds the device lock): `total` is the
+// counter's value.
+static int pending_matches_finish(iris_pending_matches *p, uint64_t total, iris_match_t *out) {
+    iris_device *d = p->dev;
+    const uint64_t take = std::min(total, p->cap);
+    if (take == 0) return 0;
+    std::vector<Partial> recs;
+    try {
+        recs.resize(total);
+    } catch (const std::bad_alloc &) {
+        return fail(IRIS_E_NOMEM, "out of host memory");
+    }
+    if (total <= std::min<uint64_t>(p->room, kMatchInline)) {
+        memcpy(recs.data(), (const char *)p->bufs.host + kMatchRecOff, total * sizeof(Partial));
+    } else {
+        CHK(set_device(d));
+        if (total > p->room) {
+            // the list did not fit: the pass once more, blocking and unshared, the buffer grown to
+            // exactly the reported count and the query's tables built again from the host copy
+            void *q = nullptr;
+            CHK(dev_malloc(d, &q, qalign(kTemplateTabBytes) + kTemplateFragDwords * 4, "match rerun query"));
+            uint32_t *tab = (uint32_t *)q, *frag = (uint32_t *)((char *)q + qalign(kTemplateTabBytes));
+            p->room = total;
+            int rc = ensure(d, p->bufs.dev, kMatchRecOff + total * sizeof(Partial));
+            if (rc == 0 && launch_query_template(d->stream, &p->query, tab, frag) != 0)
+                rc = fail(IRIS_E_HIP, "kernel launch failed: query tables");
+            if (rc == 0) rc = match_pass_enqueue(d, p, tab, frag, false);
+            uint64_t again = 0;
+            if (rc == 0 && hipMemcpyAsync(&again, match_counter(p->bufs), sizeof(again), hipMemcpyDeviceToHost, d->stream) !=
+                               hipSuccess)
+                rc = fail(IRIS_E_HIP, "hipMemcpyAsync failed");
+            const int rs = sync(d);
+            (void)hipFree(q);
+            CHK(rc);
+            CHK(rs);
+            if (again != total) return fail(IRIS_E_HIP, "match pass counts differ between two runs");
+        }
+        // the rest on the second side stream, which carries nothing of a template pipeline: the
+        // device stream and the first side stream may hold the passes submitted since
+        HIPCHK(hipMemcpyAsync(recs.data(), match_records(p->bufs), total * sizeof(Partial), hipMemcpyDeviceToHost, d->aux2));
+        HIPCHK(hipStreamSynchronize(d->aux2));
+    }
+    match_list(recs.data(), total, take, p->base, out);
+    return 0;
+}
+
+int iris_pending_matches_wait(iris_pending_t *pending, iris_match_t *out, uint64_t *count) {
+    IRIS_KEEP_DEVICE();
+    ARG(pending, "pending is NULL");
+    ARG(pending->matches, "pending of iris_template_search_async: iris_pending_wait waits for it");
+    iris_pending_matches *p = static_cast<iris_pending_matches *>(pending);
+    iris_device *d = p->dev;
+    int rc = 0;
+    if (!count) rc = fail(IRIS_E_ARG, "count is NULL");
+    else if (p->cap && !out) rc = fail(IRIS_E_ARG, "out is NULL with cap > 0");
+    hipError_t err = hipSuccess;
+    if (p->ev) err = hipEventSynchronize(p->ev);  // this pass and its copy only: later enqueued work keeps running
+    {
+        std::lock_guard<std::recursive_mutex> g(d->mu);
+        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(err));
+        if (rc == 0) {
+            uint64_t total = 0;
+            if (p->n > 0) memcpy(&total, p->bufs.host, sizeof(total));
+            if (total > p->n) rc = fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+            if (rc == 0) rc = pending_matches_finish(p, total, out);
+            if (rc == 0) *count = total;
+        }
+        if (p->n > 0) {
+            if (err != hipSuccess) {  // nothing may still write buffers that go back to the list
+                (void)hipStreamSynchronize(d->stream);
+                side_sync(d);
+            }
+            d->match_free.push_back(p->bufs);
+        }
+        if (p->ev) d->event_pool.push_back(p->ev);
+        fold_done(d);
+    }
+    delete p;
+    device_release(d);
+    return rc;
 }
 
 // iris_resolver_search's threshold sibling

@@ -226,7 +226,10 @@ __device__ __forceinline__ Partial partial_none() {
 // Threshold matching (MatchSink, iris_internal.hpp).  The decision is the f64 comparison the
 // caller would make on the search's own distance: one IEEE division per record, den = 0
 // (distance +inf) never matches, not even under threshold = +inf.
-__device__ __forceinline__ bool match_hit(const MatchSink &m, bool valid, uint32_t num, uint32_t den) {
+// Sink: MatchSink, or a struct of the same fields whose pointers are global by type (GuestSink,
+// iris_mfma.hip).
+template <class Sink>
+__device__ __forceinline__ bool match_hit(const Sink &m, bool valid, uint32_t num, uint32_t den) {
     return valid && den != 0 && (double)num / (double)den < m.threshold;
 }
 
@@ -235,8 +238,8 @@ __device__ __forceinline__ bool match_hit(const MatchSink &m, bool valid, uint32
 // agent-scope relaxed atomic add (none when the wave has no hit), and each hit whose slot lies
 // inside the buffer stores its record.  Slot order depends on which wave adds first; the host
 // sorts by index.
-template <int T>
-__device__ __forceinline__ void append_matches(const MatchSink &m, int lane, const bool (&hit)[T],
+template <int T, class Sink>
+__device__ __forceinline__ void append_matches(const Sink &m, int lane, const bool (&hit)[T],
                                                const uint32_t (&num)[T], const uint32_t (&den)[T], const int (&rot)[T],
                                                const uint64_t (&idx)[T]) {
     uint64_t mask[T];
@@ -256,13 +259,12 @@ __device__ __forceinline__ void append_matches(const MatchSink &m, int lane, con
     for (int t = 0; t < T; ++t) {
         const uint64_t slot = base + (uint64_t)__popcll(mask[t] & below);
         if (hit[t] && slot < m.cap) {
-            Partial p;
-            p.num = num[t];
-            p.den = den[t];
-            p.rot = rot[t];
-            p.pad = 0;
-            p.idx = idx[t];
-            m.buf[slot] = p;
+            auto *const p = m.buf + slot;  // field by field: a record in a typed address space has no operator=
+            p->num = num[t];
+            p->den = den[t];
+            p->rot = rot[t];
+            p->pad = 0;
+            p->idx = idx[t];
         }
         base += (uint64_t)__popcll(mask[t]);
     }

@@ -106,6 +106,20 @@ struct SharePass {
     int guest = -1;                   // ring index of the pass registered as this one's guest
     const struct iris_db *db = nullptr;  // what the pass searches: a guest must ask for the same
     uint64_t writes = 0, first = 0, n = 0;
+    bool match = false;  // a match pass (iris_template_matches_async): it hosts match passes only, a search searches only
+};
+
+// What one pending iris_template_matches_async owns from submission to wait (a per-device free
+// list: the blocking calls' one buffer and one counter cannot serve outstanding passes).  dev holds
+// the 8-byte counter, then from kMatchRecOff the records; host is a pinned slot of kMatchSlotBytes
+// that takes the counter and the first kMatchInline records behind the pass.
+constexpr size_t kMatchRecOff = 8;
+constexpr uint64_t kMatchInline = 16;  // the usual list is empty or a handful
+constexpr size_t kMatchSlotBytes = 512;
+static_assert(kMatchRecOff + kMatchInline * sizeof(iris::Partial) <= kMatchSlotBytes, "inline copy fits the slot");
+struct MatchBufs {
+    DevBuf dev;
+    void *host = nullptr;
 };
 
 struct iris_device {
@@ -126,6 +140,8 @@ struct iris_device {
     // the MatchSinks of a template batch match pass, one per padded query (the GEMM reads them
     // from memory: up to 1024 and more do not travel as kernel arguments)
     DevBuf match_sinks;
+    // asynchronous threshold matching: buffers no pending holds (the pinned slots come out of slot_blocks)
+    std::vector<MatchBufs> match_free;
     // zeroed device word of the fused (last-workgroup) search reduce; searches on the stream
     // are serialised, and each launch leaves it zeroed
     DevBuf ticket;
@@ -153,13 +169,14 @@ struct iris_device {
     // shared passes: the ring, the latest pass that may still take a guest (-1: none), the stream
     // registrations run on (the side stream waits behind the running pass, so it cannot carry them),
     // the event that orders a pass behind its registration, and the device counter of tile groups
-    // carried for guests (kernel stats "search_shared", with the registrations as its launches)
+    // carried for guests (kernel stats "search_shared", with the registrations as its launches;
+    // word and entry [1]: the match passes', "match_shared")
     SharePass share_ring[kShareRing];
     int share_next = 0, share_last = -1;
     hipStream_t share = nullptr;
     hipEvent_t share_reg = nullptr;
     unsigned long long *share_count = nullptr;
-    uint64_t share_regs = 0;
+    uint64_t share_regs[2] = {0, 0};
     // handles alive on this device (1 for the device handle itself + 1 per database
     // and engine handle): the device is torn down when the last one is released,
     // so handles may be destroyed in any order
@@ -251,6 +268,16 @@ struct Readahead {
     const struct iris_db *last_db = nullptr;
     uint64_t last_version = 0, last_end = 0;
     uint64_t grow = 0;  // records of the walk's latest window (the next one is twice its chunks)
+};
+
+// iris_template_search_async .. iris_pending_wait; iris_template_matches_async's handle extends it
+// (iris_pending_matches, iris_api_select.hip), and `matches` tells each wait which one it was given
+struct iris_pending {
+    bool matches = false;
+    iris_device *dev = nullptr;
+    hipEvent_t ev = nullptr;          // recorded after the reduce (null for an empty range)
+    iris::Partial *slot = nullptr;    // pinned host slot the reduce writes
+    uint64_t n = 0, base = 0;         // range size; index_base + first
 };
 
 struct iris_engine {
@@ -514,6 +541,23 @@ int template_engine_locked(iris_device *d, const iris_template_t *query, iris_en
 int search_enqueue(iris_engine *e, const iris_db *db, uint64_t first, uint64_t n, double *dist_dev, iris::Partial *dst,
                    bool side = false, hipEvent_t done = nullptr, uint64_t idx_base = 0, uint32_t *host_done = nullptr,
                    uint32_t seq = 0, bool *flagged = nullptr, bool share = false);
+// A sharing pass's place in the ring (iris_api_search.hip).  share_join, ahead
+// of the pass's launch: takes a ring entry (sp = nullptr: none free, or sharing is off -- the pass
+// neither hosts nor is hosted), registers the pass as guest of `share_host` (the device's
+// share_last as the call found it) if that pass can host it, and orders the device stream behind
+// the registration.  query: the host copy the guest's fragments are built from; after: an event the
+// sharing stream waits for first (or null).  A search gives its partials buffer, a match pass its
+// sink (whose counter is zeroed here, on the sharing stream).  The kernel takes sp->slot, own_done
+// and count; share_launched, behind the launch, makes the pass the one that can host next.
+struct ShareJoin {
+    SharePass *sp = nullptr;
+    const uint32_t *own_done = nullptr;  // a guest's done words
+    unsigned long long *count = nullptr;  // the device counter of tile groups carried
+};
+int share_join(iris_device *d, int share_host, const iris_db *db, uint64_t first, uint64_t n, uint32_t np,
+               const iris_template_t *query, hipEvent_t after, iris::Partial *partials, const iris::MatchSink *sink,
+               ShareJoin *out);
+int share_launched(iris_device *d, const ShareJoin &j);
 // Fills dst with the source bytes [off, off + bytes) of a write; false on a read error (errno set).
 using SlotFill = std::function<bool(void *dst, size_t off, size_t bytes)>;
 // Stores host records [0, n) at database index `index` through two pinned 64-MB slots the helper
@@ -569,6 +613,15 @@ inline void match_from(const iris::Partial &r, bool any, uint64_t base, iris_mat
         out->rotation = r.rot - IRIS_MAX_ROTATION;
     }
     out->reserved = 0;
+}
+
+// A match pass's `total` records at recs (in append order, which depends on which wave added
+// first) -> the `take` lowest indices, ascending, as match_from fills them (idx + base).
+inline void match_list(iris::Partial *recs, uint64_t total, uint64_t take, uint64_t base, iris_match_t *out) {
+    const auto by_index = [](const iris::Partial &a, const iris::Partial &b) { return a.idx < b.idx; };
+    if (take < total) std::nth_element(recs, recs + take, recs + total, by_index);
+    std::sort(recs, recs + take, by_index);
+    for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[i]);
 }
 
 // Argument checks that entry points of several files share (each defined in the file named); a

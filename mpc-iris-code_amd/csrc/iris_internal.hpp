@@ -210,7 +210,7 @@ struct Hooks {
     uint32_t resident_budget_mb = 0; // IRIS_RESIDENT_BUDGET_MB: resident copies hold at most this (0: free memory)
     bool ra_packed = true;           // IRIS_READAHEAD_PACKED=0: masks read-ahead rows cross the host link unpacked
     uint32_t ra_window_max = 0;      // IRIS_READAHEAD_WINDOW_MAX=1..1024: cap of a read-ahead window, chunks (0: by records)
-    bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches never register as guests
+    bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches and match passes never register as guests
     uint32_t search_share_delay_us = 0;  // IRIS_SEARCH_SHARE_DELAY_US: device-stream spin ahead of a pass that can host
     bool search_share_even = false;  // IRIS_SEARCH_SHARE_EVEN=1: a pass that is nobody's guest sees no guest in odd tile groups
     uint32_t ignored = 0;            // bit i: test hook kHookNames[i] was set without IRIS_TEST_HOOKS=1
@@ -283,8 +283,9 @@ struct GuestSlot {
     uint32_t ready;
     uint32_t pad;
     const void *frag;   // the guest's query fragments (a buffer of the sharing ring, not the engine's)
-    Partial *partials;  // the guest's partials buffer
+    Partial *partials;  // the guest's partials buffer (a search)
     uint32_t *done;     // the guest's done array, one word per workgroup
+    MatchSink sink;     // the guest's sink (a match pass: its counter is zeroed ahead of the publish)
 };
 // whether a range runs the form that can share: 4 tiles per wave, no K-split, separate reduce
 bool share_search_ok(const Hooks &h, LaunchRange r);
@@ -294,6 +295,13 @@ bool share_search_ok(const Hooks &h, LaunchRange r);
 int launch_template_share_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
                                  Partial *partials, uint32_t *n_partials, const GuestSlot *slot,
                                  const uint32_t *own_done, unsigned long long *count);
+// The sharing form of iris_template_matches_async (the same ranges, slot, own_done and count): every
+// tile group's hits are appended to ms, the guest's to its slot's sink.  A match pass hosts match
+// passes only, a search searches only: the caller keeps them apart.
+int launch_template_share_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                                const MatchSink &ms, const GuestSlot *slot, const uint32_t *own_done,
+                                unsigned long long *count);
+int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done);
 // zeroes a pass's guest slot and, if given, its done array of n words
 int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n);
 int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done);

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "iris_device.hpp"
 
 namespace iris {
@@ -434,8 +436,8 @@ __global__ void __launch_bounds__(256, 2)
 // ------------------------------------------------------------------ shared passes
 
 // One round of a sharing pass: NQ queries against the T tiles from tw (relative to tile0), the
-// streaming loop and epilogue of template_mfma_kernel<MF_SEARCH> (NQ = 1, T = 4) and of
-// template_multi_kernel<2> (NQ = 2, T = 2); the round's candidates are folded into best[].
+// streaming loop of template_mfma_kernel (NQ = 1, T = 4) and of template_multi_kernel<2> (NQ = 2,
+// T = 2); the round's sums go to epi(den, s): round_candidates (search) or round_matches (match).
 // Query fragments as pointers into global memory by type: the guest's pointer comes out of LDS, and
 // as a generic pointer its loads would be flat ones, behind which every wait drains the whole
 // load queue -- the prefetch ring of both paths would collapse.
@@ -474,10 +476,45 @@ __device__ __forceinline__ void round_candidates(const v16f (&den)[NQ][T], const
     }
 }
 
+// The match form's epilogue of a round: every record of the T tiles from tw whose best rotation
+// lies below query qi's threshold is appended to sink[qi] (half 0 of the wave votes, as in
+// template_mfma_kernel<MF_MATCH>).  The sinks' pointers are global by type, as the fragments: a
+// flat store or atomic would make every wait of the next round's loop a full drain.
+typedef __attribute__((address_space(1))) Partial *GlobalPartial;
+struct GlobalSink {
+    GlobalPartial buf;
+    uint64_t cap;
+    __attribute__((address_space(1))) uint64_t *count;
+    double threshold;
+};
 template <int NQ, int T>
+__device__ __forceinline__ void round_matches(const v16f (&den)[NQ][T], const v16f (&s)[NQ][T], uint64_t tile0,
+                                              uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
+                                              const GlobalSink (&sink)[NQ]) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) {
+        bool hit[T];
+        uint32_t hn[T], hd[T];
+        int hr[T];
+        uint64_t hi[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+            const bool valid = (tw + t < ntiles) && tg >= first && tg < end;
+            best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
+                dd = (uint32_t)den[qi][t][r];
+                nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);  // num = (den - S) / 2
+            }, hn[t], hd[t], hr[t]);
+            hit[t] = match_hit(sink[qi], valid && (lane >> 5) == 0, hn[t], hd[t]);
+            hi[t] = tg - first;
+        }
+        append_matches<T>(sink[qi], lane, hit, hn, hd, hr, hi);
+    }
+}
+
+template <int NQ, int T, class Epi>
 __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[NQ], uint64_t tile0,
-                                            uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
-                                            Partial (&best)[NQ]) {
+                                            uint64_t ntiles, uint64_t tw, int lane, Epi &&epi) {
     const bool active = tw < ntiles;  // wave-uniform
     v16f den[NQ][T], s[NQ][T];
 #pragma unroll
@@ -539,7 +576,7 @@ __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const 
         if constexpr (kPlaneGroups % 3 >= 1) compute(sa);
         if constexpr (kPlaneGroups % 3 == 2) compute(sb);
     }
-    round_candidates<NQ, T>(den, s, tile0, ntiles, tw, first, end, lane, best);
+    epi(den, s);
 }
 
 // The two-query round (2 queries x 2 tiles per wave) with the query operands staged once per
@@ -561,10 +598,10 @@ __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const 
 constexpr int kStagedDepth = 4;  // 242 VGPRs; 5: 255, no faster; 6 spills
 typedef uint4 FragRing[2][2][2][2][64];
 
-template <int DEPTH>
+template <int DEPTH, class Epi>
 __device__ __forceinline__ void staged_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[2], uint64_t tile0,
-                                             uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
-                                             int wslot, FragRing &ring, Partial (&best)[2]) {
+                                             uint64_t ntiles, uint64_t tw, int lane, int wslot, FragRing &ring,
+                                             Epi &&epi) {
     constexpr int T = 2;
     static_assert(kWaveSlots == 4 && DEPTH >= 3, "one fetch per wave: 2 queries x 2 chunks of a step");
     v16f den[2][T], s[2][T];
@@ -640,7 +677,7 @@ __device__ __forceinline__ void staged_round(const uint4 *__restrict__ db, const
     }
 #pragma unroll
     for (int i = 0; i < kPlaneGroups % DEPTH; ++i) step(st[(i + DEPTH - 1) % DEPTH], st[i], st[(i + 1) % DEPTH], g + i);
-    round_candidates<2, T>(den, s, tile0, ntiles, tw, first, end, lane, best);
+    epi(den, s);
 }
 
 // A round's bests of NQ queries -> the wave's entries sh[qi * N + pos] (LDS: nothing of a round
@@ -660,7 +697,6 @@ __device__ __forceinline__ void share_stash(Partial (&best)[NQ], int lane, int p
 
 // The N stashed entries of query threadIdx.x < NQ -> its Partial in out[qi][blockIdx.x] (global by
 // type, as the fragments: no flat store either).
-typedef __attribute__((address_space(1))) Partial *GlobalPartial;
 template <int NQ, int N>
 __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPartial (&out)[NQ]) {
     __syncthreads();
@@ -679,28 +715,36 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
     }
 }
 
-// The search of iris_template_search_async over large TILES ranges (4 tiles per wave, separate
-// reduce).  Each workgroup decides at its start, from words another stream may write while the
-// pass runs: its tile group was computed for this query by the pass that hosted it (own_done) ->
-// nothing to do; a guest has been published in the slot -> both queries for the workgroup's 16
-// tiles in the two-query shape (2 tiles x 2 queries per wave, twice), both partials, then the
-// guest's done word; else the single-query pass.
-//   Memory order: only the slot is written while the pass runs.  The done words and the partials
-// a pass writes for its guest are read by the guest's own launch and its reduce, which follow the
-// pass on the device stream, so the end of the kernel publishes them: they are plain stores, and
-// own_done is read relaxed.  (An agent-scope release store per tile group wrote the XCD's L2 back
-// 19 532 times a pass, 0.43 ms of a 7.8-ms two-query pass; an acquire load invalidates the CU's
-// L1 under the other workgroup's query fragments.)  `ready` is read relaxed, and only a workgroup
-// that finds it set pays the acquire, ahead of the slot's fields and the guest's fragments.
+// The pass of iris_template_search_async and iris_template_matches_async over large TILES ranges (4
+// tiles per wave; the search with its separate reduce).  Each workgroup decides at its start, from
+// words another stream may write while the pass runs: its tile group was computed for this query
+// by the pass that hosted it (own_done) -> nothing to do; a guest has been published in the slot
+// -> both queries for the workgroup's 16 tiles in the two-query shape (2 tiles x 2 queries per
+// wave, twice), both queries' results, then the guest's done word; else the single-query pass.
+//   MATCH = false: `out` is the partials array, and a workgroup's results are one Partial per query
+// (the guest's into slot->partials).  MATCH = true: `out` is the query's MatchSink, and every round
+// appends its hits to it and, in the two-query shape, the guest's hits to slot->sink; a tile group
+// is appended for a query by exactly one workgroup -- the hosting pass's, which then sets the done
+// word, or else the query's own -- so the counters stay exact.
+//   Memory order: only the slot is written while the pass runs.  The done words and whatever a
+// pass writes for its guest (partials; records and counter adds, the adds agent-scope relaxed) are
+// read by the guest's own launch and what follows it on the device stream, so the end of the
+// kernel publishes them: they are plain stores, and own_done is read relaxed.  (An agent-scope
+// release store per tile group wrote the XCD's L2 back 19 532 times a pass, 0.43 ms of a 7.8-ms
+// two-query pass; an acquire load invalidates the CU's L1 under the other workgroup's query
+// fragments.)  `ready` is read relaxed, and only a workgroup that finds it set pays the acquire,
+// ahead of the slot's fields and the guest's fragments.
 // even_only (test hook): the guest counts as not visible in odd tile groups.
+template <bool MATCH>
 __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     template_share_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, uint64_t tile0, uint64_t ntiles,
-                          uint64_t first, uint64_t end, Partial *__restrict__ partials, const GuestSlot *slot,
-                          const uint32_t *own_done, unsigned long long *count, uint32_t even_only) {
+                          uint64_t first, uint64_t end, std::conditional_t<MATCH, MatchSink, Partial *__restrict__> out,
+                          const GuestSlot *slot, const uint32_t *own_done, unsigned long long *count,
+                          uint32_t even_only) {
     // one thread reads the words (agent-scope atomics: a plain load could be served from the scalar
     // cache) and the slot's fields behind them; LDS makes the decision the same for every wave
     __shared__ uint32_t sh_flag[2];
-    __shared__ uint64_t sh_guest[3];
+    __shared__ uint64_t sh_guest[MATCH ? 6 : 3];
     if (threadIdx.x == 0) {
         const uint32_t dn =
             own_done ? __hip_atomic_load(own_done + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -710,8 +754,15 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         if (rdy) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             sh_guest[0] = (uint64_t)slot->frag;
-            sh_guest[1] = (uint64_t)slot->partials;
             sh_guest[2] = (uint64_t)slot->done;
+            if constexpr (MATCH) {
+                sh_guest[1] = (uint64_t)slot->sink.buf;
+                sh_guest[3] = slot->sink.cap;
+                sh_guest[4] = (uint64_t)slot->sink.count;
+                sh_guest[5] = (uint64_t)__double_as_longlong(slot->sink.threshold);
+            } else {
+                sh_guest[1] = (uint64_t)slot->partials;
+            }
         }
         sh_flag[0] = dn;
         sh_flag[1] = rdy;
@@ -728,31 +779,65 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         return (uint64_t)hi << 32 | lo;
     };
     constexpr int kRounds = kMfmaTiles / 2;
-    __shared__ Partial sh_best[2 * kRounds * kWaveSlots];
     __shared__ FragRing sh_ring;  // the two-query rounds' operands (static: a solo workgroup holds it too)
-    if (!shared) {
-        Partial best[1] = {partial_none()};
-        const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
-        share_round<1, kMfmaTiles>(db, qf, tile0, ntiles, tw, first, end, lane, best);
-        share_stash<1, kWaveSlots>(best, lane, wslot, sh_best);
-        const GlobalPartial out[1] = {(GlobalPartial)partials};
-        share_finish<1, kWaveSlots>(sh_best, out);
-        return;
-    }
-    const GlobalFrag qf[2] = {(GlobalFrag)qfrag, (GlobalFrag)uniform64(sh_guest[0])};
+    typedef __attribute__((address_space(1))) uint32_t *GlobalWord;
+    if constexpr (MATCH) {
+        typedef __attribute__((address_space(1))) uint64_t *GlobalCount;
+        const GlobalSink own{(GlobalPartial)out.buf, out.cap, (GlobalCount)out.count, out.threshold};
+        if (!shared) {
+            const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
+            const GlobalSink sink[1] = {own};
+            share_round<1, kMfmaTiles>(db, qf, tile0, ntiles, tw, lane, [&](const auto &den, const auto &s) {
+                round_matches<1, kMfmaTiles>(den, s, tile0, ntiles, tw, first, end, lane, sink);
+            });
+            return;
+        }
+        const GlobalFrag qf[2] = {(GlobalFrag)qfrag, (GlobalFrag)uniform64(sh_guest[0])};
+        const GlobalSink sink[2] = {own, GlobalSink{(GlobalPartial)uniform64(sh_guest[1]), uniform64(sh_guest[3]),
+                                                    (GlobalCount)uniform64(sh_guest[4]),
+                                                    __longlong_as_double((long long)uniform64(sh_guest[5]))}};
+        const GlobalWord guest_done = (GlobalWord)uniform64(sh_guest[2]);
+#pragma unroll
+        for (int rd = 0; rd < kRounds; ++rd)
+            staged_round<kStagedDepth>(db, qf, tile0, ntiles, tw + 2 * rd, lane, wslot, sh_ring,
+                                       [&](const auto &den, const auto &s) {
+                                           round_matches<2, 2>(den, s, tile0, ntiles, tw + 2 * rd, first, end, lane, sink);
+                                       });
+        __syncthreads();  // every wave has appended for the guest: only then is its tile group done
+        if (threadIdx.x == 1) {
+            __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (count) atomicAdd(count, 1ull);
+        }
+    } else {
+        __shared__ Partial sh_best[2 * kRounds * kWaveSlots];
+        if (!shared) {
+            Partial best[1] = {partial_none()};
+            const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
+            share_round<1, kMfmaTiles>(db, qf, tile0, ntiles, tw, lane, [&](const auto &den, const auto &s) {
+                round_candidates<1, kMfmaTiles>(den, s, tile0, ntiles, tw, first, end, lane, best);
+            });
+            share_stash<1, kWaveSlots>(best, lane, wslot, sh_best);
+            const GlobalPartial o[1] = {(GlobalPartial)out};
+            share_finish<1, kWaveSlots>(sh_best, o);
+            return;
+        }
+        const GlobalFrag qf[2] = {(GlobalFrag)qfrag, (GlobalFrag)uniform64(sh_guest[0])};
 #pragma unroll  // two copies of the loop: kept as a loop, the round counter and tile numbers spill
-    for (int rd = 0; rd < kRounds; ++rd) {
-        Partial best[2] = {partial_none(), partial_none()};
-        staged_round<kStagedDepth>(db, qf, tile0, ntiles, tw + 2 * rd, first, end, lane, wslot, sh_ring, best);
-        share_stash<2, kRounds * kWaveSlots>(best, lane, rd * kWaveSlots + wslot, sh_best);
-    }
-    const GlobalPartial out[2] = {(GlobalPartial)partials, (GlobalPartial)uniform64(sh_guest[1])};
-    __attribute__((address_space(1))) uint32_t *const guest_done =
-        (__attribute__((address_space(1))) uint32_t *)uniform64(sh_guest[2]);
-    share_finish<2, kRounds * kWaveSlots>(sh_best, out);
-    if (threadIdx.x == 1) {  // the thread that stored the guest's partial
-        __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (count) atomicAdd(count, 1ull);
+        for (int rd = 0; rd < kRounds; ++rd) {
+            Partial best[2] = {partial_none(), partial_none()};
+            staged_round<kStagedDepth>(db, qf, tile0, ntiles, tw + 2 * rd, lane, wslot, sh_ring,
+                                       [&](const auto &den, const auto &s) {
+                                           round_candidates<2, 2>(den, s, tile0, ntiles, tw + 2 * rd, first, end, lane, best);
+                                       });
+            share_stash<2, kRounds * kWaveSlots>(best, lane, rd * kWaveSlots + wslot, sh_best);
+        }
+        const GlobalPartial o[2] = {(GlobalPartial)out, (GlobalPartial)uniform64(sh_guest[1])};
+        const GlobalWord guest_done = (GlobalWord)uniform64(sh_guest[2]);
+        share_finish<2, kRounds * kWaveSlots>(sh_best, o);
+        if (threadIdx.x == 1) {  // the thread that stored the guest's partial
+            __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (count) atomicAdd(count, 1ull);
+        }
     }
 }
 
@@ -765,6 +850,14 @@ __global__ void share_prepare_kernel(GuestSlot *slot, uint32_t *done, uint32_t n
 __global__ void share_publish_kernel(GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done) {
     slot->frag = frag;
     slot->partials = partials;
+    slot->done = done;
+    __hip_atomic_store(&slot->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a match pass's registration: the guest's sink in place of its partials
+__global__ void share_publish_match_kernel(GuestSlot *slot, const void *frag, MatchSink sink, uint32_t *done) {
+    slot->frag = frag;
+    slot->sink = sink;
     slot->done = done;
     __hip_atomic_store(&slot->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -985,9 +1078,21 @@ int launch_template_share_search(const Hooks &h, void *stream, const void *db, c
     // test hook: a pass that is nobody's guest carries its guest in even tile groups only (the
     // guest's own launch then computes the odd ones, and carries its own guest there)
     const bool even_only = h.search_share_even && !own_done;
-    hipLaunchKernelGGL(template_share_kernel, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, partials,
-                       slot, own_done, count, (uint32_t)even_only);
+    hipLaunchKernelGGL(template_share_kernel<false>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
+                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
+                       r.first + r.n, partials, slot, own_done, count, (uint32_t)even_only);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_template_share_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                                const MatchSink &ms, const GuestSlot *slot, const uint32_t *own_done,
+                                unsigned long long *count) {
+    if (!share_search_ok(h, r)) return -1;  // the caller asks first
+    const TileRange t = search_range(h, r);
+    const bool even_only = h.search_share_even && !own_done;  // as the search's
+    hipLaunchKernelGGL(template_share_kernel<true>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
+                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
+                       r.first + r.n, ms, slot, own_done, count, (uint32_t)even_only);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -999,6 +1104,11 @@ int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t
 
 int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done) {
     hipLaunchKernelGGL(share_publish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, partials, done);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done) {
+    hipLaunchKernelGGL(share_publish_match_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, sink, done);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

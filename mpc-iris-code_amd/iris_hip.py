@@ -184,6 +184,8 @@ def load_library(path=None):
             "iris_match_merge": ([ctypes.POINTER(Match), u64, ctypes.POINTER(Match)], ctypes.c_int),
             "iris_template_matches": ([P, P, u64, u64, u64, ctypes.c_double, ctypes.POINTER(Match), u64,
                                        ctypes.POINTER(u64)], ctypes.c_int),
+            "iris_template_matches_async": ([P, P, u64, u64, u64, ctypes.c_double, u64, PP], ctypes.c_int),
+            "iris_pending_matches_wait": ([P, ctypes.POINTER(Match), ctypes.POINTER(u64)], ctypes.c_int),
             "iris_resolver_matches": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.c_double,
                                        ctypes.POINTER(Match), u64, ctypes.POINTER(u64)], ctypes.c_int),
             "iris_resolver_matches_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_double,
@@ -235,6 +237,8 @@ def load_library(path=None):
             "iris_group_template_batch_search": ([P, P, ctypes.c_uint32, ctypes.POINTER(Match)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
+            if "IRIS_HIP_LIB" in os.environ and not hasattr(lib, name):
+                continue  # an older build measured beside this one: it lacks the newer entry points
             f = getattr(lib, name)
             f.argtypes = args
             f.restype = res
@@ -273,6 +277,7 @@ def exported_symbols():
         "iris_resolver_batch_search_masks",
         "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
         "iris_resolver_batch_matches_masks", "iris_template_batch_matches",
+        "iris_template_matches_async", "iris_pending_matches_wait",
         "iris_template_topk", "iris_resolver_topk", "iris_resolver_topk_masks", "iris_topk_merge",
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
     ]
@@ -1068,6 +1073,7 @@ class TemplateEngine(_Engine):
         h = ctypes.c_void_p()
         _check(load_library().iris_template_engine_new(device.handle, _ptr(_c(q, np.uint64)), ctypes.byref(h)))
         self.handle = h
+        self._query = _c(q, np.uint64).copy()  # PendingMatches: a cap=None list longer than its room
 
     def counts(self, db, first=0, n=None):
         """-> (num [n,31] u16, den [n,31] u16)."""
@@ -1120,6 +1126,26 @@ class TemplateEngine(_Engine):
         return _collect_matches(lambda o, c, cnt: f(self.handle, db.handle, int(first), int(n), int(index_base),
                                                     float(threshold), o, c, cnt), cap, out, self)
 
+    def matches_async(self, db, threshold, first=0, n=None, index_base=0, cap=None):
+        """Enqueue matches() and return at once (iris_template_matches_async) -> PendingMatches,
+        whose wait() returns what matches() with the same arguments returns.  The engine may be
+        closed before the wait; the database stays alive and unmodified until it.  cap=None asks
+        for every match: the pending holds room as matches() would on its first call, and a longer
+        list is fetched by one blocking matches() at the wait."""
+        n = (len(db) - first) if n is None else n
+        want_all = cap is None
+        cap = max(1024, getattr(self, "_match_room", 0)) if want_all else int(cap)
+        h = ctypes.c_void_p()
+        _check(load_library().iris_template_matches_async(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                          float(threshold), cap, ctypes.byref(h)))
+        again = None
+        if want_all:
+            device, q, args = self.device, self._query, (db, threshold, first, n, index_base)
+
+            def again(count):
+                with TemplateEngine(device, q) as e:
+                    return e.matches(*args, cap=count)
+        return PendingMatches(h, cap, again)
 
     def topk(self, db, k, first=0, n=None, index_base=0):
         """The k closest records of the range, best first, in one database pass
@@ -1149,6 +1175,34 @@ class PendingSearch:
         if getattr(self, "handle", None) is not None:
             try:
                 load_library().iris_pending_wait(self.handle, None)
+            except Exception:
+                pass
+
+
+class PendingMatches:
+    """An enqueued threshold-match pass (TemplateEngine.matches_async); wait() -> (list[Match],
+    count), once."""
+
+    def __init__(self, handle, cap, again=None):
+        self.handle = handle
+        self.cap = cap
+        self._again = again
+
+    def wait(self):
+        if self.handle is None:
+            raise IrisError(-1, "PendingMatches.wait called twice")
+        buf = (Match * self.cap)() if self.cap else None
+        count = ctypes.c_uint64()
+        h, self.handle = self.handle, None
+        _check(load_library().iris_pending_matches_wait(h, buf, ctypes.byref(count)))
+        if self._again is not None and count.value > self.cap:
+            return self._again(count.value)
+        return [buf[i] for i in range(min(self.cap, count.value))], count.value
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                load_library().iris_pending_matches_wait(self.handle, None, ctypes.byref(ctypes.c_uint64()))
             except Exception:
                 pass
 
@@ -1670,7 +1724,7 @@ def f64_bits(x):
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
     "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "TOPK_MAX", "dot_bool", "dot_u16",
-    "Group", "GroupDatabase", "GroupPendingSearch",
+    "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
     "ROTATIONS", "BITS", "LIMBS", "COLS", "ROWS",
