@@ -536,6 +536,33 @@ impl Drop for PendingMatches {
     }
 }
 
+/// An enqueued top-k pass (`iris_template_topk_async`); `wait` blocks for it alone and returns
+/// what `TemplateEngine::topk` returns.
+pub struct PendingTopk {
+    raw: *mut ffi::IrisPendingTopk,
+    k: u32,
+}
+
+unsafe impl Send for PendingTopk {}
+
+impl PendingTopk {
+    pub fn wait(mut self) -> Result<Vec<(f64, usize)>> {
+        let raw = std::mem::replace(&mut self.raw, ptr::null_mut());
+        collect_topk(self.k, |out, count| unsafe { ffi::iris_pending_topk_wait(raw, out, count) })
+    }
+}
+
+impl Drop for PendingTopk {
+    fn drop(&mut self) {
+        if !self.raw.is_null() {
+            let mut count = 0u32;
+            unsafe {
+                ffi::iris_pending_topk_wait(self.raw, ptr::null_mut(), &mut count);
+            }
+        }
+    }
+}
+
 impl TemplateEngine {
     pub fn new(query: &Template) -> Self {
         Self::new_on(default_device(), query).unwrap_or_else(|e| panic!("TemplateEngine::new: {e}"))
@@ -610,6 +637,15 @@ impl TemplateEngine {
         collect_topk(k, |out, count| unsafe {
             ffi::iris_template_topk(self.h.raw, db.raw(), first, n, index_base, k, out, count)
         })
+    }
+
+    /// Enqueues `topk` and returns at once (iris_template_topk_async): a pass still running may
+    /// compute the next one submitted.  The engine may be dropped before the wait; the database
+    /// must outlive it, unmodified.
+    pub fn topk_async(&self, db: &Database, first: u64, n: u64, index_base: u64, k: u32) -> Result<PendingTopk> {
+        let mut raw = ptr::null_mut();
+        check(unsafe { ffi::iris_template_topk_async(self.h.raw, db.raw(), first, n, index_base, k, &mut raw) })?;
+        Ok(PendingTopk { raw, k })
     }
 
     /// Enqueues the search and returns at once (the engine may be dropped before the

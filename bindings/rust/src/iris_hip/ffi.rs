@@ -63,6 +63,8 @@ pub struct IrisPending {
 }
 /// `iris_pending_matches_t`: the same opaque struct (each wait refuses the other's handles).
 pub type IrisPendingMatches = IrisPending;
+/// `iris_pending_topk_t`: the same opaque struct again.
+pub type IrisPendingTopk = IrisPending;
 /// Device groups (`iris_group_t`, `iris_group_db_t`, `iris_group_pending_t`).
 #[repr(C)]
 pub struct IrisGroup {
@@ -337,6 +339,16 @@ extern "C" {
         out: *mut IrisMatch,
         count: *mut u32,
     ) -> c_int;
+    pub fn iris_template_topk_async(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        k: u32,
+        out: *mut *mut IrisPending,
+    ) -> c_int;
+    pub fn iris_pending_topk_wait(pending: *mut IrisPending, out: *mut IrisMatch, count: *mut u32) -> c_int;
     pub fn iris_resolver_topk(
         dev: *mut IrisDevice,
         shares_device: *const *const u16,

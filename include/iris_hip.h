@@ -86,9 +86,11 @@ typedef struct iris_device iris_device_t;
 typedef struct iris_db iris_db_t;
 typedef struct iris_engine iris_engine_t;
 typedef struct iris_pending iris_pending_t;
-/* The handle of iris_template_matches_async: the same opaque struct under a name of its own.  Each
- * of the two waits refuses (IRIS_E_ARG) and leaves alone a handle the other submission made. */
+/* The handles of iris_template_matches_async and iris_template_topk_async: the same opaque struct
+ * under names of their own.  Each of the three waits refuses (IRIS_E_ARG) and leaves alone a handle
+ * another submission made. */
 typedef iris_pending_t iris_pending_matches_t;
+typedef iris_pending_t iris_pending_topk_t;
 
 /* ---------------------------------------------------------------- errors */
 const char *iris_last_error(void);
@@ -531,7 +533,7 @@ int iris_template_batch_matches(iris_engine_t *engine, const iris_db_t *db, uint
  * the loops generalised are src/template.rs:43-47 + src/main.rs:616-621).  The submission
  * enqueues the pass and returns at once; iris_pending_matches_wait blocks for THAT pass only,
  * fills out (cap entries, the submission's cap; NULL only if cap == 0) and *count (required), and
- * frees the handle whatever it returns (but a search's handle: see iris_pending_matches_t).
+ * frees the handle whatever it returns (but another submission's handle: see iris_pending_matches_t).
  *
  * Contract: out and *count are byte for byte what iris_template_matches(engine, db, first, n,
  * index_base, threshold, out, cap, count) would have returned at the submission: the exact total
@@ -584,9 +586,9 @@ int iris_pending_matches_wait(iris_pending_t *pending /* an iris_pending_matches
  *
  * Out of scope: of the batch engines, the distance batch engine (its rows are shares, no
  * distances; the masks batch engine has iris_resolver_batch_topk_masks and the template batch
- * engine iris_template_batch_topk); the host-array forms (*_host), the asynchronous pipeline
- * (threshold matching alone has one, iris_template_matches_async),
- * device groups (iris_topk_merge below is the hand-sharding answer) and k > 64. */
+ * engine iris_template_batch_topk); the host-array forms (*_host); the rest of the asynchronous pipeline
+ * (the single-query template form has one, iris_template_topk_async below: no resolver, batch-engine
+ * or group form); device groups (iris_topk_merge below is the hand-sharding answer) and k > 64. */
 #define IRIS_TOPK_MAX 64
 /* iris_template_search's sibling (src/template.rs:43-47 + src/main.rs:616-621): indices are
  * index_base + first + i. */
@@ -665,6 +667,32 @@ int iris_template_batch_topk(iris_engine_t *engine, const iris_db_t *db, uint64_
  * not overlapping `records`) receives *count = min(k, valid records) records, best first, copied
  * as given; entries past *count are left untouched. */
 int iris_topk_merge(const iris_match_t *records, uint64_t nrecords, uint32_t k, iris_match_t *out, uint32_t *count);
+
+/* Pipelined form of iris_template_topk, as iris_template_search_async is of iris_template_search
+ * and iris_template_matches_async of iris_template_matches (no reference counterpart: the
+ * reference's calls block, src/lib.rs:42-53; the loops generalised are src/template.rs:43-47 +
+ * src/main.rs:616-621).  The submission enqueues the pass and returns at once;
+ * iris_pending_topk_wait blocks for THAT pass only, fills out (k entries, the submission's k;
+ * required) and *count (required), and frees the handle whatever it returns (but a handle of
+ * another submission: see iris_pending_topk_t).
+ *
+ * Contract: out[0..*count) and *count are byte for byte what iris_template_topk(engine, db, first,
+ * n, index_base, k, out, count) would have returned at the submission; entries past *count are
+ * untouched, n == 0 gives 0.  A pass that is still streaming the database may compute the top-k
+ * pass submitted after it (same records of the same database, unwritten since; k may differ); the
+ * result does not depend on it.  A top-k pass computes neither a search nor a match pass, nor the
+ * reverse.
+ *
+ * The value arguments (k in 1..IRIS_TOPK_MAX, out) are checked before the handles; engine-kind,
+ * database, layout and range checks are iris_template_topk's, made at the submission (the wait's
+ * out and count at the wait); a batch engine is refused, and so is an engine that keeps no host
+ * copy of its query.  The engine may be destroyed before the wait; the database must stay alive
+ * and unmodified until it.  Every pending holds one list of k records per wave of its pass (24 k
+ * bytes each; 120 MB at k = 64 over 10M templates) until its wait. */
+int iris_template_topk_async(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                             uint64_t index_base, uint32_t k, iris_pending_t **out /* an iris_pending_topk_t */);
+int iris_pending_topk_wait(iris_pending_t *pending /* an iris_pending_topk_t */, iris_match_t *out,
+                           uint32_t *count);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

@@ -721,6 +721,30 @@ private:
     uint64_t cap_;
 };
 
+// An enqueued top-k pass (TemplateEngine::topk_async): wait() once for what topk() with the same
+// arguments returns; destroying it unwaited waits and discards the result.
+class PendingTopk {
+public:
+    PendingTopk(iris_pending_topk_t *p, uint32_t k) : p_(p), k_(k) {}
+    PendingTopk(PendingTopk &&o) noexcept : p_(o.p_), k_(o.k_) { o.p_ = nullptr; }
+    PendingTopk(const PendingTopk &) = delete;
+    PendingTopk &operator=(const PendingTopk &) = delete;
+    ~PendingTopk() {
+        uint32_t count = 0;
+        if (p_) (void)iris_pending_topk_wait(p_, nullptr, &count);
+    }
+    std::vector<Match> wait() {
+        if (!p_) throw Error(IRIS_E_ARG, "PendingTopk::wait called twice");
+        iris_pending_topk_t *p = p_;
+        p_ = nullptr;
+        return detail::collect_topk(k_, [&](Match *out, uint32_t *count) { return iris_pending_topk_wait(p, out, count); });
+    }
+
+private:
+    iris_pending_topk_t *p_;
+    uint32_t k_;
+};
+
 // Template vs Template database (src/template.rs:43-64) with the resolver's argmin.
 class TemplateEngine : public detail::Engine {
 public:
@@ -752,6 +776,13 @@ public:
         iris_pending_t *p = nullptr;
         check(iris_template_search_async(h_, db.handle(), first, n, index_base, &p));
         return PendingSearch(p);
+    }
+    // pipelined form of topk(): returns once the pass is enqueued; a pass still running may compute
+    // the next one submitted (iris_template_topk_async)
+    PendingTopk topk_async(const Database &db, uint32_t k, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        iris_pending_topk_t *p = nullptr;
+        check(iris_template_topk_async(h_, db.handle(), first, n, index_base, k, &p));
+        return PendingTopk(p, k);
     }
     // pipelined form of matches() with an explicit cap (the list holds the min(count, cap) lowest
     // indices, count is the total): returns once the pass is enqueued; a pass still running may

@@ -194,6 +194,8 @@ void device_teardown(iris_device *d) {
         side_sync(d);
         for (MatchBufs &m : d->match_free)
             if (m.dev.p) (void)hipFree(m.dev.p);
+        for (MatchBufs &m : d->topk_free)
+            if (m.dev.p) (void)hipFree(m.dev.p);
         for (int b = 0; b < 2; ++b) {
             if (d->apart[b].p) (void)hipFree(d->apart[b].p);
             if (d->apart_read[b]) (void)hipEventDestroy(d->apart_read[b]);
@@ -391,9 +393,12 @@ int iris_device_kernel_stats(iris_device_t *d, const char *kernel, uint64_t *lau
     IRIS_KEEP_DEVICE();
     ARG(d && kernel, "NULL argument");
     std::lock_guard<std::recursive_mutex> g(d->mu);
-    const int shared = !strcmp(kernel, "search_shared") ? 0 : !strcmp(kernel, "match_shared") ? 1 : -1;
+    const int shared = !strcmp(kernel, "search_shared")  ? kShareSearch
+                       : !strcmp(kernel, "match_shared") ? kShareMatch
+                       : !strcmp(kernel, "topk_shared")  ? kShareTopk
+                                                         : -1;
     if (shared >= 0) {
-        // shared passes: launches = searches (match passes) registered as guests, items = tile groups
+        // shared passes: launches = searches (match, top-k passes) registered as guests, items = tile groups
         // carried for them (a device counter, read behind whatever the device stream holds); no time
         // of its own
         unsigned long long carried = 0;
@@ -433,10 +438,10 @@ int iris_device_reset_stats(iris_device_t *d) {
     std::lock_guard<std::recursive_mutex> g(d->mu);
     d->stats.clear();
     d->ra_launches = d->ra_records = d->ra_window_max = 0;
-    d->share_regs[0] = d->share_regs[1] = 0;
+    for (uint64_t &r : d->share_regs) r = 0;
     if (d->share_count) {
         CHK(set_device(d));
-        HIPCHK(hipMemsetAsync(d->share_count, 0, 2 * sizeof(*d->share_count), d->stream));
+        HIPCHK(hipMemsetAsync(d->share_count, 0, kShareKinds * sizeof(*d->share_count), d->stream));
     }
     return 0;
 }

@@ -69,28 +69,28 @@ int share_take(iris_device *d, uint32_t np, SharePass **out) {
 }  // namespace
 
 int iris_api::share_join(iris_device *d, int share_host, const iris_db *db, uint64_t first, uint64_t n, uint32_t np,
-                         const iris_template_t *query, hipEvent_t after, Partial *partials, const MatchSink *sink,
-                         ShareJoin *out) {
+                         const iris_template_t *query, hipEvent_t after, ShareKind kind, Partial *partials,
+                         const MatchSink *sink, ShareJoin *out) {
     *out = ShareJoin{};
     SharePass *sp = nullptr;
     if (d->hooks.search_share) CHK(share_take(d, np, &sp));
     if (!sp) return 0;
-    const bool match = sink != nullptr;
+    const bool match = kind == kShareMatch;
     sp->db = db;
     sp->writes = db->writes;
     sp->first = first;
     sp->n = n;
-    sp->match = match;
+    sp->kind = kind;
     // the pass before this one hosts it if it came from the same entry point and covers the same
     // records of the same database, unwritten since, has no guest yet and has not ended
     SharePass *host = share_host >= 0 ? &d->share_ring[share_host] : nullptr;
-    const bool guest = host && host != sp && host->guest < 0 && host->match == match && host->db == db &&
+    const bool guest = host && host != sp && host->guest < 0 && host->kind == kind && host->db == db &&
                        host->writes == db->writes && host->first == first && host->n == n &&
                        hipEventQuery(host->ended) == hipErrorNotReady;
     // on the sharing stream: behind `after` (a search: the reduce that last read its partials
     // buffer), the slot (and done words) zeroed -- and a match pass's counter: on the device stream,
     // ahead of the pass's own launch, the zeroing would land after the hosting pass and wipe what it
-    // counted for this one -- then, for a guest, its fragments built from the host copy of the query
+    // counted for this one; a top-k pass's lists need no zeroing, every unit being stored once -- then, for a guest, its fragments built from the host copy of the query
     // (the engine's own buffer is built in device-stream order, behind the running pass) and the slot
     // of the hosting pass published
     if (after) HIPCHK(hipStreamWaitEvent(d->share, after, 0));
@@ -101,11 +101,11 @@ int iris_api::share_join(iris_device *d, int share_host, const iris_db *db, uint
         uint32_t *tab = (uint32_t *)sp->qbuf;
         uint32_t *frag = (uint32_t *)((char *)sp->qbuf + qalign(kTemplateTabBytes));
         if (launch_query_template(d->share, query, tab, frag) != 0 ||
-            (match ? launch_share_publish_match(d->share, host->slot, frag, *sink, (uint32_t *)sp->done.p)
-                   : launch_share_publish(d->share, host->slot, frag, partials, (uint32_t *)sp->done.p)) != 0)
+            (sink ? launch_share_publish_match(d->share, host->slot, frag, *sink, (uint32_t *)sp->done.p)
+                  : launch_share_publish(d->share, host->slot, frag, partials, (uint32_t *)sp->done.p)) != 0)
             return fail(IRIS_E_HIP, "kernel launch failed: share_publish");
         host->guest = (int)(sp - d->share_ring);
-        d->share_regs[match] += 1;
+        d->share_regs[kind] += 1;
     }
     HIPCHK(hipEventRecord(d->share_reg, d->share));
     HIPCHK(hipStreamWaitEvent(d->stream, d->share_reg, 0));
@@ -117,7 +117,7 @@ int iris_api::share_join(iris_device *d, int share_host, const iris_db *db, uint
     }
     out->sp = sp;
     out->own_done = guest ? (const uint32_t *)sp->done.p : nullptr;
-    out->count = d->share_count + match;
+    out->count = d->share_count + kind;
     return 0;
 }
 
@@ -188,7 +188,8 @@ int iris_api::search_enqueue(iris_engine_t *e, const iris_db_t *db, uint64_t fir
                             share_search_ok(d->hooks, r);
     if (share_form) {
         ShareJoin j;
-        CHK(share_join(d, share_host, db, first, n, np, e->host_query, d->apart_read[b], part, nullptr, &j));
+        CHK(share_join(d, share_host, db, first, n, np, e->host_query, d->apart_read[b], kShareSearch, part, nullptr,
+                       &j));
         CHK(timed(d, "template_search", n, [&] {
             return launch_template_share_search(d->hooks, d->stream, db->data, e->qfrag, r, part, &written,
                                                 j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
@@ -349,7 +350,8 @@ int iris_template_search_async(iris_engine_t *e, const iris_db_t *db, uint64_t f
 int iris_pending_wait(iris_pending_t *p, iris_match_t *out) {
     IRIS_KEEP_DEVICE();
     ARG(p, "pending is NULL");
-    ARG(!p->matches, "pending of iris_template_matches_async: iris_pending_matches_wait waits for it");
+    ARG(p->kind != kShareMatch, "pending of iris_template_matches_async: iris_pending_matches_wait waits for it");
+    ARG(p->kind != kShareTopk, "pending of iris_template_topk_async: iris_pending_topk_wait waits for it");
     iris_device *d = p->dev;
     hipError_t err = hipSuccess;
     if (p->ev) err = hipEventSynchronize(p->ev);  // this search only: later enqueued work keeps running

@@ -1,6 +1,6 @@
 // iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
-// and batched, with the runners that turn launch units into match lists, and the pipelined form of
-// the single-query template match.  Calls, locking and errors: see iris_api.hip.
+// and batched, with the runners that turn launch units into match lists, and the pipelined forms of
+// the single-query template match and top-k.  Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
 #include <new>
@@ -217,7 +217,7 @@ static int match_pass_enqueue(iris_device *d, const iris_pending_matches *p, con
         // the sharing form (§4.1): the range the asynchronous search shares on, the hooks included
         ShareJoin j;
         CHK(share_join(d, d->share_last, p->db, p->first, p->n, mfma_search_partials(d->hooks, r), &p->query, nullptr,
-                       nullptr, &ms, &j));
+                       kShareMatch, nullptr, &ms, &j));
         d->share_last = -1;
         if (!j.sp) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
         CHK(timed(d, "template_match", p->n, [&] {
@@ -247,7 +247,7 @@ int iris_template_matches_async(iris_engine_t *e, const iris_db_t *db, uint64_t 
     if (!e->host_query) return fail(IRIS_E_ARG, "engine keeps no host copy of its query");
     iris_pending_matches *p = new (std::nothrow) iris_pending_matches();
     if (!p) return fail(IRIS_E_NOMEM, "out of host memory");
-    p->matches = true;
+    p->kind = kShareMatch;
     p->dev = d;
     p->db = db;
     p->first = first;
@@ -344,7 +344,8 @@ static int pending_matches_finish(iris_pending_matches *p, uint64_t total, iris_
 int iris_pending_matches_wait(iris_pending_t *pending, iris_match_t *out, uint64_t *count) {
     IRIS_KEEP_DEVICE();
     ARG(pending, "pending is NULL");
-    ARG(pending->matches, "pending of iris_template_search_async: iris_pending_wait waits for it");
+    ARG(pending->kind != kShareSearch, "pending of iris_template_search_async: iris_pending_wait waits for it");
+    ARG(pending->kind != kShareTopk, "pending of iris_template_topk_async: iris_pending_topk_wait waits for it");
     iris_pending_matches *p = static_cast<iris_pending_matches *>(pending);
     iris_device *d = p->dev;
     int rc = 0;
@@ -469,6 +470,180 @@ int iris_template_topk(iris_engine_t *e, const iris_db_t *db, uint64_t first, ui
         return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts)
                      : launch_template_topk(d->stream, db->data, e->qtab, r, ts);
     });
+}
+
+// ------------------------------------------------------------------ pipelined top-k
+
+// iris_template_topk_async .. iris_pending_topk_wait.  The pass stores its lists
+// into a buffer of the pending's own; behind it, on the side stream, the merge folds them and its
+// last level writes the k records to the pending's pinned slot -- as the blocking call's writes the
+// device's pinned result -- and `ev` is recorded there.
+struct iris_pending_topk : iris_pending {  // dev, ev (null for an empty range), n, base: as the search's
+    MatchBufs bufs;
+    uint32_t k = 0;
+};
+
+// buffers for a pending whose pass writes `units` lists of k (caller holds the device lock)
+static int topk_bufs_take(iris_device *d, uint64_t units, uint32_t k, MatchBufs *out) {
+    if (d->topk_free.empty()) {  // as match_bufs_take
+        constexpr int kSlots = 32;
+        void *blk = nullptr;
+        hipError_t e = hipHostMalloc(&blk, kSlots * kTopkSlotBytes, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(IRIS_E_NOMEM, std::string("hipHostMalloc top-k slots: ") + hipGetErrorString(e));
+        d->slot_blocks.push_back(blk);
+        for (int i = kSlots - 1; i >= 0; --i)
+            d->topk_free.push_back(MatchBufs{DevBuf{}, (char *)blk + (size_t)i * kTopkSlotBytes});
+    }
+    // the one returned last whose buffer is large enough (a steady pipeline keeps to a few), else one
+    // that has no buffer yet: growing a buffer frees it, and hipFree waits for the device -- for the
+    // very pass that could have hosted this one (k, and so the size, changes from call to call)
+    const size_t bytes = (units + topk_spare_lists(units)) * k * sizeof(Partial);
+    size_t pick = d->topk_free.size() - 1;
+    for (size_t i = d->topk_free.size(); i-- > 0;)
+        if (d->topk_free[i].dev.cap >= bytes) {
+            pick = i;
+            break;
+        }
+    if (d->topk_free[pick].dev.cap < bytes)
+        for (size_t i = d->topk_free.size(); i-- > 0;)
+            if (!d->topk_free[i].dev.p) {
+                pick = i;
+                break;
+            }
+    MatchBufs b = d->topk_free[pick];
+    d->topk_free.erase(d->topk_free.begin() + pick);
+    const int rc = ensure(d, b.dev, bytes);
+    if (rc != 0) {
+        d->topk_free.push_back(b);
+        return rc;
+    }
+    *out = b;
+    return 0;
+}
+
+// The pass of a pending over its range into its lists, on the device stream.  Large TILES ranges
+// run the sharing form (§4.1) and take a place in the ring; every other range runs the blocking
+// call's kernel and neither hosts nor is hosted.
+static int topk_pass_enqueue(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r,
+                             const MatchSink &ts) {
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    if (tiles && share_search_ok(d->hooks, r)) {
+        ShareJoin j;
+        CHK(share_join(d, d->share_last, db, r.first, r.n, mfma_search_partials(d->hooks, r), e->host_query, nullptr,
+                       kShareTopk, nullptr, &ts, &j));
+        d->share_last = -1;
+        CHK(timed(d, "template_topk", r.n, [&] {
+            return launch_template_share_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts, j.sp ? j.sp->slot : nullptr,
+                                              j.own_done, j.count);
+        }));
+        return share_launched(d, j);
+    }
+    d->share_last = -1;  // only the device's latest pass can host
+    return timed(d, "template_topk", r.n, [&] {
+        return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts)
+                     : launch_template_topk(d->stream, db->data, e->qtab, r, ts);
+    });
+}
+
+int iris_template_topk_async(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                             uint32_t k, iris_pending_t **out) {
+    IRIS_KEEP_DEVICE();
+    ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");  // the value arguments first
+    ARG(out, "out is NULL");
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (!e->host_query) return fail(IRIS_E_ARG, "engine keeps no host copy of its query");
+    iris_pending_topk *p = new (std::nothrow) iris_pending_topk();
+    if (!p) return fail(IRIS_E_NOMEM, "out of host memory");
+    p->kind = kShareTopk;
+    p->dev = d;
+    p->n = n;
+    p->base = index_base + first;
+    p->k = k;
+    if (n == 0) {
+        device_retain(d);
+        *out = p;
+        return 0;
+    }
+    const LaunchRange r{first, n};
+    const uint64_t units = db->k.layout == IRIS_LAYOUT_TILES ? mfma_topk_units(d->hooks, r) : template_topk_units(r);
+    int rc = topk_bufs_take(d, units, k, &p->bufs);
+    const bool taken = rc == 0;
+    if (rc == 0) {
+        p->ev = take_event(d);
+        if (!p->ev) rc = fail(IRIS_E_HIP, "hipEventCreate failed");
+    }
+    if (rc == 0) rc = ensure_aux(d);
+    Partial *lists = (Partial *)p->bufs.dev.p, *spare = lists + units * k;
+    if (rc == 0) rc = topk_pass_enqueue(d, e, db, r, topk_sink(lists, k));
+    if (rc == 0) {
+        // behind the pass, on the side stream (the next pass is not held up): the merge, whose last
+        // level writes the pinned slot, then the pending's event
+        hipError_t err = hipEventRecord(p->ev, d->stream);
+        if (err == hipSuccess) err = hipStreamWaitEvent(d->aux, p->ev, 0);
+        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("enqueue top-k merge: ") + hipGetErrorString(err));
+        if (rc == 0)
+            rc = timed(d, "topk_merge", units,
+                       [&] { return launch_topk_merge(d->aux, lists, spare, units, k, (Partial *)p->bufs.host); }, d->aux);
+        if (rc == 0 && (err = hipEventRecord(p->ev, d->aux)) != hipSuccess)
+            rc = fail(IRIS_E_HIP, std::string("enqueue top-k merge: ") + hipGetErrorString(err));
+    }
+    if (rc != 0) {
+        if (taken) {
+            (void)hipStreamSynchronize(d->stream);  // whatever was enqueued no longer writes the buffers
+            side_sync(d);
+            d->topk_free.push_back(p->bufs);
+        }
+        if (p->ev) d->event_pool.push_back(p->ev);
+        delete p;
+        return rc;
+    }
+    device_retain(d);
+    *out = p;
+    return 0;
+}
+
+int iris_pending_topk_wait(iris_pending_t *pending, iris_match_t *out, uint32_t *count) {
+    IRIS_KEEP_DEVICE();
+    ARG(pending, "pending is NULL");
+    ARG(pending->kind != kShareSearch, "pending of iris_template_search_async: iris_pending_wait waits for it");
+    ARG(pending->kind != kShareMatch, "pending of iris_template_matches_async: iris_pending_matches_wait waits for it");
+    iris_pending_topk *p = static_cast<iris_pending_topk *>(pending);
+    iris_device *d = p->dev;
+    int rc = 0;
+    if (!out) rc = fail(IRIS_E_ARG, "out is NULL");
+    else if (!count) rc = fail(IRIS_E_ARG, "count is NULL");
+    hipError_t err = hipSuccess;
+    if (p->ev) err = hipEventSynchronize(p->ev);  // this pass and its merge only: later enqueued work keeps running
+    {
+        std::lock_guard<std::recursive_mutex> g(d->mu);
+        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(err));
+        if (rc == 0) {
+            // the blocking call's conversion: the list is sorted with the empty entries last
+            uint32_t c = 0;
+            if (p->n > 0) {
+                const Partial *res = (const Partial *)p->bufs.host;
+                while (c < p->k && res[c].den != 0) ++c;
+                for (uint32_t i = 0; i < c; ++i) match_from(res[i], true, p->base, &out[i]);
+            }
+            *count = c;
+        }
+        if (p->n > 0) {
+            if (err != hipSuccess) {  // nothing may still write buffers that go back to the list
+                (void)hipStreamSynchronize(d->stream);
+                side_sync(d);
+            }
+            d->topk_free.push_back(p->bufs);
+        }
+        if (p->ev) d->event_pool.push_back(p->ev);
+        fold_done(d);
+    }
+    delete p;
+    device_release(d);
+    return rc;
 }
 
 // iris_resolver_search's top-k sibling

@@ -318,6 +318,19 @@ __device__ __forceinline__ void topk_insert(Partial &entry, uint32_t k, int lane
 __device__ __forceinline__ void topk_store(const MatchSink &m, uint64_t unit, int lane, const Partial &entry) {
     if ((uint64_t)lane < m.cap) m.buf[unit * m.cap + (uint64_t)lane] = entry;
 }
+// The same store into lists whose pointer is global by type (GlobalLists, iris_mfma.hip: the sharing
+// pass's sink), field by field as append_matches stores its records.
+template <class Lists>
+__device__ __forceinline__ void topk_store_lists(const Lists &m, uint64_t unit, int lane, const Partial &entry) {
+    if ((uint32_t)lane < m.k) {
+        auto *const p = m.buf + (unit * m.k + (uint64_t)lane);
+        p->num = entry.num;
+        p->den = entry.den;
+        p->rot = entry.rot;
+        p->pad = 0;
+        p->idx = entry.idx;
+    }
+}
 
 // Last-workgroup reduction (a search's partials reduce without a second launch).  Thread 0
 // publishes this workgroup's partial with agent-scope atomic stores (sc1: written through

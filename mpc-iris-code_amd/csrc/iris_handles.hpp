@@ -97,6 +97,10 @@ struct UploadTune {
 // pass owns on the device.  The entries form a ring; one is taken again only once its own pass and
 // the pass that registered as its guest (the only other one that touches it) have ended.
 constexpr int kShareRing = 8;
+// The entry point a sharing pass came from: a pass hosts only a pass of its own kind.  The value
+// indexes the registrations and the device counters of tile groups carried (kernel stats
+// "search_shared", "match_shared", "topk_shared").
+enum ShareKind { kShareSearch = 0, kShareMatch = 1, kShareTopk = 2, kShareKinds = 3 };
 struct SharePass {
     iris::GuestSlot *slot = nullptr;  // this pass's guest slot, read by its kernel
     DevBuf done;                      // as a guest: the words the hosting pass sets, read by this pass's kernel
@@ -106,7 +110,7 @@ struct SharePass {
     int guest = -1;                   // ring index of the pass registered as this one's guest
     const struct iris_db *db = nullptr;  // what the pass searches: a guest must ask for the same
     uint64_t writes = 0, first = 0, n = 0;
-    bool match = false;  // a match pass (iris_template_matches_async): it hosts match passes only, a search searches only
+    ShareKind kind = kShareSearch;
 };
 
 // What one pending iris_template_matches_async owns from submission to wait (a per-device free
@@ -121,6 +125,10 @@ struct MatchBufs {
     DevBuf dev;
     void *host = nullptr;
 };
+// A pending iris_template_topk_async owns the same pair from a free list of its own: dev holds the
+// pass's lists and behind them the merge's spare lists ((units + topk_spare_lists(units)) * k
+// records), host is a pinned slot of kTopkSlotBytes that takes the merged k records.
+constexpr size_t kTopkSlotBytes = iris::kTopkMax * sizeof(iris::Partial);
 
 struct iris_device {
     int ordinal = 0;
@@ -142,6 +150,8 @@ struct iris_device {
     DevBuf match_sinks;
     // asynchronous threshold matching: buffers no pending holds (the pinned slots come out of slot_blocks)
     std::vector<MatchBufs> match_free;
+    // asynchronous top-k: the same for its pendings
+    std::vector<MatchBufs> topk_free;
     // zeroed device word of the fused (last-workgroup) search reduce; searches on the stream
     // are serialised, and each launch leaves it zeroed
     DevBuf ticket;
@@ -170,13 +180,13 @@ struct iris_device {
     // registrations run on (the side stream waits behind the running pass, so it cannot carry them),
     // the event that orders a pass behind its registration, and the device counter of tile groups
     // carried for guests (kernel stats "search_shared", with the registrations as its launches;
-    // word and entry [1]: the match passes', "match_shared")
+    // word and entry [1]: the match passes', "match_shared"; [2]: the top-k passes', "topk_shared")
     SharePass share_ring[kShareRing];
     int share_next = 0, share_last = -1;
     hipStream_t share = nullptr;
     hipEvent_t share_reg = nullptr;
     unsigned long long *share_count = nullptr;
-    uint64_t share_regs[2] = {0, 0};
+    uint64_t share_regs[kShareKinds] = {0, 0, 0};
     // handles alive on this device (1 for the device handle itself + 1 per database
     // and engine handle): the device is torn down when the last one is released,
     // so handles may be destroyed in any order
@@ -271,9 +281,10 @@ struct Readahead {
 };
 
 // iris_template_search_async .. iris_pending_wait; iris_template_matches_async's handle extends it
-// (iris_pending_matches, iris_api_select.hip), and `matches` tells each wait which one it was given
+// (iris_pending_matches, iris_api_select.hip), as does iris_template_topk_async's (iris_pending_topk),
+// and `kind` tells each wait which one it was given
 struct iris_pending {
-    bool matches = false;
+    ShareKind kind = kShareSearch;
     iris_device *dev = nullptr;
     hipEvent_t ev = nullptr;          // recorded after the reduce (null for an empty range)
     iris::Partial *slot = nullptr;    // pinned host slot the reduce writes
@@ -547,16 +558,16 @@ int search_enqueue(iris_engine *e, const iris_db *db, uint64_t first, uint64_t n
 // share_last as the call found it) if that pass can host it, and orders the device stream behind
 // the registration.  query: the host copy the guest's fragments are built from; after: an event the
 // sharing stream waits for first (or null).  A search gives its partials buffer, a match pass its
-// sink (whose counter is zeroed here, on the sharing stream).  The kernel takes sp->slot, own_done
-// and count; share_launched, behind the launch, makes the pass the one that can host next.
+// sink (whose counter is zeroed here, on the sharing stream), a top-k pass its topk_sink.  The
+// kernel takes sp->slot, own_done and count; share_launched, behind the launch, makes the pass the one that can host next.
 struct ShareJoin {
     SharePass *sp = nullptr;
     const uint32_t *own_done = nullptr;  // a guest's done words
     unsigned long long *count = nullptr;  // the device counter of tile groups carried
 };
 int share_join(iris_device *d, int share_host, const iris_db *db, uint64_t first, uint64_t n, uint32_t np,
-               const iris_template_t *query, hipEvent_t after, iris::Partial *partials, const iris::MatchSink *sink,
-               ShareJoin *out);
+               const iris_template_t *query, hipEvent_t after, ShareKind kind, iris::Partial *partials,
+               const iris::MatchSink *sink, ShareJoin *out);
 int share_launched(iris_device *d, const ShareJoin &j);
 // Fills dst with the source bytes [off, off + bytes) of a write; false on a read error (errno set).
 using SlotFill = std::function<bool(void *dst, size_t off, size_t bytes)>;

@@ -210,7 +210,7 @@ struct Hooks {
     uint32_t resident_budget_mb = 0; // IRIS_RESIDENT_BUDGET_MB: resident copies hold at most this (0: free memory)
     bool ra_packed = true;           // IRIS_READAHEAD_PACKED=0: masks read-ahead rows cross the host link unpacked
     uint32_t ra_window_max = 0;      // IRIS_READAHEAD_WINDOW_MAX=1..1024: cap of a read-ahead window, chunks (0: by records)
-    bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches and match passes never register as guests
+    bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches, match and top-k passes never register as guests
     uint32_t search_share_delay_us = 0;  // IRIS_SEARCH_SHARE_DELAY_US: device-stream spin ahead of a pass that can host
     bool search_share_even = false;  // IRIS_SEARCH_SHARE_EVEN=1: a pass that is nobody's guest sees no guest in odd tile groups
     uint32_t ignored = 0;            // bit i: test hook kHookNames[i] was set without IRIS_TEST_HOOKS=1
@@ -285,7 +285,7 @@ struct GuestSlot {
     const void *frag;   // the guest's query fragments (a buffer of the sharing ring, not the engine's)
     Partial *partials;  // the guest's partials buffer (a search)
     uint32_t *done;     // the guest's done array, one word per workgroup
-    MatchSink sink;     // the guest's sink (a match pass: its counter is zeroed ahead of the publish)
+    MatchSink sink;     // the guest's sink (a match pass: its counter is zeroed ahead of the publish; a top-k pass: topk_sink)
 };
 // whether a range runs the form that can share: 4 tiles per wave, no K-split, separate reduce
 bool share_search_ok(const Hooks &h, LaunchRange r);
@@ -301,6 +301,14 @@ int launch_template_share_search(const Hooks &h, void *stream, const void *db, c
 int launch_template_share_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
                                 const MatchSink &ms, const GuestSlot *slot, const uint32_t *own_done,
                                 unsigned long long *count);
+// The sharing form of iris_template_topk_async (the same ranges, slot, own_done and count): every
+// wave stores its k best of the tile group at unit blockIdx.x * 4 + wave of ts (topk_sink) -- the
+// units launch_template_mfma_topk numbers, mfma_topk_units(h, r) of them -- and the guest's at the
+// same unit of its slot's sink (topk_sink(lists, k): k may differ).  A top-k pass hosts top-k passes only.
+int launch_template_share_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                               const MatchSink &ts, const GuestSlot *slot, const uint32_t *own_done,
+                               unsigned long long *count);
+// a match pass's registration, and a top-k pass's (sink = topk_sink(lists, k))
 int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done);
 // zeroes a pass's guest slot and, if given, its done array of n words
 int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n);

@@ -512,6 +512,45 @@ __device__ __forceinline__ void round_matches(const v16f (&den)[NQ][T], const v1
     }
 }
 
+// The top-k form's epilogue of a round: each query's candidates of the T tiles from tw (half 0 of
+// the wave votes, den = 0 otherwise, as in template_mfma_kernel<MF_TOPK>) go into that query's
+// wave-resident list, list[qi] being this lane's entry.  A query's T candidates are formed first, so
+// its accumulators are dead when the inserts run.
+struct GlobalLists {
+    GlobalPartial buf;  // lists[units][k]
+    uint32_t k;
+};
+template <int NQ, int T>
+__device__ __forceinline__ void round_topk(const v16f (&den)[NQ][T], const v16f (&s)[NQ][T], uint64_t tile0,
+                                           uint64_t ntiles, uint64_t tw, uint64_t first, uint64_t end, int lane,
+                                           const uint32_t (&k)[NQ], Partial (&list)[NQ]) {
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) {
+        uint32_t hn[T], hd[T];
+        int hr[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+            const bool valid = (tw + t < ntiles) && tg >= first && tg < end;
+            best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
+                dd = (uint32_t)den[qi][t][r];
+                nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);  // num = (den - S) / 2
+            }, hn[t], hd[t], hr[t]);
+            if (!(valid && (lane >> 5) == 0)) hd[t] = 0;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            Partial c;
+            c.num = hn[t];
+            c.den = hd[t];
+            c.rot = hr[t];
+            c.pad = 0;
+            c.idx = (tile0 + tw + t) * kTileRecs + (lane & 31) - first;
+            topk_insert(list[qi], k[qi], lane, c, true);
+        }
+    }
+}
+
 template <int NQ, int T, class Epi>
 __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[NQ], uint64_t tile0,
                                             uint64_t ntiles, uint64_t tw, int lane, Epi &&epi) {
@@ -715,19 +754,24 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
     }
 }
 
-// The pass of iris_template_search_async and iris_template_matches_async over large TILES ranges (4
-// tiles per wave; the search with its separate reduce).  Each workgroup decides at its start, from
-// words another stream may write while the pass runs: its tile group was computed for this query
-// by the pass that hosted it (own_done) -> nothing to do; a guest has been published in the slot
-// -> both queries for the workgroup's 16 tiles in the two-query shape (2 tiles x 2 queries per
-// wave, twice), both queries' results, then the guest's done word; else the single-query pass.
-//   MATCH = false: `out` is the partials array, and a workgroup's results are one Partial per query
-// (the guest's into slot->partials).  MATCH = true: `out` is the query's MatchSink, and every round
+// The pass of iris_template_search_async, iris_template_matches_async and iris_template_topk_async
+// over large TILES ranges (4 tiles per wave; the search with its separate reduce).  Each workgroup
+// decides at its start, from words another stream may write while the pass runs: its tile group was
+// computed for this query by the pass that hosted it (own_done) -> nothing to do; a guest has been
+// published in the slot -> both queries for the workgroup's 16 tiles in the two-query shape (2
+// tiles x 2 queries per wave, twice), both queries' results, then the guest's done word; else the
+// single-query pass.
+//   SH_SEARCH: `out` is the partials array, and a workgroup's results are one Partial per query
+// (the guest's into slot->partials).  SH_MATCH: `out` is the query's MatchSink, and every round
 // appends its hits to it and, in the two-query shape, the guest's hits to slot->sink; a tile group
 // is appended for a query by exactly one workgroup -- the hosting pass's, which then sets the done
-// word, or else the query's own -- so the counters stay exact.
+// word, or else the query's own -- so the counters stay exact.  SH_TOPK: `out` is the query's
+// topk_sink, the guest's is slot->sink (k may differ); every wave keeps one sorted list per query
+// over its 4 tiles (round_topk) and stores it, empty or not, at unit blockIdx.x * kWaveSlots +
+// wslot of that query's lists -- the unit template_mfma_kernel<MF_TOPK> numbers -- so each unit of
+// a query's lists is written exactly once, by the hosting pass or by the query's own launch.
 //   Memory order: only the slot is written while the pass runs.  The done words and whatever a
-// pass writes for its guest (partials; records and counter adds, the adds agent-scope relaxed) are
+// pass writes for its guest (partials; records and counter adds, the adds agent-scope relaxed; lists) are
 // read by the guest's own launch and what follows it on the device stream, so the end of the
 // kernel publishes them: they are plain stores, and own_done is read relaxed.  (An agent-scope
 // release store per tile group wrote the XCD's L2 back 19 532 times a pass, 0.43 ms of a 7.8-ms
@@ -735,16 +779,20 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
 // fragments.)  `ready` is read relaxed, and only a workgroup that finds it set pays the acquire,
 // ahead of the slot's fields and the guest's fragments.
 // even_only (test hook): the guest counts as not visible in odd tile groups.
-template <bool MATCH>
+// (ints, not an unnamed enum: MODE == SH_SEARCH is part of the kernel's mangled name, and host and
+// device passes number unnamed types differently)
+constexpr int SH_SEARCH = 0, SH_MATCH = 1, SH_TOPK = 2;
+template <int MODE>
 __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     template_share_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, uint64_t tile0, uint64_t ntiles,
-                          uint64_t first, uint64_t end, std::conditional_t<MATCH, MatchSink, Partial *__restrict__> out,
+                          uint64_t first, uint64_t end,
+                          std::conditional_t<MODE == SH_SEARCH, Partial *__restrict__, MatchSink> out,
                           const GuestSlot *slot, const uint32_t *own_done, unsigned long long *count,
                           uint32_t even_only) {
     // one thread reads the words (agent-scope atomics: a plain load could be served from the scalar
     // cache) and the slot's fields behind them; LDS makes the decision the same for every wave
     __shared__ uint32_t sh_flag[2];
-    __shared__ uint64_t sh_guest[MATCH ? 6 : 3];
+    __shared__ uint64_t sh_guest[MODE == SH_MATCH ? 6 : MODE == SH_TOPK ? 4 : 3];
     if (threadIdx.x == 0) {
         const uint32_t dn =
             own_done ? __hip_atomic_load(own_done + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -755,7 +803,10 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             sh_guest[0] = (uint64_t)slot->frag;
             sh_guest[2] = (uint64_t)slot->done;
-            if constexpr (MATCH) {
+            if constexpr (MODE == SH_TOPK) {
+                sh_guest[1] = (uint64_t)slot->sink.buf;
+                sh_guest[3] = slot->sink.cap;
+            } else if constexpr (MODE == SH_MATCH) {
                 sh_guest[1] = (uint64_t)slot->sink.buf;
                 sh_guest[3] = slot->sink.cap;
                 sh_guest[4] = (uint64_t)slot->sink.count;
@@ -781,7 +832,51 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     constexpr int kRounds = kMfmaTiles / 2;
     __shared__ FragRing sh_ring;  // the two-query rounds' operands (static: a solo workgroup holds it too)
     typedef __attribute__((address_space(1))) uint32_t *GlobalWord;
-    if constexpr (MATCH) {
+    if constexpr (MODE == SH_TOPK) {
+        const uint64_t unit = (uint64_t)blockIdx.x * kWaveSlots + wslot;
+        const GlobalLists own{(GlobalPartial)out.buf, (uint32_t)out.cap};
+        if (!shared) {
+            const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
+            const uint32_t k[1] = {own.k};
+            Partial list[1] = {partial_none()};
+            share_round<1, kMfmaTiles>(db, qf, tile0, ntiles, tw, lane, [&](const auto &den, const auto &s) {
+                round_topk<1, kMfmaTiles>(den, s, tile0, ntiles, tw, first, end, lane, k, list);
+            });
+            topk_store_lists(own, unit, lane, list[0]);
+            return;
+        }
+        const GlobalFrag qf[2] = {(GlobalFrag)qfrag, (GlobalFrag)uniform64(sh_guest[0])};
+        const GlobalLists guest{(GlobalPartial)uniform64(sh_guest[1]),
+                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sh_guest[3])};
+        const GlobalWord guest_done = (GlobalWord)uniform64(sh_guest[2]);
+        const uint32_t k[2] = {own.k, guest.k};
+        // the two lists wait in LDS while the next round streams (resident, their 10 VGPRs spill:
+        // 256 VGPRs and 12 B of scratch); each lane reads back the entry it wrote, so no barrier
+        __shared__ Partial sh_list[kWaveSlots][2][64];
+        Partial list[2] = {partial_none(), partial_none()};
+#pragma unroll
+        for (int rd = 0; rd < kRounds; ++rd) {
+            staged_round<kStagedDepth>(db, qf, tile0, ntiles, tw + 2 * rd, lane, wslot, sh_ring,
+                                       [&](const auto &den, const auto &s) {
+                                           if (rd > 0) {
+                                               list[0] = sh_list[wslot][0][lane];
+                                               list[1] = sh_list[wslot][1][lane];
+                                           }
+                                           round_topk<2, 2>(den, s, tile0, ntiles, tw + 2 * rd, first, end, lane, k, list);
+                                       });
+            if (rd + 1 < kRounds) {
+                sh_list[wslot][0][lane] = list[0];
+                sh_list[wslot][1][lane] = list[1];
+            }
+        }
+        topk_store_lists(own, unit, lane, list[0]);
+        topk_store_lists(guest, unit, lane, list[1]);
+        __syncthreads();  // every wave has stored the guest's list: only then is its tile group done
+        if (threadIdx.x == 1) {
+            __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (count) atomicAdd(count, 1ull);
+        }
+    } else if constexpr (MODE == SH_MATCH) {
         typedef __attribute__((address_space(1))) uint64_t *GlobalCount;
         const GlobalSink own{(GlobalPartial)out.buf, out.cap, (GlobalCount)out.count, out.threshold};
         if (!shared) {
@@ -854,7 +949,8 @@ __global__ void share_publish_kernel(GuestSlot *slot, const void *frag, Partial 
     __hip_atomic_store(&slot->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// a match pass's registration: the guest's sink in place of its partials
+// a match or top-k pass's registration: the guest's sink (a top-k pass: topk_sink(lists, k)) in place
+// of its partials
 __global__ void share_publish_match_kernel(GuestSlot *slot, const void *frag, MatchSink sink, uint32_t *done) {
     slot->frag = frag;
     slot->sink = sink;
@@ -1078,7 +1174,7 @@ int launch_template_share_search(const Hooks &h, void *stream, const void *db, c
     // test hook: a pass that is nobody's guest carries its guest in even tile groups only (the
     // guest's own launch then computes the odd ones, and carries its own guest there)
     const bool even_only = h.search_share_even && !own_done;
-    hipLaunchKernelGGL(template_share_kernel<false>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
+    hipLaunchKernelGGL(template_share_kernel<SH_SEARCH>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
                        (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
                        r.first + r.n, partials, slot, own_done, count, (uint32_t)even_only);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1090,9 +1186,21 @@ int launch_template_share_match(const Hooks &h, void *stream, const void *db, co
     if (!share_search_ok(h, r)) return -1;  // the caller asks first
     const TileRange t = search_range(h, r);
     const bool even_only = h.search_share_even && !own_done;  // as the search's
-    hipLaunchKernelGGL(template_share_kernel<true>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
+    hipLaunchKernelGGL(template_share_kernel<SH_MATCH>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
                        (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
                        r.first + r.n, ms, slot, own_done, count, (uint32_t)even_only);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_template_share_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                               const MatchSink &ts, const GuestSlot *slot, const uint32_t *own_done,
+                               unsigned long long *count) {
+    if (!share_search_ok(h, r)) return -1;  // the caller asks first
+    const TileRange t = search_range(h, r);
+    const bool even_only = h.search_share_even && !own_done;  // as the search's
+    hipLaunchKernelGGL(template_share_kernel<SH_TOPK>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
+                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
+                       r.first + r.n, ts, slot, own_done, count, (uint32_t)even_only);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -196,6 +196,8 @@ def load_library(path=None):
                                              ctypes.POINTER(u64)], ctypes.c_int),
             "iris_template_topk": ([P, P, u64, u64, u64, ctypes.c_uint32, ctypes.POINTER(Match),
                                     ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "iris_template_topk_async": ([P, P, u64, u64, u64, ctypes.c_uint32, PP], ctypes.c_int),
+            "iris_pending_topk_wait": ([P, ctypes.POINTER(Match), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_resolver_topk": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.c_uint32,
                                     ctypes.POINTER(Match), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_resolver_topk_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.c_uint32,
@@ -278,6 +280,7 @@ def exported_symbols():
         "iris_template_matches", "iris_resolver_matches", "iris_resolver_matches_masks",
         "iris_resolver_batch_matches_masks", "iris_template_batch_matches",
         "iris_template_matches_async", "iris_pending_matches_wait",
+        "iris_template_topk_async", "iris_pending_topk_wait",
         "iris_template_topk", "iris_resolver_topk", "iris_resolver_topk_masks", "iris_topk_merge",
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
     ]
@@ -1157,6 +1160,39 @@ class TemplateEngine(_Engine):
                                               o, cnt), k)
 
 
+    def topk_async(self, db, k, first=0, n=None, index_base=0):
+        """Enqueue topk() and return at once (iris_template_topk_async) -> PendingTopk, whose
+        wait() returns what topk() with the same arguments returns.  The engine may be closed
+        before the wait; the database stays alive and unmodified until it."""
+        n = (len(db) - first) if n is None else n
+        h = ctypes.c_void_p()
+        _check(load_library().iris_template_topk_async(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                       int(k), ctypes.byref(h)))
+        return PendingTopk(h, int(k))
+
+
+class PendingTopk:
+    """An enqueued top-k pass (TemplateEngine.topk_async); wait() -> list[Match], once."""
+
+    def __init__(self, handle, k):
+        self.handle = handle
+        self.k = k
+
+    def wait(self):
+        if self.handle is None:
+            raise IrisError(-1, "PendingTopk.wait called twice")
+        h, self.handle = self.handle, None
+        f = load_library().iris_pending_topk_wait
+        return _collect_topk(lambda o, cnt: f(h, o, cnt), self.k)
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                load_library().iris_pending_topk_wait(self.handle, None, ctypes.byref(ctypes.c_uint32()))
+            except Exception:
+                pass
+
+
 class PendingSearch:
     """An enqueued search (TemplateEngine.search_async); wait() -> Match, once."""
 
@@ -1724,7 +1760,7 @@ def f64_bits(x):
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
     "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "TOPK_MAX", "dot_bool", "dot_u16",
-    "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches",
+    "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
     "ROTATIONS", "BITS", "LIMBS", "COLS", "ROWS",
