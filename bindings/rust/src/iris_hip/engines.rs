@@ -639,6 +639,19 @@ impl TemplateEngine {
         })
     }
 
+    /// The distribution of the distances of [first, first + n) in one database pass
+    /// (iris_template_histogram; no reference counterpart) -> (bins, invalid): a record is counted
+    /// in bin `min(nbins - 1, floor(distance * nbins))`, one without a valid rotation in `invalid`
+    /// alone.  `nbins` is a power of two up to `ffi::IRIS_HIST_MAX_BINS`; histograms of chunks add.
+    pub fn histogram(&self, db: &Database, first: u64, n: u64, nbins: u32) -> Result<(Vec<u64>, u64)> {
+        let mut bins = vec![0u64; nbins.clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize];
+        let mut invalid = 0u64;
+        check(unsafe {
+            ffi::iris_template_histogram(self.h.raw, db.raw(), first, n, nbins, bins.as_mut_ptr(), &mut invalid)
+        })?;
+        Ok((bins, invalid))
+    }
+
     /// Enqueues `topk` and returns at once (iris_template_topk_async): a pass still running may
     /// compute the next one submitted.  The engine may be dropped before the wait; the database
     /// must outlive it, unmodified.
@@ -772,6 +785,31 @@ impl TemplateBatchEngine {
             .iter()
             .enumerate()
             .map(|(q, &c)| buf[q * room..q * room + c as usize].iter().map(match_to_pair).collect())
+            .collect())
+    }
+
+    /// Every query's distance histogram of [first, first + n) in one pass over the templates
+    /// (iris_template_batch_histogram): entry q is what `TemplateEngine::histogram` gives for
+    /// query q.
+    pub fn batch_histogram(&self, db: &Database, first: u64, n: u64, nbins: u32) -> Result<Vec<(Vec<u64>, u64)>> {
+        let room = nbins.clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize;
+        let mut bins = vec![0u64; self.nq * room];
+        let mut invalid = vec![0u64; self.nq];
+        check(unsafe {
+            ffi::iris_template_batch_histogram(
+                self.h.raw,
+                db.raw(),
+                first,
+                n,
+                nbins,
+                bins.as_mut_ptr(),
+                invalid.as_mut_ptr(),
+            )
+        })?;
+        Ok(invalid
+            .iter()
+            .enumerate()
+            .map(|(q, &inv)| (bins[q * room..(q + 1) * room].to_vec(), inv))
             .collect())
     }
 }

@@ -17,6 +17,7 @@ pub const IRIS_LIMBS: usize = 200;
 pub const IRIS_ROTATIONS: usize = 31;
 pub const IRIS_MAX_ROTATION: i32 = 15;
 pub const IRIS_TOPK_MAX: u32 = 64;
+pub const IRIS_HIST_MAX_BINS: u32 = 1024;
 
 /// Status codes.
 pub const IRIS_OK: c_int = 0;
@@ -400,6 +401,26 @@ extern "C" {
         k: u32,
         out: *mut IrisMatch,
         count: *mut u32,
+    ) -> c_int;
+    // histograms: a range's distance distribution in one pass (no reference counterpart; nbins is a
+    // power of two in 1..IRIS_HIST_MAX_BINS, bins and invalid are overwritten)
+    pub fn iris_template_histogram(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        nbins: u32,
+        bins: *mut u64,
+        invalid: *mut u64,
+    ) -> c_int;
+    pub fn iris_template_batch_histogram(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        nbins: u32,
+        bins: *mut u64,
+        invalid: *mut u64,
     ) -> c_int;
     // threshold matching: every record below a distance (no reference counterpart for the threshold)
     pub fn iris_template_matches(

@@ -694,6 +694,57 @@ int iris_template_topk_async(iris_engine_t *engine, const iris_db_t *db, uint64_
 int iris_pending_topk_wait(iris_pending_t *pending /* an iris_pending_topk_t */, iris_match_t *out,
                            uint32_t *count);
 
+/* -------------------------------------------------------------- histograms
+ * The distribution of a range's distances in one database pass -- the impostor score histogram a
+ * false-match rate is read from, and so the answer to where a threshold belongs before
+ * iris_template_matches can use one.  The reference has no counterpart; the loops generalised are
+ * the search's: src/template.rs:43-47 per record, src/main.rs:616-621 over records, with "count it
+ * in its bin" in place of "keep the minimum".
+ *
+ * Distance: a record's distance is the f64 the sibling search would report if that record were
+ * alone in the range, (double)num / (double)den of its best rotation (exact fraction minimum,
+ * lowest rotation on ties).  Binning: a record with a valid rotation is counted in bin
+ * min(nbins - 1, floor(distance * nbins)), so bin j covers [j/nbins, (j+1)/nbins) and the last bin
+ * also takes distance 1.0.  A record without a valid rotation (every den == 0, distance +inf) is
+ * counted in *invalid and in no bin: sum(bins) + *invalid == n, always.
+ *
+ * nbins: a power of two in 1..IRIS_HIST_MAX_BINS (IRIS_E_ARG otherwise).  A power of two makes
+ * distance * nbins exact in f64, and two things follow:
+ *   1. the prefix sum bins[0] + ... + bins[j-1] equals, exactly, the total iris_template_matches
+ *      reports for threshold = (double)j / nbins over the same range;
+ *   2. the bin equals the integer floor(num * nbins / den) (the product stays below 2^24), which
+ *      is what the device computes: no f64 division per record.
+ *
+ * bins (nbins uint64_t) and invalid are required host pointers.  The call OVERWRITES them, it does
+ * not accumulate: histograms of chunks, shards or GPUs add, so a caller sums them itself.  n == 0
+ * writes zeros; a refused call leaves both untouched.  Counts are integers and their sum does not
+ * depend on the order of the additions, so identical calls return identical bytes.
+ *
+ * The value arguments (nbins, bins, invalid) are checked before the handles; engine-kind,
+ * database, layout and range checks and the locking are the sibling search's.  The single-query
+ * call refuses a batch engine; the batch call has iris_template_batch_matches' checks (more than 3
+ * queries need a TILES database).  The bytes copied back per call are 8 (nbins + 1) per query,
+ * whatever n is.
+ *
+ * Out of scope: the resolver forms and the masks batch form (the natural follow-up, from the
+ * resolver's decode); the pipelined and device-group forms (histograms add: a caller sums its
+ * shards); host-array forms; bin counts that are not a power of two and caller-given edges;
+ * weighted counts; more than 1024 bins (the batched kernel keeps four queries' histograms in LDS
+ * beside its 128-KiB fragment ring: 16 KiB at 1024 bins fit the CU's 160 KiB, 64 KiB at 4096 do
+ * not). */
+#define IRIS_HIST_MAX_BINS 1024u
+/* iris_template_search's sibling: the distribution of the distances that search folds a minimum of */
+int iris_template_histogram(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                            uint32_t nbins, uint64_t *bins /* [nbins] */, uint64_t *invalid);
+/* iris_template_batch_search's sibling, for a template batch engine: one histogram per query in
+ * one pass.  bins: nq*nbins uint64_t, query-major; invalid: nq uint64_t.  Contract: histogram q and
+ * invalid[q] are byte for byte what iris_template_histogram returns for TemplateEngine(queries[q])
+ * over the same range.  More than 3 queries run one pass of the batched GEMM, every workgroup
+ * keeping its queries' histograms in LDS across its walk; up to 3 run iris_template_histogram's own
+ * pass each.  The call waits once. */
+int iris_template_batch_histogram(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                                  uint32_t nbins, uint64_t *bins /* [nq][nbins] */, uint64_t *invalid /* [nq] */);
+
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):
  *   dot_bool(&[u64;200], &[u64;200]) -> u16   src/arch/generic.rs:4-9

@@ -58,6 +58,12 @@ struct Matches {
     uint64_t count = 0;
 };
 constexpr uint64_t kAllMatches = UINT64_MAX;  // cap: return every match
+// Result of a histogram call (iris_*_histogram): bins[j] = records whose distance lies in
+// [j/nbins, (j+1)/nbins) (the last bin takes 1.0 too), invalid = records without a valid rotation.
+struct Histogram {
+    std::vector<uint64_t> bins;
+    uint64_t invalid = 0;
+};
 
 class Error : public std::runtime_error {
 public:
@@ -771,6 +777,16 @@ public:
             return iris_template_topk(h_, db.handle(), first, n, index_base, k, out, count);
         });
     }
+    // The distribution of the range's distances in one database pass (iris_template_histogram; no
+    // reference counterpart): bins[j] counts the records with min(nbins - 1, floor(distance * nbins))
+    // == j, invalid those without a valid rotation; nbins is a power of two up to IRIS_HIST_MAX_BINS.
+    // Histograms of chunks add.
+    Histogram histogram(const Database &db, uint32_t nbins, uint64_t first, uint64_t n) const {
+        Histogram res;
+        res.bins.assign(nbins && nbins <= IRIS_HIST_MAX_BINS ? nbins : 1, 0);
+        check(iris_template_histogram(h_, db.handle(), first, n, nbins, res.bins.data(), &res.invalid));
+        return res;
+    }
     // pipelined form: returns once the search is enqueued (the engine may be destroyed before the wait)
     PendingSearch search_async(const Database &db, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
         iris_pending_t *p = nullptr;
@@ -859,6 +875,19 @@ public:
         check(iris_template_batch_topk(h_, db.handle(), first, n, index_base, k, flat.data(), counts.data()));
         std::vector<std::vector<Match>> res(nq_);
         for (uint32_t q = 0; q < nq_; ++q) res[q].assign(flat.begin() + (size_t)q * room, flat.begin() + (size_t)q * room + counts[q]);
+        return res;
+    }
+    // Every query's distance histogram in one pass over the templates (iris_template_batch_histogram):
+    // result[q] is what TemplateEngine(queries[q]).histogram gives over the same range.
+    std::vector<Histogram> histogram(const Database &db, uint32_t nbins, uint64_t first, uint64_t n) const {
+        const uint32_t room = nbins && nbins <= IRIS_HIST_MAX_BINS ? nbins : 1;
+        std::vector<uint64_t> flat((size_t)nq_ * room), invalid(nq_);
+        check(iris_template_batch_histogram(h_, db.handle(), first, n, nbins, flat.data(), invalid.data()));
+        std::vector<Histogram> res(nq_);
+        for (uint32_t q = 0; q < nq_; ++q) {
+            res[q].bins.assign(flat.begin() + (size_t)q * room, flat.begin() + (size_t)(q + 1) * room);
+            res[q].invalid = invalid[q];
+        }
         return res;
     }
 

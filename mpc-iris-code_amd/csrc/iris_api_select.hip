@@ -1,6 +1,7 @@
 // iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
-// and batched, with the runners that turn launch units into match lists, and the pipelined forms of
-// the single-query template match and top-k.  Calls, locking and errors: see iris_api.hip.
+// and batched, with the runners that turn launch units into match lists, the pipelined forms of
+// the single-query template match and top-k, and the distance histograms of the template engines.
+// Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
 #include <new>
@@ -974,6 +975,131 @@ int iris_template_batch_topk(iris_engine_t *e, const iris_db_t *db, uint64_t fir
         }, geo.nqg * geo.qper - nq});
     }
     return topk_run_units(d, n, base, k, out, counts, nq, units);
+}
+
+// ------------------------------------------------------------------ histograms
+
+static int hist_args(uint32_t nbins, const uint64_t *bins, const uint64_t *invalid) {
+    ARG(nbins >= 1 && nbins <= IRIS_HIST_MAX_BINS && (nbins & (nbins - 1)) == 0,
+        "nbins must be a power of two in 1..IRIS_HIST_MAX_BINS (1024)");
+    ARG(bins, "bins is NULL");
+    ARG(invalid, "invalid is NULL");
+    return 0;
+}
+
+// The nq rows of nbins + 1 counters in the pinned host result (bins, then the invalid count) ->
+// the caller's arrays, once every row adds up to the range: nothing is written before that.
+static int hist_finish(iris_device *d, uint64_t n, uint32_t nbins, uint32_t nq, uint64_t *bins, uint64_t *invalid) {
+    const uint64_t *res = (const uint64_t *)d->host_result;
+    const size_t words = (size_t)nbins + 1;
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint64_t sum = 0;
+        for (size_t i = 0; i < words; ++i) sum += res[q * words + i];
+        if (sum != n) return fail(IRIS_E_HIP, "histogram pass did not count every record of the range once");
+    }
+    for (uint32_t q = 0; q < nq; ++q) {
+        memcpy(bins + (size_t)q * nbins, res + q * words, nbins * sizeof(uint64_t));
+        invalid[q] = res[q * words + nbins];
+    }
+    return 0;
+}
+
+// One histogram call of nq single-query passes over n records (iris_template_histogram: nq = 1; a
+// batch engine of up to kBatchStreamMax queries).  Query q has `copies` copies of its nbins + 1
+// counters in the device's counter buffer, all zeroed on the stream first; its pass -- launch(q,
+// sink), timed as "template_hist" -- adds every workgroup's LDS histogram to copy
+// blockIdx.x % copies, "hist_reduce" sums the copies straight into the pinned host result, and the
+// call waits once.  copies = 1 (the IRIS_HIST_COPIES=1 test hook): the passes add into the result
+// itself and a copy brings it back (DESIGN.md 4.17 has both measured).  A histogram always fits, so
+// there is no second pass.
+static int hist_run(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, uint64_t *invalid, uint32_t nq,
+                    const std::function<int(uint32_t, const MatchSink &)> &launch) {
+    if (n == 0) {
+        memset(bins, 0, (size_t)nq * nbins * sizeof(uint64_t));
+        memset(invalid, 0, nq * sizeof(uint64_t));
+        return 0;
+    }
+    const uint32_t words = nbins + 1, copies = d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
+    const size_t row = (size_t)copies * words;
+    CHK(ensure(d, d->match_count, nq * row * sizeof(uint64_t)));
+    CHK(ensure_host_result(d, (size_t)nq * words * sizeof(uint64_t)));
+    uint64_t *cnt = (uint64_t *)d->match_count.p;
+    HIPCHK(hipMemsetAsync(cnt, 0, nq * row * sizeof(uint64_t), d->stream));
+    for (uint32_t q = 0; q < nq; ++q)
+        CHK(timed(d, "template_hist", n, [&] { return launch(q, hist_sink(cnt + q * row, nbins, copies)); }));
+    if (copies > 1)
+        CHK(timed(d, "hist_reduce", nq * row, [&] {
+            return launch_hist_reduce(d->stream, cnt, words, copies, nq, (uint64_t *)d->host_result);
+        }));
+    else
+        HIPCHK(hipMemcpyAsync(d->host_result, cnt, (size_t)nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+    CHK(sync(d));
+    return hist_finish(d, n, nbins, nq, bins, invalid);
+}
+
+// iris_template_search's histogram sibling (header: "histograms")
+int iris_template_histogram(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint32_t nbins,
+                            uint64_t *bins, uint64_t *invalid) {
+    IRIS_KEEP_DEVICE();
+    CHK(hist_args(nbins, bins, invalid));  // the value arguments first: refused whatever the handles
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    return hist_run(d, n, nbins, bins, invalid, 1, [&](uint32_t, const MatchSink &hs) {
+        return db->k.layout == IRIS_LAYOUT_TILES ? launch_template_mfma_hist(d->hooks, d->stream, db->data, e->qfrag, r, hs)
+                                                 : launch_template_hist(d->stream, db->data, e->qtab, r, hs);
+    });
+}
+
+// iris_template_batch_search's histogram sibling, with iris_template_batch_matches' checks and
+// dispatch.  Engines of up to kBatchStreamMax queries: one single-query histogram pass per query
+// ("template_hist"), all enqueued before the one wait.  The GEMM: one launch of
+// batch_lds_kernel<..., BL_HIST> ("template_batch_hist") over all query groups; a workgroup adds its
+// queries' LDS histograms once, after its walk, straight into the rows of the device's counter
+// buffer -- one row per padded query, the padding queries' rows ignored -- and a copy brings the nq
+// rows back.
+int iris_template_batch_histogram(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint32_t nbins,
+                                  uint64_t *bins, uint64_t *invalid) {
+    IRIS_KEEP_DEVICE();
+    CHK(hist_args(nbins, bins, invalid));  // the value arguments first: refused whatever the handles
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
+    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
+    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
+        "batched search of more than 3 queries needs a template database in the TILES layout");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const uint32_t nq = e->nq;
+    const LaunchRange r{first, n};
+    if (!e->sub.empty())
+        return hist_run(d, n, nbins, bins, invalid, nq, [&](uint32_t q, const MatchSink &hs) {
+            const iris_engine *c = e->sub[q];
+            return db->k.layout == IRIS_LAYOUT_TILES
+                       ? launch_template_mfma_hist(d->hooks, d->stream, db->data, c->qfrag, r, hs)
+                       : launch_template_hist(d->stream, db->data, c->qtab, r, hs);
+        });
+    if (n == 0) {
+        memset(bins, 0, (size_t)nq * nbins * sizeof(uint64_t));
+        memset(invalid, 0, nq * sizeof(uint64_t));
+        return 0;
+    }
+    const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
+    const size_t words = (size_t)nbins + 1, rows = (size_t)geo.nqg * geo.qper;
+    CHK(ensure(d, d->match_count, rows * words * sizeof(uint64_t)));
+    CHK(ensure_host_result(d, nq * words * sizeof(uint64_t)));
+    uint64_t *cnt = (uint64_t *)d->match_count.p;
+    HIPCHK(hipMemsetAsync(cnt, 0, rows * words * sizeof(uint64_t), d->stream));
+    CHK(timed(d, "template_batch_hist", n * nq,
+              [&] { return launch_batch_hist(d->hooks, d->stream, db->data, e->qfrag, r, geo, cnt, nbins); }));
+    HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+    CHK(sync(d));
+    return hist_finish(d, n, nbins, nq, bins, invalid);
 }
 
 }  // extern "C"

@@ -102,7 +102,20 @@ __global__ void __launch_bounds__(256) batch_reduce_kernel(const Partial *__rest
 // stores: query q's at outp.lists + q * outp.stride + unit * outp.k, unit = gi * (NW / QW) + tset,
 // (NW / QW) * G lists per query.  A padding query's zero tile gives den = 0 in every row, so its
 // lists stay empty.  No shuffle reduction, no LDS hand-off, no partials and no reduce.
-enum { BL_SEARCH = 0, BL_MATCH = 1, BL_TOPK = 2 };
+//
+// BL_HIST (iris_template_batch_histogram): the match form up to each (query, tile)'s best rotation;
+// half 0 then counts the record in the workgroup's LDS histogram of that query ([BQL][nbins + 1] u32
+// beside the fragment ring, resident across all the workgroup's N-groups; hist_count, iris_device.hpp).
+// The histograms are zeroed ahead of a barrier before the walk and, behind a barrier after it, their
+// non-zero words are added to row qg * BQL + query of outp.counts.  Both barriers stand outside the
+// walk, where every wave of every workgroup -- staggered or not, with or without an N-group --
+// arrives.  A padding query's zero tile gives den = 0 in every row: its row counts the range as
+// invalid, and the host ignores it.
+enum { BL_SEARCH = 0, BL_MATCH = 1, BL_TOPK = 2, BL_HIST = 3 };
+struct BatchHistRows {
+    uint64_t *counts;  // [query of the launch][nbins + 1], zeroed on the stream before the launch
+    uint32_t nbins;    // a power of two, 1..kHistMaxBins
+};
 struct BatchTopkLists {
     Partial *lists;   // [query of the launch][units + spare][k]
     uint64_t stride;  // records between two queries' lists
@@ -119,6 +132,10 @@ struct BatchOut<BL_MATCH> {
 template <>
 struct BatchOut<BL_TOPK> {
     typedef BatchTopkLists type;
+};
+template <>
+struct BatchOut<BL_HIST> {
+    typedef BatchHistRows type;
 };
 template <int NW, int WT, int WQL, int BQL, int MODE = BL_SEARCH, int GPL = 4>
 __global__ void __launch_bounds__(64 * NW, 1)
@@ -221,6 +238,12 @@ __global__ void __launch_bounds__(64 * NW, 1)
     if constexpr (MODE == BL_TOPK) {
 #pragma unroll
         for (int qi = 0; qi < WQL; ++qi) list[qi] = partial_none();
+    }
+    if constexpr (MODE == BL_HIST) {
+        uint32_t *hist = hist_lds<kBQ>();
+#pragma unroll
+        for (int qi = 0; qi < kBQ; ++qi) hist_zero(hist + qi * (kHistMaxBins + 1), outp.nbins);
+        __syncthreads();
     }
     v16f den[WQL][WT], sacc[WQL][WT];
     auto zero = [&] {
@@ -344,6 +367,28 @@ __global__ void __launch_bounds__(64 * NW, 1)
                 }
 #pragma unroll
                 for (int qi = 0; qi < WQL; ++qi) append_matches<WT>(sink[qi], lane, hit[qi], bn[qi], bd[qi], br[qi], idx);
+            } else if constexpr (MODE == BL_HIST) {
+                // the match form's decision (best_rotation, the same `valid`, half 0 counts)
+#pragma unroll
+                for (int t = 0; t < WT; ++t) {
+                    const uint64_t trel = (gi + (uint64_t)j * G) * kTilesPerGroup + tset * WT + t;
+                    const uint64_t tg = (tile0 + trel) * 32 + (lane & 31);
+                    const bool valid = live && trel < ntiles && tg >= first && tg < end;
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) {
+                        uint32_t bn, bd;
+                        int br;
+                        best_rotation(
+                            lane,
+                            [&](int r, uint32_t &nn, uint32_t &dd) {
+                                dd = (uint32_t)den[qi][t][r];
+                                nn = (uint32_t)(((int)dd - (int)sacc[qi][t][r]) >> 1);
+                            },
+                            bn, bd, br);
+                        hist_count(hist_lds<kBQ>() + (qset * WQL + qi) * (kHistMaxBins + 1), outp.nbins, lane, valid && h == 0,
+                                   bn, bd);
+                    }
+                }
             } else if constexpr (MODE == BL_TOPK) {
                 // the match form's decision (best_rotation, the same `valid`, half 0 proposes), one
                 // (query, tile) at a time: each candidate set goes into its query's list before the
@@ -410,6 +455,13 @@ __global__ void __launch_bounds__(64 * NW, 1)
         barrier();
     }
 
+    if constexpr (MODE == BL_HIST) {
+        __syncthreads();  // outside the walk: a workgroup without an N-group arrives too
+#pragma unroll
+        for (int qi = 0; qi < kBQ; ++qi)
+            hist_flush(hist_lds<kBQ>() + qi * (kHistMaxBins + 1), outp.nbins,
+                       outp.counts + (uint64_t)(qg * kBQ + qi) * (outp.nbins + 1));
+    }
     if constexpr (MODE == BL_TOPK) {
         const uint64_t unit = (uint64_t)gi * (NW / QW) + tset;
 #pragma unroll
@@ -505,6 +557,19 @@ int launch_batch_match(const Hooks &h, void *stream, const void *db, const void 
     auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_MATCH> : batch_lds_kernel<8, 2, 2, 2, BL_MATCH>;
     hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
                        (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G, sinks);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The histogram form of that pass: counts = the device array of g.nqg * g.qper rows of nbins + 1
+// counters.  One launch, no reduce.
+int launch_batch_hist(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                      const BatchGeometry &g, uint64_t *counts, uint32_t nbins) {
+    if (r.n == 0) return 0;
+    if (nbins == 0 || nbins > kHistMaxBins || (nbins & (nbins - 1))) return -1;
+    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_HIST> : batch_lds_kernel<8, 2, 2, 2, BL_HIST>;
+    hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
+                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G,
+                       BatchHistRows{counts, nbins});
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

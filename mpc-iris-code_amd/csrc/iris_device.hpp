@@ -270,6 +270,45 @@ __device__ __forceinline__ void append_matches(const Sink &m, int lane, const bo
     }
 }
 
+// Histograms (iris_*_histogram; hist_sink, iris_internal.hpp).  A workgroup bins its records in an
+// LDS histogram of `nbins` u32 counters and one more word for the records without a valid rotation,
+// and adds the non-zero words to global memory once.  Every wave of the workgroup calls hist_zero,
+// reaches a barrier, counts, reaches a second barrier and calls hist_flush: the callers place both
+// barriers in workgroup-uniform control flow.
+__device__ __forceinline__ uint32_t hist_sink_bins(const MatchSink &m) { return (uint32_t)m.cap; }
+__device__ __forceinline__ uint64_t *hist_sink_copy(const MatchSink &m) {  // this workgroup's copy of the counters
+    return m.count + (uint64_t)(blockIdx.x & (uint32_t)(m.cap >> 32)) * (hist_sink_bins(m) + 1);
+}
+__device__ __forceinline__ void hist_zero(uint32_t *lds, uint32_t nbins) {
+    for (uint32_t i = threadIdx.x; i <= nbins; i += blockDim.x) lds[i] = 0;
+}
+// One record per lane (`counted` lanes only; every lane of the wave calls this).  The bin is the
+// integer floor(num * nbins / den), num <= den <= 12800 and nbins <= 1024 a power of two, so the
+// product is below 2^24 and equals floor of the f64 distance times nbins (the header's rule);
+// distance 1.0 joins the last bin.  den = 0: a ballot counts the wave's invalid records, one add.
+__device__ __forceinline__ void hist_count(uint32_t *lds, uint32_t nbins, int lane, bool counted, uint32_t num,
+                                           uint32_t den) {
+    if (counted && den != 0) {
+        const uint32_t b = num * nbins / den;
+        atomicAdd(&lds[b < nbins ? b : nbins - 1], 1u);
+    }
+    const uint64_t inv = __ballot(counted && den == 0);
+    if (inv != 0 && lane == 0) atomicAdd(&lds[nbins], (uint32_t)__popcll(inv));
+}
+// the workgroup's non-zero words -> dst (agent-scope relaxed u64 adds, as append_matches adds its
+// counter; neighbouring lanes add to neighbouring words)
+__device__ __forceinline__ void hist_flush(const uint32_t *lds, uint32_t nbins, uint64_t *dst) {
+    for (uint32_t i = threadIdx.x; i <= nbins; i += blockDim.x) {
+        const uint32_t v = lds[i];
+        if (v != 0) __hip_atomic_fetch_add(dst + i, (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+template <int Q>
+__device__ __forceinline__ uint32_t *hist_lds() {  // [Q][kHistMaxBins + 1], of the kernels that call it only
+    __shared__ uint32_t h[Q * (kHistMaxBins + 1)];
+    return h;
+}
+
 // Top-k (iris_*_topk).  A wave keeps its best candidates so far as ONE sorted list, entry j in
 // lane j (`entry`; den = 0 is an empty entry, empties last), in the search order of
 // partial_better_dev -- a total order, indices being unique.  It takes the place of the search

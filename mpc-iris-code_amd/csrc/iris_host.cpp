@@ -521,7 +521,7 @@ constexpr const char *kHookNames[] = {"IRIS_TILES_PER_WAVE",  "IRIS_FUSED_REDUCE
                                       "IRIS_GROUP_STALL",     "IRIS_GROUP_UNORDERED", "IRIS_UPLOAD",
                                       "IRIS_LOAD_WINDOWS",    "IRIS_READAHEAD_WINDOW", "IRIS_RESIDENT_BUDGET_MB",
                                       "IRIS_READAHEAD_PACKED", "IRIS_READAHEAD_WINDOW_MAX", "IRIS_SEARCH_SHARE",
-                                      "IRIS_SEARCH_SHARE_DELAY_US", "IRIS_SEARCH_SHARE_EVEN"};
+                                      "IRIS_SEARCH_SHARE_DELAY_US", "IRIS_SEARCH_SHARE_EVEN", "IRIS_HIST_COPIES"};
 constexpr int kNumHooks = (int)(sizeof(kHookNames) / sizeof(kHookNames[0]));
 
 const char *env(const char *name) {
@@ -569,6 +569,11 @@ void read_hooks(Hooks *h) {
         case 14: h->search_share = v[0] != '0'; break;
         case 15: h->search_share_delay_us = env_u32(v, 1000000); break;
         case 16: h->search_share_even = v[0] != '0'; break;
+        case 17: {  // a power of two up to kHistCopies; anything else keeps the default
+            const uint32_t c = env_u32(v, kHistCopies);
+            h->hist_copies = c && !(c & (c - 1)) ? c : 0;
+            break;
+        }
         }
     }
 }
@@ -597,7 +602,8 @@ size_t format_hooks(const Hooks &h, char *buf, size_t len) {
              " upload=" + upload_names[h.upload & 3] +
              " search_share=" + std::to_string(h.search_share) +
              " search_share_delay_us=" + std::to_string(h.search_share_delay_us) +
-             " search_share_even=" + std::to_string(h.search_share_even);
+             " search_share_even=" + std::to_string(h.search_share_even) +
+             " hist_copies=" + (h.hist_copies ? std::to_string(h.hist_copies) : std::string("auto"));
     std::string ign;
     for (int i = 0; i < kNumHooks; ++i)
         if (h.ignored >> i & 1u) ign += (ign.empty() ? "" : ",") + std::string(kHookNames[i]);

@@ -165,6 +165,17 @@ struct MatchSink {
 constexpr uint32_t kTopkMax = 64;    // one list entry per lane
 constexpr uint32_t kTopkFanIn = 64;  // lists one merge workgroup folds into one
 inline MatchSink topk_sink(Partial *lists, uint32_t k) { return MatchSink{lists, k, nullptr, 0.0}; }
+// A histogram pass (iris_*_histogram) takes it as well: count = counters[copies][nbins + 1], u64,
+// zeroed on the stream before the launch, and cap = nbins | (copies - 1) << 32 (both powers of two);
+// buf and threshold are unused.  A workgroup bins its records in LDS (bin = min(nbins - 1,
+// num * nbins / den) of the best rotation, integers: num * nbins < 2^24) and adds its non-zero
+// words to copy blockIdx.x % copies: words 0 .. nbins - 1 the bins, word nbins the records without
+// a valid rotation.  copies = 1 is the result itself; launch_hist_reduce sums more.
+constexpr uint32_t kHistMaxBins = IRIS_HIST_MAX_BINS;
+constexpr uint32_t kHistCopies = 64;  // the flush and its measurement
+inline MatchSink hist_sink(uint64_t *counters, uint32_t nbins, uint32_t copies) {
+    return MatchSink{nullptr, (uint64_t)nbins | (uint64_t)(copies - 1) << 32, counters, 0.0};
+}
 
 // ---------------------------------------------------------------- generator
 // Counter-based synthetic data: limb = splitmix64 output number
@@ -213,6 +224,7 @@ struct Hooks {
     bool search_share = true;        // IRIS_SEARCH_SHARE=0: asynchronous searches, match and top-k passes never register as guests
     uint32_t search_share_delay_us = 0;  // IRIS_SEARCH_SHARE_DELAY_US: device-stream spin ahead of a pass that can host
     bool search_share_even = false;  // IRIS_SEARCH_SHARE_EVEN=1: a pass that is nobody's guest sees no guest in odd tile groups
+    uint32_t hist_copies = 0;        // IRIS_HIST_COPIES=1|2|..|64: counter copies of a histogram pass (0: kHistCopies; 1: straight into the result)
     uint32_t ignored = 0;            // bit i: test hook kHookNames[i] was set without IRIS_TEST_HOOKS=1
 };
 // The bound of forming a device group when IRIS_GROUP_TIMEOUT_MS is not set (iris_group.hip)
@@ -369,6 +381,14 @@ int launch_resolver_topk(void *stream, const uint16_t *const *shares, uint32_t p
                          const MatchSink &ts);
 int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
                       const uint16_t *const *shares, uint32_t parts, const MatchSink &ts);
+// Histogram passes (iris_*_histogram): the sibling search's streaming loop and dispatch with the
+// LDS histogram as epilogue; hs = hist_sink(counters, nbins, copies), the counters zeroed on the
+// stream by the caller.  No partials and no second pass: a histogram always fits.
+int launch_template_mfma_hist(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                              const MatchSink &hs);
+int launch_template_hist(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &hs);
+// dst[q][i] = sum over c < copies of src[q][c][i], q < nq, i < words (dst: device or pinned host memory)
+int launch_hist_reduce(void *stream, const uint64_t *src, uint32_t words, uint32_t copies, uint32_t nq, uint64_t *dst);
 inline uint64_t topk_spare_lists(uint64_t units) { return (units + kTopkFanIn - 1) / kTopkFanIn; }
 int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t units, uint32_t k, Partial *out);
 // one level, `slots` queries that share `units` at a time (blockIdx.y): slot s reads src + s * src_stride
@@ -394,6 +414,12 @@ int launch_batch_match(const Hooks &h, void *stream, const void *db, const void 
 uint64_t batch_topk_units(const BatchGeometry &g);
 int launch_batch_topk(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
                       const BatchGeometry &g, Partial *lists, uint64_t stride, uint32_t k);
+// the histogram form of that pass (batch_lds_kernel<..., BL_HIST>): counts = DEVICE array [query of g]
+// [nbins + 1] of u64 (g.nqg * g.qper rows, in qtiles' order, zeroed on the stream by the caller);
+// every workgroup adds its non-zero words once, after its walk.  A padding query's row counts
+// every record as invalid; the host ignores it.
+int launch_batch_hist(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                      const BatchGeometry &g, uint64_t *counts, uint32_t nbins);
 int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
                     double *dist_out, Partial *partials);
 int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,

@@ -117,7 +117,9 @@ __device__ __forceinline__ Partial wave_best(Partial c) {
 // MODE_MATCH: the records below ms.threshold are appended to ms (iris_template_matches)
 // MODE_TOPK: the wave's min(k, 64) best records go to its list ms.buf[wave] (ms = topk_sink,
 // iris_template_topk)
-enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2, MODE_TOPK = 3 };
+// MODE_HIST: every record of the range is counted in the bin of its best rotation (ms = hist_sink,
+// iris_template_histogram), in the workgroup's LDS histogram, flushed once
+enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2, MODE_TOPK = 3, MODE_HIST = 4 };
 
 // Each wave: one 64-record block.  Workgroup: 4 waves.
 template <int MODE>
@@ -189,6 +191,16 @@ __global__ void __launch_bounds__(256, 5)
             }
         }
         if (!valid) c.den = 0;
+        if constexpr (MODE == MODE_HIST) {
+            // both barriers in uniform control flow: nothing above returns, inactive waves included
+            uint32_t *hist = hist_lds<1>();
+            hist_zero(hist, hist_sink_bins(ms));
+            __syncthreads();
+            hist_count(hist, hist_sink_bins(ms), lane, valid, c.num, c.den);
+            __syncthreads();
+            hist_flush(hist, hist_sink_bins(ms), hist_sink_copy(ms));
+            return;
+        }
         if constexpr (MODE == MODE_MATCH) {
             const bool hit[1] = {match_hit(ms, valid, c.num, c.den)};
             const uint32_t hn[1] = {c.num}, hd[1] = {c.den};
@@ -571,6 +583,33 @@ int launch_template_match(void *stream, const void *db, const void *qtab, Launch
     hipLaunchKernelGGL(template_kernel<MODE_MATCH>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
                        (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, ms);
+    return check_launch();
+}
+
+int launch_template_hist(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &hs) {
+    if (r.n == 0) return 0;
+    const BlockRange b = block_range(r);
+    hipLaunchKernelGGL(template_kernel<MODE_HIST>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, hs);
+    return check_launch();
+}
+
+// one thread per counter word and query (blockIdx.y): the sum of its copies
+__global__ void __launch_bounds__(256) hist_reduce_kernel(const uint64_t *__restrict__ src, uint32_t words,
+                                                          uint32_t copies, uint64_t *__restrict__ dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= words) return;
+    const uint64_t *s = src + (uint64_t)blockIdx.y * copies * words + i;
+    uint64_t sum = 0;
+    for (uint32_t c = 0; c < copies; ++c) sum += s[(uint64_t)c * words];
+    dst[(uint64_t)blockIdx.y * words + i] = sum;
+}
+
+int launch_hist_reduce(void *stream, const uint64_t *src, uint32_t words, uint32_t copies, uint32_t nq, uint64_t *dst) {
+    if (words == 0 || copies == 0 || nq == 0 || nq > 65535) return -1;
+    hipLaunchKernelGGL(hist_reduce_kernel, dim3((words + 255) / 256, nq), dim3(256), 0, (hipStream_t)stream, src, words,
+                       copies, dst);
     return check_launch();
 }
 

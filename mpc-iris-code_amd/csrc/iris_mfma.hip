@@ -79,7 +79,10 @@ __device__ __forceinline__ uint4 stream_load(const uint4 *p) {
 // is appended to ms (iris_template_matches); no partials, no reduce
 // MF_TOPK: the wave's k best records (ms = topk_sink: k = ms.cap) go to its list ms.buf[wave]
 // (iris_template_topk); the running best becomes the wave-resident list, no partials, no reduce
-enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2, MF_TOPK = 3 };
+// MF_HIST: every record of the range is counted in the bin of its best rotation's distance (ms =
+// hist_sink: iris_template_histogram) -- LDS atomics into the workgroup's histogram, whose non-zero
+// words are added to the workgroup's copy of the counters once; no partials, no reduce
+enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2, MF_TOPK = 3, MF_HIST = 4 };
 
 // KS > 1 (small ranges, T = kSplitT): the KS waves of a tile group split K -- wave w computes
 // chunk groups [w' * 100 / KS, +100 / KS) of tiles T * (blockIdx.x * (4 / KS) + w / KS) + t (w' = w % KS)
@@ -179,6 +182,12 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
             if constexpr (kG % 3 == 2) compute(sb);
         }
     }
+    // MF_HIST: every wave zeroes its share of the workgroup's histogram -- inactive waves and
+    // non-zero K-slices too -- ahead of a barrier all of them reach (K-split: the one below)
+    if constexpr (MODE == MF_HIST) {
+        hist_zero(hist_lds<1>(), hist_sink_bins(ms));
+        if constexpr (KS == 1) __syncthreads();
+    }
     if constexpr (KS > 1) {  // the K-slices' partial sums -> slice 0's accumulators (exact)
         __shared__ float red[W][T][32][64];
         if (slice != 0) {
@@ -254,6 +263,10 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                 hi[t] = o;
                 continue;
             }
+            if constexpr (MODE == MF_HIST) {  // half 0 counts: both halves hold the record's best
+                hist_count(hist_lds<1>(), hist_sink_bins(ms), lane, valid && h == 0, bn, bd);
+                continue;
+            }
             if constexpr (MODE == MF_TOPK) {  // den = 0: no candidate (half 0 votes)
                 hn[t] = bn;
                 hd[t] = valid && h == 0 ? bd : 0;
@@ -271,6 +284,11 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         }
     }
     if constexpr (MODE == MF_MATCH) append_matches<T>(ms, lane, hit, hn, hd, hr, hi);
+    // MF_HIST: the kernel has no early exit, so every wave reaches this barrier as it reached the first
+    if constexpr (MODE == MF_HIST) {
+        __syncthreads();
+        hist_flush(hist_lds<1>(), hist_sink_bins(ms), hist_sink_copy(ms));
+    }
     // MF_TOPK: the tiles' candidates go into the wave's list once the accumulators are dead (best:
     // this lane's entry).  One list per tile group: with a K-split only slice 0's wave holds sums.
     if constexpr (MODE == MF_TOPK) {
@@ -1235,6 +1253,19 @@ int launch_template_mfma_match(const Hooks &h, void *stream, const void *db, con
     hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
                        (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, ms);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the search's dispatch, MF_HIST epilogue
+int launch_template_mfma_hist(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                              const MatchSink &hs) {
+    if (r.n == 0) return 0;
+    const TileRange t = tile_range(h, r);
+    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_HIST, kSplitT, 4>
+                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_HIST, 1> : template_mfma_kernel<MF_HIST>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
+                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, hs);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -208,6 +208,8 @@ def load_library(path=None):
                                           ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_topk_merge": ([ctypes.POINTER(Match), u64, ctypes.c_uint32, ctypes.POINTER(Match),
                                  ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "iris_template_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
+            "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
                                         ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
             "iris_engine_query_tables": ([P, P, ctypes.c_size_t, P, ctypes.c_size_t], ctypes.c_int),
@@ -283,6 +285,7 @@ def exported_symbols():
         "iris_template_topk_async", "iris_pending_topk_wait",
         "iris_template_topk", "iris_resolver_topk", "iris_resolver_topk_masks", "iris_topk_merge",
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
+        "iris_template_histogram", "iris_template_batch_histogram",
     ]
 
 
@@ -542,6 +545,7 @@ def decode_distance(distances, denominators):
 
 
 TOPK_MAX = 64  # IRIS_TOPK_MAX
+HIST_MAX_BINS = 1024  # IRIS_HIST_MAX_BINS
 
 
 def _collect_topk(call, k):
@@ -1159,6 +1163,19 @@ class TemplateEngine(_Engine):
         return _collect_topk(lambda o, cnt: f(self.handle, db.handle, int(first), int(n), int(index_base), int(k),
                                               o, cnt), k)
 
+    def histogram(self, db, nbins, first=0, n=None):
+        """The distribution of the range's distances in one database pass (iris_template_histogram;
+        no reference counterpart) -> (np.ndarray[nbins] of uint64, invalid).  A record is counted in
+        bin min(nbins - 1, floor(distance * nbins)) of its best rotation's distance, a record
+        without a valid rotation in `invalid` alone; nbins is a power of two up to HIST_MAX_BINS.
+        The prefix sum of j bins is matches(j / nbins, cap=0)'s total.  Histograms of chunks add."""
+        n = (len(db) - first) if n is None else n
+        nb = int(nbins)
+        bins = np.zeros(nb if 0 < nb <= HIST_MAX_BINS else 1, np.uint64)
+        invalid = ctypes.c_uint64()
+        _check(load_library().iris_template_histogram(self.handle, db.handle, int(first), int(n), nb, _ptr(bins),
+                                                      ctypes.byref(invalid)))
+        return bins, int(invalid.value)
 
     def topk_async(self, db, k, first=0, n=None, index_base=0):
         """Enqueue topk() and return at once (iris_template_topk_async) -> PendingTopk, whose
@@ -1309,6 +1326,19 @@ class TemplateBatchEngine(_Engine):
         _check(load_library().iris_template_batch_topk(self.handle, db.handle, int(first), int(n), int(index_base),
                                                        int(k), out, counts))
         return [[_copy_match(out[q * room + j]) for j in range(counts[q])] for q in range(self.nq)]
+
+    def histogram(self, db, nbins, first=0, n=None):
+        """Every query's distance histogram in one pass over the templates
+        (iris_template_batch_histogram) -> (np.ndarray[nq, nbins] of uint64, np.ndarray[nq] of
+        uint64): row q and entry q are what TemplateEngine(queries[q]).histogram gives over the
+        same range."""
+        n = (len(db) - first) if n is None else n
+        nb = int(nbins)
+        bins = np.zeros((self.nq, nb if 0 < nb <= HIST_MAX_BINS else 1), np.uint64)
+        invalid = np.zeros(self.nq, np.uint64)
+        _check(load_library().iris_template_batch_histogram(self.handle, db.handle, int(first), int(n), nb, _ptr(bins),
+                                                            _ptr(invalid)))
+        return bins, invalid
 
 
 class DistanceBatchEngine(_Engine):
@@ -1759,7 +1789,7 @@ def f64_bits(x):
 
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
-    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "TOPK_MAX", "dot_bool", "dot_u16",
+    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "TOPK_MAX", "HIST_MAX_BINS", "dot_bool", "dot_u16",
     "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
