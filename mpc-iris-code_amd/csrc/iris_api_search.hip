@@ -1,12 +1,10 @@
 // iris_api_search.hip — the C ABI (include/iris_hip.h): template counts, searches (blocking,
-// asynchronous with their shared passes, batched) and distances.  Calls, locking and errors: see
-// iris_api.hip.
+// asynchronous with their shared passes, batched) and distances.  The asynchronous search's handle
+// lives by iris_pending.hpp.  Calls, locking and errors: see iris_api.hip.
 #include <math.h>
 #include <string.h>
 
-#include <new>
-
-#include "iris_handles.hpp"
+#include "iris_pending.hpp"
 
 using namespace iris;
 using namespace iris_api;
@@ -15,6 +13,17 @@ int iris_api::template_args(iris_engine *e, const iris_db *db) {
     ARG(e && db, "NULL argument");
     ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq == 0, "not a single-query template engine");
     ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
+    ARG(e->dev == db->dev, "engine and database live on different devices");
+    return 0;
+}
+
+int iris_api::template_batch_args(iris_engine *e, const iris_db *db) {
+    ARG(e && db, "NULL argument");
+    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
+    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
+    // batches of up to kBatchStreamMax queries stream (any layout); the GEMM reads TILES
+    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
+        "batched search of more than 3 queries needs a template database in the TILES layout");
     ARG(e->dev == db->dev, "engine and database live on different devices");
     return 0;
 }
@@ -325,48 +334,25 @@ int iris_template_search_async(iris_engine_t *e, const iris_db_t *db, uint64_t f
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
-    iris_pending *p = new (std::nothrow) iris_pending();
-    if (!p) return fail(IRIS_E_NOMEM, "out of host memory");
-    p->dev = d;
-    p->n = n;
-    p->base = index_base + first;
+    iris_pending *p = nullptr;
+    CHK(pending_new(d, kShareSearch, n, index_base + first, &p));
+    if (n == 0) return pending_publish(p, out);
     int rc = take_result_slot(d, &p->slot);
-    if (rc == 0 && n > 0) {
-        p->ev = take_event(d);
-        if (!p->ev) rc = fail(IRIS_E_HIP, "hipEventCreate failed");
-    }
+    if (rc == 0) rc = pending_arm(p);
     if (rc == 0) rc = search_enqueue(e, db, first, n, nullptr, p->slot, true, p->ev, 0, nullptr, 0, nullptr, true);
-    if (rc != 0) {
-        if (p->slot) d->free_slots.push_back(p->slot);
-        if (p->ev) d->event_pool.push_back(p->ev);
-        delete p;
-        return rc;
-    }
-    device_retain(d);
-    *out = p;
-    return 0;
+    if (rc != 0) return pending_abandon(p, rc);
+    return pending_publish(p, out);
 }
 
-int iris_pending_wait(iris_pending_t *p, iris_match_t *out) {
+int iris_pending_wait(iris_pending_t *pending, iris_match_t *out) {
     IRIS_KEEP_DEVICE();
-    ARG(p, "pending is NULL");
-    ARG(p->kind != kShareMatch, "pending of iris_template_matches_async: iris_pending_matches_wait waits for it");
-    ARG(p->kind != kShareTopk, "pending of iris_template_topk_async: iris_pending_topk_wait waits for it");
-    iris_device *d = p->dev;
-    hipError_t err = hipSuccess;
-    if (p->ev) err = hipEventSynchronize(p->ev);  // this search only: later enqueued work keeps running
-    Partial res{};
+    iris_pending *p = nullptr;
+    CHK(pending_claim(pending, kShareSearch, &p));
+    const hipError_t err = pending_await(p);
+    Partial res{};  // copied before the lock is taken: the slot is this handle's alone
     if (p->n > 0 && err == hipSuccess) memcpy(&res, p->slot, sizeof(Partial));
-    {
-        std::lock_guard<std::recursive_mutex> g(d->mu);
-        d->free_slots.push_back(p->slot);
-        if (p->ev) d->event_pool.push_back(p->ev);
-        fold_done(d);
-    }
     const uint64_t n = p->n, base = p->base;
-    delete p;
-    device_release(d);
-    if (err != hipSuccess) return fail(IRIS_E_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(err));
+    CHK(pending_retire(p, err, 0, [] { return 0; }));
     if (out) match_from(res, n > 0, base, out);
     return 0;
 }
@@ -396,12 +382,7 @@ int iris_template_batch_search(iris_engine_t *e, const iris_db_t *db, uint64_t f
                                iris_match_t *out) {
     IRIS_KEEP_DEVICE();
     ARG(e && db && out, "NULL argument");
-    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
-    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
-    // batches of up to kBatchStreamMax queries stream (any layout); the GEMM reads TILES
-    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
-        "batched search of more than 3 queries needs a template database in the TILES layout");
-    ARG(e->dev == db->dev, "engine and database live on different devices");
+    CHK(template_batch_args(e, db));
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));

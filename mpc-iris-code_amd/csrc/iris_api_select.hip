@@ -1,17 +1,90 @@
 // iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
 // and batched, with the runners that turn launch units into match lists, the pipelined forms of
-// the single-query template match and top-k, and the distance histograms of the template engines.
+// the single-query template match and top-k (their handles live by iris_pending.hpp; here is only
+// what a match or a top-k handle adds), and the distance histograms of the template engines.
 // Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
-#include <new>
-
-#include "iris_handles.hpp"
+#include "iris_pending.hpp"
 
 using namespace iris;
 using namespace iris_api;
 
 extern "C" {
+
+// ------------------------------------------------------------------ the single-query passes
+
+// What a pass does with a record's distance; all three take a MatchSink (a match sink, topk_sink,
+// hist_sink)
+enum SelectMode { kSelMatch, kSelTopk, kSelHist };
+
+// One single-query template pass over r on the device stream, timed under its mode's name: the MFMA
+// kernel on a TILES database (the engine's qfrag), the LANES kernel otherwise (its qtab).
+static int launch_template_select(iris_device *d, const iris_db *db, const void *qtab, const void *qfrag, LaunchRange r,
+                                  SelectMode mode, const MatchSink &sink) {
+    static const char *const names[] = {"template_match", "template_topk", "template_hist"};
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    return timed(d, names[mode], r.n, [&] {
+        switch (mode) {
+        case kSelMatch:
+            return tiles ? launch_template_mfma_match(d->hooks, d->stream, db->data, qfrag, r, sink)
+                         : launch_template_match(d->stream, db->data, qtab, r, sink);
+        case kSelTopk:
+            return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, qfrag, r, sink)
+                         : launch_template_topk(d->stream, db->data, qtab, r, sink);
+        default:
+            return tiles ? launch_template_mfma_hist(d->hooks, d->stream, db->data, qfrag, r, sink)
+                         : launch_template_hist(d->stream, db->data, qtab, r, sink);
+        }
+    });
+}
+
+// The single-query masks form of a match or a top-k pass, on masks engine c and the shares of its
+// query: a TILES database runs the fused masks_mfma_kernel; LANES the masks kernel into the
+// workspace (the denominators) and then the resolver kernel.  *den: the denominators once they are
+// enqueued -- a caller that launches again (the rerun of an overflowing list) while the workspace
+// is still theirs keeps it, and they are not computed twice.
+static int masks_single_launch(iris_device *d, const iris_engine *c, const iris_db *db, LaunchRange r,
+                               const uint16_t *const *shares, uint32_t parts, SelectMode mode, const MatchSink &sink,
+                               const uint16_t **den) {
+    const bool match = mode == kSelMatch;
+    if (db->k.layout == IRIS_LAYOUT_TILES)
+        return timed(d, match ? "masks_match" : "masks_topk", r.n, [&] {
+            return match ? launch_masks_match(d->hooks, d->stream, db->data, c->qfrag, r, shares, parts, sink)
+                         : launch_masks_topk(d->hooks, d->stream, db->data, c->qfrag, r, shares, parts, sink);
+        });
+    if (!*den) CHK(enqueue_masks_denoms(c, db, r, den));
+    return timed(d, match ? "resolver_match" : "resolver_topk", r.n, [&] {
+        return match ? launch_resolver_match(d->stream, shares, parts, *den, r.n, sink)
+                     : launch_resolver_topk(d->stream, shares, parts, *den, r.n, sink);
+    });
+}
+
+// The pass of a pipelined match (kShareMatch) or top-k (kShareTopk) call over r into ms, on the
+// device stream.  shared: a large TILES range -- the range the asynchronous search shares on, the
+// hooks included -- runs the sharing form (§4.1) and takes a place in the ring; every other pass
+// (the rerun of an overflowing match list among them) runs the blocking call's kernel and neither
+// hosts nor is hosted.  query: the host copy a guest's fragments are built from.
+static int select_pass_enqueue(iris_device *d, const iris_db *db, LaunchRange r, const void *qtab, const void *qfrag,
+                               const iris_template_t *query, ShareKind kind, const MatchSink &ms, bool shared) {
+    const bool match = kind == kShareMatch;
+    if (shared && db->k.layout == IRIS_LAYOUT_TILES && share_search_ok(d->hooks, r)) {
+        ShareJoin j;
+        CHK(share_join(d, d->share_last, db, r.first, r.n, mfma_search_partials(d->hooks, r), query, nullptr, kind, nullptr,
+                       &ms, &j));
+        d->share_last = -1;
+        // a match pass's counter: share_join zeroes it on the sharing stream, but only with a ring entry
+        if (match && !j.sp) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
+        CHK(timed(d, match ? "template_match" : "template_topk", r.n, [&] {
+            return (match ? launch_template_share_match : launch_template_share_topk)(
+                d->hooks, d->stream, db->data, qfrag, r, ms, j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
+        }));
+        return share_launched(d, j);
+    }
+    d->share_last = -1;  // only the device's latest pass can host
+    if (match) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
+    return launch_template_select(d, db, qtab, qfrag, r, match ? kSelMatch : kSelTopk, ms);
+}
 
 // ------------------------------------------------------------------ threshold matching
 
@@ -142,12 +215,10 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
     return 0;
 }
 
-// The single-query calls: one unit of one query, `launch` timed as `name`.
+// The single-query calls: one unit of one query.
 static int matches_run(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
-                       uint64_t *count, const char *name, const std::function<int(const MatchSink &)> &launch) {
-    const std::vector<MatchUnit> unit{MatchUnit{0, 1, [&](const MatchSink *ms) {
-        return timed(d, name, n, [&] { return launch(ms[0]); });
-    }}};
+                       uint64_t *count, const std::function<int(const MatchSink &)> &launch) {
+    const std::vector<MatchUnit> unit{MatchUnit{0, 1, [&](const MatchSink *ms) { return launch(ms[0]); }}};
     return matches_run_units(d, n, base, threshold, out, cap, count, 1, true, unit);
 }
 
@@ -162,21 +233,18 @@ int iris_template_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first,
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
-    return matches_run(d, n, index_base + first, threshold, out, cap, count, "template_match", [&](const MatchSink &ms) {
-        return db->k.layout == IRIS_LAYOUT_TILES
-                   ? launch_template_mfma_match(d->hooks, d->stream, db->data, e->qfrag, r, ms)
-                   : launch_template_match(d->stream, db->data, e->qtab, r, ms);
+    return matches_run(d, n, index_base + first, threshold, out, cap, count, [&](const MatchSink &ms) {
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, kSelMatch, ms);
     });
 }
 
 // ------------------------------------------------------------------ pipelined threshold matching
 
-// iris_template_matches_async .. iris_pending_matches_wait.  The pass appends
-// into buffers of the pending's own; behind it, on the side stream, the counter and the first
-// kMatchInline records go to the pending's pinned slot, and `ev` is recorded there.
-struct iris_pending_matches : iris_pending {  // dev, ev (null for an empty range), n, base: as the search's
+// iris_template_matches_async .. iris_pending_matches_wait (the handle's life:
+// iris_pending.hpp).  The pass appends into the pending's device buffer; its side-stream step takes
+// the counter and the first kMatchInline records to the pending's pinned slot.
+struct iris_pending_matches : iris_pending {
     const iris_db *db = nullptr;  // the caller keeps it alive and unmodified until the wait
-    MatchBufs bufs;
     uint64_t first = 0, cap = 0, room = 0;
     double threshold = 0;
     iris_template_t query;  // an overflowing list runs the pass again after the engine may be gone
@@ -185,54 +253,12 @@ struct iris_pending_matches : iris_pending {  // dev, ev (null for an empty rang
 static uint64_t *match_counter(const MatchBufs &b) { return (uint64_t *)b.dev.p; }
 static Partial *match_records(const MatchBufs &b) { return (Partial *)((char *)b.dev.p + kMatchRecOff); }
 
-// buffers for a pending with room for `room` records (caller holds the device lock)
-static int match_bufs_take(iris_device *d, uint64_t room, MatchBufs *out) {
-    if (d->match_free.empty()) {  // pinned slots in blocks, as take_result_slot's; device buffers on first use
-        constexpr int kSlots = 64;
-        void *blk = nullptr;
-        hipError_t e = hipHostMalloc(&blk, kSlots * kMatchSlotBytes, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(IRIS_E_NOMEM, std::string("hipHostMalloc match slots: ") + hipGetErrorString(e));
-        d->slot_blocks.push_back(blk);
-        for (int i = kSlots - 1; i >= 0; --i)
-            d->match_free.push_back(MatchBufs{DevBuf{}, (char *)blk + (size_t)i * kMatchSlotBytes});
-    }
-    MatchBufs b = d->match_free.back();  // the one returned last: a steady pipeline keeps to a few
-    d->match_free.pop_back();
-    const int rc = ensure(d, b.dev, kMatchRecOff + room * sizeof(Partial));
-    if (rc != 0) {
-        d->match_free.push_back(b);
-        return rc;
-    }
-    *out = b;
-    return 0;
-}
-
-// The pass of a pending over its range into its buffers, on the device stream; shared: it may take
-// a place in the sharing ring (the submission; the rerun of an overflowing list never does).
+// The pass of a pending over its range into its buffers; shared: the submission (the rerun of an
+// overflowing list never shares).
 static int match_pass_enqueue(iris_device *d, const iris_pending_matches *p, const void *qtab, const void *qfrag,
                               bool shared) {
-    const LaunchRange r{p->first, p->n};
     const MatchSink ms{match_records(p->bufs), p->room, match_counter(p->bufs), p->threshold};
-    const bool tiles = p->db->k.layout == IRIS_LAYOUT_TILES;
-    if (shared && tiles && share_search_ok(d->hooks, r)) {
-        // the sharing form (§4.1): the range the asynchronous search shares on, the hooks included
-        ShareJoin j;
-        CHK(share_join(d, d->share_last, p->db, p->first, p->n, mfma_search_partials(d->hooks, r), &p->query, nullptr,
-                       kShareMatch, nullptr, &ms, &j));
-        d->share_last = -1;
-        if (!j.sp) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
-        CHK(timed(d, "template_match", p->n, [&] {
-            return launch_template_share_match(d->hooks, d->stream, p->db->data, qfrag, r, ms, j.sp ? j.sp->slot : nullptr,
-                                               j.own_done, j.count);
-        }));
-        return share_launched(d, j);
-    }
-    d->share_last = -1;  // only the device's latest pass can host
-    HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
-    return timed(d, "template_match", p->n, [&] {
-        return tiles ? launch_template_mfma_match(d->hooks, d->stream, p->db->data, qfrag, r, ms)
-                     : launch_template_match(d->stream, p->db->data, qtab, r, ms);
-    });
+    return select_pass_enqueue(d, p->db, LaunchRange{p->first, p->n}, qtab, qfrag, &p->query, kShareMatch, ms, shared);
 }
 
 int iris_template_matches_async(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
@@ -246,54 +272,26 @@ int iris_template_matches_async(iris_engine_t *e, const iris_db_t *db, uint64_t 
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     if (!e->host_query) return fail(IRIS_E_ARG, "engine keeps no host copy of its query");
-    iris_pending_matches *p = new (std::nothrow) iris_pending_matches();
-    if (!p) return fail(IRIS_E_NOMEM, "out of host memory");
-    p->kind = kShareMatch;
-    p->dev = d;
+    iris_pending_matches *p = nullptr;
+    CHK(pending_new(d, kShareMatch, n, index_base + first, &p));
     p->db = db;
     p->first = first;
-    p->n = n;
-    p->base = index_base + first;
     p->cap = cap;
     p->threshold = threshold;
     p->query = *e->host_query;
-    if (n == 0) {
-        device_retain(d);
-        *out = p;
-        return 0;
-    }
+    if (n == 0) return pending_publish(p, out);
     p->room = std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom));
-    int rc = match_bufs_take(d, p->room, &p->bufs);
-    bool taken = rc == 0;
-    if (rc == 0) {
-        p->ev = take_event(d);
-        if (!p->ev) rc = fail(IRIS_E_HIP, "hipEventCreate failed");
-    }
-    if (rc == 0) rc = ensure_aux(d);
+    int rc = bufs_take(d, kMatchPool, kMatchRecOff + p->room * sizeof(Partial), p);
+    if (rc == 0) rc = pending_arm(p);
     if (rc == 0) rc = match_pass_enqueue(d, p, e->qtab, e->qfrag, true);
-    if (rc == 0) {
-        // behind the pass, on the side stream (the next pass is not held up): the counter and the
-        // first records to the pinned slot, then the pending's event
-        hipError_t err = hipEventRecord(p->ev, d->stream);
-        if (err == hipSuccess) err = hipStreamWaitEvent(d->aux, p->ev, 0);
+    if (rc == 0) rc = pending_side_begin(p);
+    if (rc == 0) {  // the counter and the first records to the pinned slot
         const size_t bytes = kMatchRecOff + std::min<uint64_t>(p->room, kMatchInline) * sizeof(Partial);
-        if (err == hipSuccess) err = hipMemcpyAsync(p->bufs.host, p->bufs.dev.p, bytes, hipMemcpyDeviceToHost, d->aux);
-        if (err == hipSuccess) err = hipEventRecord(p->ev, d->aux);
-        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("enqueue match copy: ") + hipGetErrorString(err));
+        rc = pending_side_chk(p, hipMemcpyAsync(p->bufs.host, p->bufs.dev.p, bytes, hipMemcpyDeviceToHost, d->aux));
     }
-    if (rc != 0) {
-        if (taken) {
-            (void)hipStreamSynchronize(d->stream);  // whatever was enqueued no longer writes the buffers
-            side_sync(d);
-            d->match_free.push_back(p->bufs);
-        }
-        if (p->ev) d->event_pool.push_back(p->ev);
-        delete p;
-        return rc;
-    }
-    device_retain(d);
-    *out = p;
-    return 0;
+    if (rc == 0) rc = pending_side_end(p);
+    if (rc != 0) return pending_abandon(p, rc);
+    return pending_publish(p, out);
 }
 
 // The list of a pending whose pass has ended (caller holds the device lock): `total` is the
@@ -344,39 +342,19 @@ static int pending_matches_finish(iris_pending_matches *p, uint64_t total, iris_
 
 int iris_pending_matches_wait(iris_pending_t *pending, iris_match_t *out, uint64_t *count) {
     IRIS_KEEP_DEVICE();
-    ARG(pending, "pending is NULL");
-    ARG(pending->kind != kShareSearch, "pending of iris_template_search_async: iris_pending_wait waits for it");
-    ARG(pending->kind != kShareTopk, "pending of iris_template_topk_async: iris_pending_topk_wait waits for it");
-    iris_pending_matches *p = static_cast<iris_pending_matches *>(pending);
-    iris_device *d = p->dev;
+    iris_pending_matches *p = nullptr;
+    CHK(pending_claim(pending, kShareMatch, &p));
     int rc = 0;
     if (!count) rc = fail(IRIS_E_ARG, "count is NULL");
     else if (p->cap && !out) rc = fail(IRIS_E_ARG, "out is NULL with cap > 0");
-    hipError_t err = hipSuccess;
-    if (p->ev) err = hipEventSynchronize(p->ev);  // this pass and its copy only: later enqueued work keeps running
-    {
-        std::lock_guard<std::recursive_mutex> g(d->mu);
-        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(err));
-        if (rc == 0) {
-            uint64_t total = 0;
-            if (p->n > 0) memcpy(&total, p->bufs.host, sizeof(total));
-            if (total > p->n) rc = fail(IRIS_E_HIP, "match pass counted more records than the range holds");
-            if (rc == 0) rc = pending_matches_finish(p, total, out);
-            if (rc == 0) *count = total;
-        }
-        if (p->n > 0) {
-            if (err != hipSuccess) {  // nothing may still write buffers that go back to the list
-                (void)hipStreamSynchronize(d->stream);
-                side_sync(d);
-            }
-            d->match_free.push_back(p->bufs);
-        }
-        if (p->ev) d->event_pool.push_back(p->ev);
-        fold_done(d);
-    }
-    delete p;
-    device_release(d);
-    return rc;
+    return pending_retire(p, pending_await(p), rc, [&]() -> int {
+        uint64_t total = 0;
+        if (p->n > 0) memcpy(&total, p->bufs.host, sizeof(total));
+        if (total > p->n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+        CHK(pending_matches_finish(p, total, out));
+        *count = total;
+        return 0;
+    });
 }
 
 // iris_resolver_search's threshold sibling
@@ -390,8 +368,8 @@ int iris_resolver_matches(iris_device_t *d, const uint16_t *const *shares, uint3
     CHK(share_args(shares, parts, n, denoms != nullptr));
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
-    return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
-        return launch_resolver_match(d->stream, shares, parts, denoms, n, ms);
+    return matches_run(d, n, index_base, threshold, out, cap, count, [&](const MatchSink &ms) {
+        return timed(d, "resolver_match", n, [&] { return launch_resolver_match(d->stream, shares, parts, denoms, n, ms); });
     });
 }
 
@@ -410,14 +388,9 @@ int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t 
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
-    if (db->k.layout == IRIS_LAYOUT_TILES)
-        return matches_run(d, n, index_base, threshold, out, cap, count, "masks_match", [&](const MatchSink &ms) {
-            return launch_masks_match(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, ms);
-        });
     const uint16_t *den = nullptr;
-    if (n) CHK(enqueue_masks_denoms(e, db, r, &den));
-    return matches_run(d, n, index_base, threshold, out, cap, count, "resolver_match", [&](const MatchSink &ms) {
-        return launch_resolver_match(d->stream, shares_device, parts, den, n, ms);
+    return matches_run(d, n, index_base, threshold, out, cap, count, [&](const MatchSink &ms) {
+        return masks_single_launch(d, e, db, r, shares_device, parts, kSelMatch, ms, &den);
     });
 }
 
@@ -430,27 +403,28 @@ static int topk_args(uint32_t k, const iris_match_t *out, const uint32_t *count)
     return 0;
 }
 
+// the lists a single-query template top-k pass over r (not empty) writes
+static uint64_t template_topk_lists(const iris_device *d, const iris_db *db, LaunchRange r) {
+    return db->k.layout == IRIS_LAYOUT_TILES ? mfma_topk_units(d->hooks, r) : template_topk_units(r);
+}
+
 // One top-k call over n records: `launch` enqueues the pass whose `units` waves each store their
 // k best at the lists it is given (the device's match buffer: units lists, then the merge's spare
 // lists), the merge levels follow on the stream and the last one writes k records to the pinned
 // host result -- 24 k bytes whatever n is -- and the call waits once.  The list is sorted with the
 // empty entries (den = 0) last, so the count is the length of its valid prefix.
 static int topk_run(iris_device *d, uint64_t n, uint64_t base, uint32_t k, iris_match_t *out, uint32_t *count,
-                    const char *name, uint64_t units, const std::function<int(const MatchSink &)> &launch) {
+                    uint64_t units, const std::function<int(const MatchSink &)> &launch) {
     *count = 0;
     if (n == 0) return 0;
     CHK(ensure(d, d->matches, (units + topk_spare_lists(units)) * k * sizeof(Partial)));
     CHK(ensure_host_result(d, (size_t)k * sizeof(Partial)));
     Partial *lists = (Partial *)d->matches.p, *spare = lists + units * k;
-    CHK(timed(d, name, n, [&] { return launch(topk_sink(lists, k)); }));
+    CHK(launch(topk_sink(lists, k)));
     CHK(timed(d, "topk_merge", units,
               [&] { return launch_topk_merge(d->stream, lists, spare, units, k, (Partial *)d->host_result); }));
     CHK(sync(d));
-    const Partial *res = (const Partial *)d->host_result;
-    uint32_t c = 0;
-    while (c < k && res[c].den != 0) ++c;
-    for (uint32_t i = 0; i < c; ++i) match_from(res[i], true, base, &out[i]);
-    *count = c;
+    *count = topk_list((const Partial *)d->host_result, k, base, out);
     return 0;
 }
 
@@ -465,86 +439,21 @@ int iris_template_topk(iris_engine_t *e, const iris_db_t *db, uint64_t first, ui
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
-    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
-    const uint64_t units = n ? (tiles ? mfma_topk_units(d->hooks, r) : template_topk_units(r)) : 0;
-    return topk_run(d, n, index_base + first, k, out, count, "template_topk", units, [&](const MatchSink &ts) {
-        return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts)
-                     : launch_template_topk(d->stream, db->data, e->qtab, r, ts);
+    const uint64_t units = n ? template_topk_lists(d, db, r) : 0;
+    return topk_run(d, n, index_base + first, k, out, count, units, [&](const MatchSink &ts) {
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, kSelTopk, ts);
     });
 }
 
 // ------------------------------------------------------------------ pipelined top-k
 
-// iris_template_topk_async .. iris_pending_topk_wait.  The pass stores its lists
-// into a buffer of the pending's own; behind it, on the side stream, the merge folds them and its
-// last level writes the k records to the pending's pinned slot -- as the blocking call's writes the
-// device's pinned result -- and `ev` is recorded there.
-struct iris_pending_topk : iris_pending {  // dev, ev (null for an empty range), n, base: as the search's
-    MatchBufs bufs;
+// iris_template_topk_async .. iris_pending_topk_wait (the handle's life:
+// iris_pending.hpp).  The pass stores its lists into the pending's device buffer; its side-stream
+// step is the merge, whose last level writes the k records to the pending's pinned slot -- as the
+// blocking call's writes the device's pinned result.
+struct iris_pending_topk : iris_pending {
     uint32_t k = 0;
 };
-
-// buffers for a pending whose pass writes `units` lists of k (caller holds the device lock)
-static int topk_bufs_take(iris_device *d, uint64_t units, uint32_t k, MatchBufs *out) {
-    if (d->topk_free.empty()) {  // as match_bufs_take
-        constexpr int kSlots = 32;
-        void *blk = nullptr;
-        hipError_t e = hipHostMalloc(&blk, kSlots * kTopkSlotBytes, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(IRIS_E_NOMEM, std::string("hipHostMalloc top-k slots: ") + hipGetErrorString(e));
-        d->slot_blocks.push_back(blk);
-        for (int i = kSlots - 1; i >= 0; --i)
-            d->topk_free.push_back(MatchBufs{DevBuf{}, (char *)blk + (size_t)i * kTopkSlotBytes});
-    }
-    // the one returned last whose buffer is large enough (a steady pipeline keeps to a few), else one
-    // that has no buffer yet: growing a buffer frees it, and hipFree waits for the device -- for the
-    // very pass that could have hosted this one (k, and so the size, changes from call to call)
-    const size_t bytes = (units + topk_spare_lists(units)) * k * sizeof(Partial);
-    size_t pick = d->topk_free.size() - 1;
-    for (size_t i = d->topk_free.size(); i-- > 0;)
-        if (d->topk_free[i].dev.cap >= bytes) {
-            pick = i;
-            break;
-        }
-    if (d->topk_free[pick].dev.cap < bytes)
-        for (size_t i = d->topk_free.size(); i-- > 0;)
-            if (!d->topk_free[i].dev.p) {
-                pick = i;
-                break;
-            }
-    MatchBufs b = d->topk_free[pick];
-    d->topk_free.erase(d->topk_free.begin() + pick);
-    const int rc = ensure(d, b.dev, bytes);
-    if (rc != 0) {
-        d->topk_free.push_back(b);
-        return rc;
-    }
-    *out = b;
-    return 0;
-}
-
-// The pass of a pending over its range into its lists, on the device stream.  Large TILES ranges
-// run the sharing form (§4.1) and take a place in the ring; every other range runs the blocking
-// call's kernel and neither hosts nor is hosted.
-static int topk_pass_enqueue(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r,
-                             const MatchSink &ts) {
-    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
-    if (tiles && share_search_ok(d->hooks, r)) {
-        ShareJoin j;
-        CHK(share_join(d, d->share_last, db, r.first, r.n, mfma_search_partials(d->hooks, r), e->host_query, nullptr,
-                       kShareTopk, nullptr, &ts, &j));
-        d->share_last = -1;
-        CHK(timed(d, "template_topk", r.n, [&] {
-            return launch_template_share_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts, j.sp ? j.sp->slot : nullptr,
-                                              j.own_done, j.count);
-        }));
-        return share_launched(d, j);
-    }
-    d->share_last = -1;  // only the device's latest pass can host
-    return timed(d, "template_topk", r.n, [&] {
-        return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, e->qfrag, r, ts)
-                     : launch_template_topk(d->stream, db->data, e->qtab, r, ts);
-    });
-}
 
 int iris_template_topk_async(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
                              uint32_t k, iris_pending_t **out) {
@@ -557,94 +466,37 @@ int iris_template_topk_async(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     if (!e->host_query) return fail(IRIS_E_ARG, "engine keeps no host copy of its query");
-    iris_pending_topk *p = new (std::nothrow) iris_pending_topk();
-    if (!p) return fail(IRIS_E_NOMEM, "out of host memory");
-    p->kind = kShareTopk;
-    p->dev = d;
-    p->n = n;
-    p->base = index_base + first;
+    iris_pending_topk *p = nullptr;
+    CHK(pending_new(d, kShareTopk, n, index_base + first, &p));
     p->k = k;
-    if (n == 0) {
-        device_retain(d);
-        *out = p;
-        return 0;
-    }
+    if (n == 0) return pending_publish(p, out);
     const LaunchRange r{first, n};
-    const uint64_t units = db->k.layout == IRIS_LAYOUT_TILES ? mfma_topk_units(d->hooks, r) : template_topk_units(r);
-    int rc = topk_bufs_take(d, units, k, &p->bufs);
-    const bool taken = rc == 0;
-    if (rc == 0) {
-        p->ev = take_event(d);
-        if (!p->ev) rc = fail(IRIS_E_HIP, "hipEventCreate failed");
-    }
-    if (rc == 0) rc = ensure_aux(d);
+    const uint64_t units = template_topk_lists(d, db, r);
+    int rc = bufs_take(d, kTopkPool, (units + topk_spare_lists(units)) * k * sizeof(Partial), p);
+    if (rc == 0) rc = pending_arm(p);
     Partial *lists = (Partial *)p->bufs.dev.p, *spare = lists + units * k;
-    if (rc == 0) rc = topk_pass_enqueue(d, e, db, r, topk_sink(lists, k));
-    if (rc == 0) {
-        // behind the pass, on the side stream (the next pass is not held up): the merge, whose last
-        // level writes the pinned slot, then the pending's event
-        hipError_t err = hipEventRecord(p->ev, d->stream);
-        if (err == hipSuccess) err = hipStreamWaitEvent(d->aux, p->ev, 0);
-        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("enqueue top-k merge: ") + hipGetErrorString(err));
-        if (rc == 0)
-            rc = timed(d, "topk_merge", units,
-                       [&] { return launch_topk_merge(d->aux, lists, spare, units, k, (Partial *)p->bufs.host); }, d->aux);
-        if (rc == 0 && (err = hipEventRecord(p->ev, d->aux)) != hipSuccess)
-            rc = fail(IRIS_E_HIP, std::string("enqueue top-k merge: ") + hipGetErrorString(err));
-    }
-    if (rc != 0) {
-        if (taken) {
-            (void)hipStreamSynchronize(d->stream);  // whatever was enqueued no longer writes the buffers
-            side_sync(d);
-            d->topk_free.push_back(p->bufs);
-        }
-        if (p->ev) d->event_pool.push_back(p->ev);
-        delete p;
-        return rc;
-    }
-    device_retain(d);
-    *out = p;
-    return 0;
+    if (rc == 0)
+        rc = select_pass_enqueue(d, db, r, e->qtab, e->qfrag, e->host_query, kShareTopk, topk_sink(lists, k), true);
+    if (rc == 0) rc = pending_side_begin(p);
+    if (rc == 0)  // the merge, whose last level writes the pinned slot
+        rc = timed(d, "topk_merge", units,
+                   [&] { return launch_topk_merge(d->aux, lists, spare, units, k, (Partial *)p->bufs.host); }, d->aux);
+    if (rc == 0) rc = pending_side_end(p);
+    if (rc != 0) return pending_abandon(p, rc);
+    return pending_publish(p, out);
 }
 
 int iris_pending_topk_wait(iris_pending_t *pending, iris_match_t *out, uint32_t *count) {
     IRIS_KEEP_DEVICE();
-    ARG(pending, "pending is NULL");
-    ARG(pending->kind != kShareSearch, "pending of iris_template_search_async: iris_pending_wait waits for it");
-    ARG(pending->kind != kShareMatch, "pending of iris_template_matches_async: iris_pending_matches_wait waits for it");
-    iris_pending_topk *p = static_cast<iris_pending_topk *>(pending);
-    iris_device *d = p->dev;
+    iris_pending_topk *p = nullptr;
+    CHK(pending_claim(pending, kShareTopk, &p));
     int rc = 0;
     if (!out) rc = fail(IRIS_E_ARG, "out is NULL");
     else if (!count) rc = fail(IRIS_E_ARG, "count is NULL");
-    hipError_t err = hipSuccess;
-    if (p->ev) err = hipEventSynchronize(p->ev);  // this pass and its merge only: later enqueued work keeps running
-    {
-        std::lock_guard<std::recursive_mutex> g(d->mu);
-        if (err != hipSuccess) rc = fail(IRIS_E_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(err));
-        if (rc == 0) {
-            // the blocking call's conversion: the list is sorted with the empty entries last
-            uint32_t c = 0;
-            if (p->n > 0) {
-                const Partial *res = (const Partial *)p->bufs.host;
-                while (c < p->k && res[c].den != 0) ++c;
-                for (uint32_t i = 0; i < c; ++i) match_from(res[i], true, p->base, &out[i]);
-            }
-            *count = c;
-        }
-        if (p->n > 0) {
-            if (err != hipSuccess) {  // nothing may still write buffers that go back to the list
-                (void)hipStreamSynchronize(d->stream);
-                side_sync(d);
-            }
-            d->topk_free.push_back(p->bufs);
-        }
-        if (p->ev) d->event_pool.push_back(p->ev);
-        fold_done(d);
-    }
-    delete p;
-    device_release(d);
-    return rc;
+    return pending_retire(p, pending_await(p), rc, [&] {
+        *count = p->n > 0 ? topk_list((const Partial *)p->bufs.host, p->k, p->base, out) : 0;
+        return 0;
+    });
 }
 
 // iris_resolver_search's top-k sibling
@@ -657,8 +509,8 @@ int iris_resolver_topk(iris_device_t *d, const uint16_t *const *shares, uint32_t
     CHK(share_args(shares, parts, n, denoms != nullptr));
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
-    return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
-        return launch_resolver_topk(d->stream, shares, parts, denoms, n, ts);
+    return topk_run(d, n, index_base, k, out, count, resolver_topk_units(n), [&](const MatchSink &ts) {
+        return timed(d, "resolver_topk", n, [&] { return launch_resolver_topk(d->stream, shares, parts, denoms, n, ts); });
     });
 }
 
@@ -677,15 +529,10 @@ int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
-    if (db->k.layout == IRIS_LAYOUT_TILES)
-        return topk_run(d, n, index_base, k, out, count, "masks_topk", n ? masks_topk_units(d->hooks, r) : 0,
-                        [&](const MatchSink &ts) {
-                            return launch_masks_topk(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, ts);
-                        });
+    const uint64_t units = db->k.layout != IRIS_LAYOUT_TILES ? resolver_topk_units(n) : n ? masks_topk_units(d->hooks, r) : 0;
     const uint16_t *den = nullptr;
-    if (n) CHK(enqueue_masks_denoms(e, db, r, &den));
-    return topk_run(d, n, index_base, k, out, count, "resolver_topk", resolver_topk_units(n), [&](const MatchSink &ts) {
-        return launch_resolver_topk(d->stream, shares_device, parts, den, n, ts);
+    return topk_run(d, n, index_base, k, out, count, units, [&](const MatchSink &ts) {
+        return masks_single_launch(d, e, db, r, shares_device, parts, kSelTopk, ts, &den);
     });
 }
 
@@ -742,13 +589,7 @@ static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k,
         }
     }
     CHK(sync(d));
-    for (uint32_t q = 0; q < nq; ++q) {
-        const Partial *r = res + (size_t)q * k;
-        uint32_t c = 0;
-        while (c < k && r[c].den != 0) ++c;
-        for (uint32_t i = 0; i < c; ++i) match_from(r[i], true, base, &out[(size_t)q * k + i]);
-        counts[q] = c;
-    }
+    for (uint32_t q = 0; q < nq; ++q) counts[q] = topk_list(res + (size_t)q * k, k, base, out + (size_t)q * k);
     return 0;
 }
 
@@ -785,17 +626,9 @@ int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64
             // one query through the single-query forms, on its slab of every part
             const uint64_t lists = w.tiles ? masks_topk_units(d->hooks, w.r) : resolver_topk_units(n);
             units.push_back(TopkUnit{u.q0, 1, lists, [=](Partial *buf, uint64_t) {
-                const uint16_t *sl[8];
+                const uint16_t *sl[8], *den = nullptr;
                 w.slabs(u.q0, shares_device, parts, sl);
-                if (w.tiles)
-                    return timed(d, "masks_topk", n, [&] {
-                        return launch_masks_topk(d->hooks, d->stream, db->data, u.one->qfrag, w.r, sl, parts, topk_sink(buf, k));
-                    });
-                const uint16_t *den = nullptr;
-                CHK(enqueue_masks_denoms(u.one, db, w.r, &den));
-                return timed(d, "resolver_topk", n, [&] {
-                    return launch_resolver_topk(d->stream, sl, parts, den, n, topk_sink(buf, k));
-                });
+                return masks_single_launch(d, u.one, db, w.r, sl, parts, kSelTopk, topk_sink(buf, k), &den);
             }});
         }
     }
@@ -833,17 +666,9 @@ int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uin
         } else {
             // one query through the single-query forms, on its slab of every part
             units.push_back(MatchUnit{u.q0, 1, [=](const MatchSink *ms) {
-                const uint16_t *sl[8];
+                const uint16_t *sl[8], *den = nullptr;
                 w.slabs(u.q0, shares_device, parts, sl);
-                if (w.tiles)
-                    return timed(d, "masks_match", n, [&] {
-                        return launch_masks_match(d->hooks, d->stream, db->data, u.one->qfrag, w.r, sl, parts, ms[0]);
-                    });
-                const uint16_t *den = nullptr;
-                CHK(enqueue_masks_denoms(u.one, db, w.r, &den));
-                return timed(d, "resolver_match", n, [&] {
-                    return launch_resolver_match(d->stream, sl, parts, den, n, ms[0]);
-                });
+                return masks_single_launch(d, u.one, db, w.r, sl, parts, kSelMatch, ms[0], &den);
             }});
         }
     }
@@ -865,12 +690,7 @@ int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t 
                                 double threshold, iris_match_t *out, uint64_t cap, uint64_t *counts) {
     IRIS_KEEP_DEVICE();
     CHK(matches_args(threshold, out, cap, counts));  // the value arguments first: refused whatever the handles
-    ARG(e && db, "NULL argument");
-    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
-    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
-    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
-        "batched search of more than 3 queries needs a template database in the TILES layout");
-    ARG(e->dev == db->dev, "engine and database live on different devices");
+    CHK(template_batch_args(e, db));
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
@@ -883,11 +703,7 @@ int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t 
         for (uint32_t q = 0; n && q < nq; ++q) {
             const iris_engine *c = e->sub[q];
             units.push_back(MatchUnit{q, 1, [=](const MatchSink *ms) {
-                return timed(d, "template_match", n, [&] {
-                    return db->k.layout == IRIS_LAYOUT_TILES
-                               ? launch_template_mfma_match(d->hooks, d->stream, db->data, c->qfrag, r, ms[0])
-                               : launch_template_match(d->stream, db->data, c->qtab, r, ms[0]);
-                });
+                return launch_template_select(d, db, c->qtab, c->qfrag, r, kSelMatch, ms[0]);
             }});
         }
         return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, nullptr, kBatchMatchBudget);
@@ -938,12 +754,7 @@ int iris_template_batch_topk(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");  // the value arguments first
     ARG(out, "out is NULL");
     ARG(counts, "counts is NULL");
-    ARG(e && db, "NULL argument");
-    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
-    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
-    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
-        "batched search of more than 3 queries needs a template database in the TILES layout");
-    ARG(e->dev == db->dev, "engine and database live on different devices");
+    CHK(template_batch_args(e, db));
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
@@ -953,15 +764,11 @@ int iris_template_batch_topk(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     const uint64_t base = index_base + first;
     std::vector<TopkUnit> units;
     if (!e->sub.empty()) {
-        const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
-        const uint64_t lists = n ? (tiles ? mfma_topk_units(d->hooks, r) : template_topk_units(r)) : 0;
+        const uint64_t lists = n ? template_topk_lists(d, db, r) : 0;
         for (uint32_t q = 0; n && q < nq; ++q) {
             const iris_engine *c = e->sub[q];
             units.push_back(TopkUnit{q, 1, lists, [=](Partial *buf, uint64_t) {
-                return timed(d, "template_topk", n, [&] {
-                    return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, c->qfrag, r, topk_sink(buf, k))
-                                 : launch_template_topk(d->stream, db->data, c->qtab, r, topk_sink(buf, k));
-                });
+                return launch_template_select(d, db, c->qtab, c->qfrag, r, kSelTopk, topk_sink(buf, k));
             }});
         }
         return topk_run_units(d, n, base, k, out, counts, nq, units);
@@ -1004,29 +811,31 @@ static int hist_finish(iris_device *d, uint64_t n, uint32_t nbins, uint32_t nq, 
     return 0;
 }
 
+// the histograms of an empty range
+static int hist_empty(uint32_t nq, uint32_t nbins, uint64_t *bins, uint64_t *invalid) {
+    memset(bins, 0, (size_t)nq * nbins * sizeof(uint64_t));
+    memset(invalid, 0, nq * sizeof(uint64_t));
+    return 0;
+}
+
 // One histogram call of nq single-query passes over n records (iris_template_histogram: nq = 1; a
 // batch engine of up to kBatchStreamMax queries).  Query q has `copies` copies of its nbins + 1
 // counters in the device's counter buffer, all zeroed on the stream first; its pass -- launch(q,
-// sink), timed as "template_hist" -- adds every workgroup's LDS histogram to copy
+// sink), "template_hist" -- adds every workgroup's LDS histogram to copy
 // blockIdx.x % copies, "hist_reduce" sums the copies straight into the pinned host result, and the
 // call waits once.  copies = 1 (the IRIS_HIST_COPIES=1 test hook): the passes add into the result
 // itself and a copy brings it back (DESIGN.md 4.17 has both measured).  A histogram always fits, so
 // there is no second pass.
 static int hist_run(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, uint64_t *invalid, uint32_t nq,
                     const std::function<int(uint32_t, const MatchSink &)> &launch) {
-    if (n == 0) {
-        memset(bins, 0, (size_t)nq * nbins * sizeof(uint64_t));
-        memset(invalid, 0, nq * sizeof(uint64_t));
-        return 0;
-    }
+    if (n == 0) return hist_empty(nq, nbins, bins, invalid);
     const uint32_t words = nbins + 1, copies = d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
     const size_t row = (size_t)copies * words;
     CHK(ensure(d, d->match_count, nq * row * sizeof(uint64_t)));
     CHK(ensure_host_result(d, (size_t)nq * words * sizeof(uint64_t)));
     uint64_t *cnt = (uint64_t *)d->match_count.p;
     HIPCHK(hipMemsetAsync(cnt, 0, nq * row * sizeof(uint64_t), d->stream));
-    for (uint32_t q = 0; q < nq; ++q)
-        CHK(timed(d, "template_hist", n, [&] { return launch(q, hist_sink(cnt + q * row, nbins, copies)); }));
+    for (uint32_t q = 0; q < nq; ++q) CHK(launch(q, hist_sink(cnt + q * row, nbins, copies)));
     if (copies > 1)
         CHK(timed(d, "hist_reduce", nq * row, [&] {
             return launch_hist_reduce(d->stream, cnt, words, copies, nq, (uint64_t *)d->host_result);
@@ -1049,8 +858,7 @@ int iris_template_histogram(iris_engine_t *e, const iris_db_t *db, uint64_t firs
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
     return hist_run(d, n, nbins, bins, invalid, 1, [&](uint32_t, const MatchSink &hs) {
-        return db->k.layout == IRIS_LAYOUT_TILES ? launch_template_mfma_hist(d->hooks, d->stream, db->data, e->qfrag, r, hs)
-                                                 : launch_template_hist(d->stream, db->data, e->qtab, r, hs);
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, kSelHist, hs);
     });
 }
 
@@ -1065,12 +873,7 @@ int iris_template_batch_histogram(iris_engine_t *e, const iris_db_t *db, uint64_
                                   uint64_t *bins, uint64_t *invalid) {
     IRIS_KEEP_DEVICE();
     CHK(hist_args(nbins, bins, invalid));  // the value arguments first: refused whatever the handles
-    ARG(e && db, "NULL argument");
-    ARG(e->kind == IRIS_KIND_TEMPLATES && e->nq > 0, "not a batched template engine");
-    ARG(db->k.kind == IRIS_KIND_TEMPLATES, "database does not hold templates");
-    ARG(db->k.layout == IRIS_LAYOUT_TILES || !e->sub.empty(),
-        "batched search of more than 3 queries needs a template database in the TILES layout");
-    ARG(e->dev == db->dev, "engine and database live on different devices");
+    CHK(template_batch_args(e, db));
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
@@ -1079,16 +882,9 @@ int iris_template_batch_histogram(iris_engine_t *e, const iris_db_t *db, uint64_
     const LaunchRange r{first, n};
     if (!e->sub.empty())
         return hist_run(d, n, nbins, bins, invalid, nq, [&](uint32_t q, const MatchSink &hs) {
-            const iris_engine *c = e->sub[q];
-            return db->k.layout == IRIS_LAYOUT_TILES
-                       ? launch_template_mfma_hist(d->hooks, d->stream, db->data, c->qfrag, r, hs)
-                       : launch_template_hist(d->stream, db->data, c->qtab, r, hs);
+            return launch_template_select(d, db, e->sub[q]->qtab, e->sub[q]->qfrag, r, kSelHist, hs);
         });
-    if (n == 0) {
-        memset(bins, 0, (size_t)nq * nbins * sizeof(uint64_t));
-        memset(invalid, 0, nq * sizeof(uint64_t));
-        return 0;
-    }
+    if (n == 0) return hist_empty(nq, nbins, bins, invalid);
     const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
     const size_t words = (size_t)nbins + 1, rows = (size_t)geo.nqg * geo.qper;
     CHK(ensure(d, d->match_count, rows * words * sizeof(uint64_t)));

@@ -280,17 +280,6 @@ struct Readahead {
     uint64_t grow = 0;  // records of the walk's latest window (the next one is twice its chunks)
 };
 
-// iris_template_search_async .. iris_pending_wait; iris_template_matches_async's handle extends it
-// (iris_pending_matches, iris_api_select.hip), as does iris_template_topk_async's (iris_pending_topk),
-// and `kind` tells each wait which one it was given
-struct iris_pending {
-    ShareKind kind = kShareSearch;
-    iris_device *dev = nullptr;
-    hipEvent_t ev = nullptr;          // recorded after the reduce (null for an empty range)
-    iris::Partial *slot = nullptr;    // pinned host slot the reduce writes
-    uint64_t n = 0, base = 0;         // range size; index_base + first
-};
-
 struct iris_engine {
     iris_device *dev = nullptr;
     int kind = 0;             // IRIS_KIND_* of the DB it runs against
@@ -635,10 +624,20 @@ inline void match_list(iris::Partial *recs, uint64_t total, uint64_t take, uint6
     for (uint64_t i = 0; i < take; ++i) match_from(recs[i], true, base, &out[i]);
 }
 
+// The valid prefix of a top-k list of k records (sorted, the empty entries -- den = 0 -- last) ->
+// iris_match_t as match_from fills them; returns its length.  Inline for match_from's reason.
+inline uint32_t topk_list(const iris::Partial *res, uint32_t k, uint64_t base, iris_match_t *out) {
+    uint32_t c = 0;
+    while (c < k && res[c].den != 0) ++c;
+    for (uint32_t i = 0; i < c; ++i) match_from(res[i], true, base, &out[i]);
+    return c;
+}
+
 // Argument checks that entry points of several files share (each defined in the file named); a
 // call sits where its entry point's order of checks, and so the message that wins, stays as it is.
 int range_ok(const iris_db *db, uint64_t first, uint64_t n);  // iris_api.hip
 int template_args(iris_engine *e, const iris_db *db);         // iris_api_search.hip: a single-query template engine
+int template_batch_args(iris_engine *e, const iris_db *db);   // iris_api_search.hip: a batched template engine
 int masks_batch_args(iris_engine *e, const iris_db *db);      // iris_api_engines.hip: a masks batch engine
 // iris_api_resolver.hip: the resolver calls' share arrays; a single-query masks engine; and the masks
 // kernel of a LANES database into d->out_a, the denominators of the *_masks calls
