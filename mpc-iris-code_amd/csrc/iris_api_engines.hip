@@ -842,7 +842,7 @@ static int enqueue_masks_batch(iris_engine *e, const iris_db *db, uint64_t first
             CHK(enqueue_u16_engine(u.one, db, first, n, o + u.q0 * w.slab));
         } else {
             CHK(timed(d, "masks_batch", n * u.m, [&] {
-                return launch_masks_batch(d->hooks, d->stream, db->data, u.frags, u.m, w.r, o + u.q0 * w.slab, nullptr);
+                return launch_masks_batch(Pass::Search, d->hooks, d->stream, db->data, u.frags, u.m, w.r, o + u.q0 * w.slab);
             }));
         }
     }

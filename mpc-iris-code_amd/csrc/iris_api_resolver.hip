@@ -63,7 +63,7 @@ int iris_resolver_search(iris_device_t *d, const uint16_t *const *shares, uint32
     const uint32_t np = resolver_partials(n);
     CHK(ensure(d, d->partials, (size_t)std::max<uint32_t>(np, 1) * sizeof(Partial)));
     CHK(timed(d, "resolver", n, [&] {
-        return launch_resolver(d->stream, shares, parts, denoms, n, dist_out_device, (Partial *)d->partials.p);
+        return launch_resolver(Pass::Search, d->stream, shares, parts, denoms, n, {dist_out_device, (Partial *)d->partials.p});
     }));
     Partial res{};
     CHK(resolver_finish(d, n ? np : 0, &res));
@@ -93,8 +93,8 @@ int iris_resolver_search_masks(iris_engine_t *e, const iris_db_t *db, uint64_t f
         const uint32_t np = n ? masks_resolve_partials(d->hooks, r) : 0;
         CHK(ensure(d, d->partials, (size_t)std::max<uint32_t>(np, 1) * sizeof(Partial)));
         CHK(timed(d, "masks_resolve", n, [&] {
-            return launch_masks_resolve(d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts, dist_out_device,
-                                        (Partial *)d->partials.p);
+            return launch_masks_resolve(Pass::Search, d->hooks, d->stream, db->data, e->qfrag, r, shares_device, parts,
+                                        {dist_out_device, (Partial *)d->partials.p});
         }));
         CHK(resolver_finish(d, np, &res));
     } else {
@@ -103,7 +103,7 @@ int iris_resolver_search_masks(iris_engine_t *e, const iris_db_t *db, uint64_t f
         const uint32_t np = resolver_partials(n);
         CHK(ensure(d, d->partials, (size_t)std::max<uint32_t>(np, 1) * sizeof(Partial)));
         CHK(timed(d, "resolver", n, [&] {
-            return launch_resolver(d->stream, shares_device, parts, den, n, dist_out_device, (Partial *)d->partials.p);
+            return launch_resolver(Pass::Search, d->stream, shares_device, parts, den, n, {dist_out_device, (Partial *)d->partials.p});
         }));
         CHK(resolver_finish(d, n ? np : 0, &res));
     }
@@ -148,7 +148,7 @@ int iris_resolver_batch_search_masks(iris_engine_t *e, const iris_db_t *db, uint
             const MasksBatchResolve rs{shares_device, parts, u.q0, dist_out_device, pq, stride};
             uint32_t np = 0;
             CHK(timed(d, "masks_batch_resolve", n * u.m, [&] {
-                return launch_masks_batch(d->hooks, d->stream, db->data, u.frags, u.m, w.r, nullptr, &rs, &np);
+                return launch_masks_batch(Pass::Search, d->hooks, d->stream, db->data, u.frags, u.m, w.r, {rs, &np});
             }));
             for (uint32_t s = 0; s < u.m; ++s) CHK(reduce(u.q0 + s, np));
             continue;
@@ -159,13 +159,13 @@ int iris_resolver_batch_search_masks(iris_engine_t *e, const iris_db_t *db, uint
         double *dist = dist_out_device ? dist_out_device + (uint64_t)u.q0 * n : nullptr;
         if (w.tiles) {
             CHK(timed(d, "masks_resolve", n, [&] {
-                return launch_masks_resolve(d->hooks, d->stream, db->data, u.one->qfrag, w.r, sl, parts, dist, pq);
+                return launch_masks_resolve(Pass::Search, d->hooks, d->stream, db->data, u.one->qfrag, w.r, sl, parts, {dist, pq});
             }));
             CHK(reduce(u.q0, masks_resolve_partials(d->hooks, w.r)));
         } else {
             const uint16_t *den = nullptr;
             CHK(enqueue_masks_denoms(u.one, db, w.r, &den));
-            CHK(timed(d, "resolver", n, [&] { return launch_resolver(d->stream, sl, parts, den, n, dist, pq); }));
+            CHK(timed(d, "resolver", n, [&] { return launch_resolver(Pass::Search, d->stream, sl, parts, den, n, {dist, pq}); }));
             CHK(reduce(u.q0, resolver_partials(n)));
         }
     }
@@ -244,8 +244,8 @@ int iris_resolver_search_masks_host(iris_engine_t *e, const iris_db_t *db, uint6
         const LaunchRange r{first + a, m};
         const uint32_t np = masks_resolve_partials(d->hooks, r);
         rc = timed(d, "masks_resolve", m, [&] {
-            return launch_masks_resolve(d->hooks, d->stream, db->data, e->qfrag, r, &dsum, 1, nullptr,
-                                        (Partial *)d->partials.p);
+            return launch_masks_resolve(Pass::Search, d->hooks, d->stream, db->data, e->qfrag, r, &dsum, 1,
+                                        {nullptr, (Partial *)d->partials.p});
         });
         // the chunk's winner, its index offset to the call's records, into result slot c
         if (rc == 0)
@@ -313,7 +313,7 @@ static int resolver_host_pinned(iris_device *d, const uint16_t *const *shares, u
         const uint16_t *dden = (const uint16_t *)(stage + m * row);
         const uint32_t np = resolver_partials(m);
         rc = timed(d, "resolver", m, [&] {
-            return launch_resolver(d->stream, &dsum, 1, dden, m, nullptr, (Partial *)d->partials.p);
+            return launch_resolver(Pass::Search, d->stream, &dsum, 1, dden, m, {nullptr, (Partial *)d->partials.p});
         });
         // the chunk's winner, its index offset to the call's records, into result slot c
         if (rc == 0)

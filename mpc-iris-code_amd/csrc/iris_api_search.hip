@@ -160,8 +160,8 @@ int iris_api::search_enqueue(iris_engine_t *e, const iris_db_t *db, uint64_t fir
         const FusedFinish fin{(uint32_t *)d->ticket.p, dst, idx_base, host_done, seq};
         uint32_t written = 0;
         CHK(timed(d, "template_search", n, [&] {
-            return launch_template_mfma_search(d->hooks, d->stream, db->data, e->qfrag, r, dist_dev, (Partial *)d->partials.p,
-                                               &written, &fin);
+            return launch_template_mfma(Pass::Search, d->hooks, d->stream, db->data, e->qfrag, r,
+                                        {dist_dev, (Partial *)d->partials.p}, &written, &fin);
         }));
         if (flagged) *flagged = host_done != nullptr;
         if (!side) return 0;
@@ -200,15 +200,15 @@ int iris_api::search_enqueue(iris_engine_t *e, const iris_db_t *db, uint64_t fir
         CHK(share_join(d, share_host, db, first, n, np, e->host_query, d->apart_read[b], kShareSearch, part, nullptr,
                        &j));
         CHK(timed(d, "template_search", n, [&] {
-            return launch_template_share_search(d->hooks, d->stream, db->data, e->qfrag, r, part, &written,
-                                                j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
+            return launch_template_share(Pass::Search, d->hooks, d->stream, db->data, e->qfrag, r, {nullptr, part}, &written,
+                                         j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
         }));
         CHK(share_launched(d, j));
     } else {
         CHK(timed(d, "template_search", n, [&] {
             if (layout == IRIS_LAYOUT_TILES)
-                return launch_template_mfma_search(d->hooks, d->stream, db->data, e->qfrag, r, dist_dev, part, &written);
-            return launch_template_search(d->stream, db->data, e->qtab, r, dist_dev, part, &written);
+                return launch_template_mfma(Pass::Search, d->hooks, d->stream, db->data, e->qfrag, r, {dist_dev, part}, &written);
+            return launch_template(Pass::Search, d->stream, db->data, e->qtab, r, {dist_dev, part}, &written);
         }));
     }
     if (!side)  // the reduce writes the winner straight into pinned host memory: no copy before the wait
@@ -243,8 +243,8 @@ int iris_template_counts(iris_engine_t *e, const iris_db_t *db, uint64_t first, 
         uint16_t *da = den_out ? (uint16_t *)d->out_b.p : nullptr;
         CHK(timed(d, "template_counts", m, [&] {
             return db->k.layout == IRIS_LAYOUT_TILES
-                       ? launch_template_mfma_counts(d->hooks, d->stream, db->data, e->qfrag, r, na, da)
-                       : launch_template_counts(d->stream, db->data, e->qtab, r, na, da);
+                       ? launch_template_mfma(Pass::Counts, d->hooks, d->stream, db->data, e->qfrag, r, {na, da})
+                       : launch_template(Pass::Counts, d->stream, db->data, e->qtab, r, {na, da});
         }));
         if (num_out)
             HIPCHK(hipMemcpyAsync(num_out + done * kRot, d->out_a.p, m * kRot * 2, hipMemcpyDeviceToHost, d->stream));
@@ -401,8 +401,8 @@ int iris_template_batch_search(iris_engine_t *e, const iris_db_t *db, uint64_t f
         CHK(ensure(d, d->partials, (size_t)nqp * geo.G * sizeof(Partial)));
         CHK(ensure_host_result(d, (size_t)nqp * sizeof(Partial)));
         CHK(timed(d, "template_batch", n * e->nq, [&] {
-            return launch_batch(d->hooks, d->stream, db->data, e->qfrag, r, geo, (Partial *)d->partials.p,
-                                (Partial *)d->host_result);
+            return launch_batch(Pass::Search, d->hooks, d->stream, db->data, e->qfrag, r, geo,
+                                {(Partial *)d->partials.p, (Partial *)d->host_result});
         }));
     }
     CHK(sync(d));

@@ -14,28 +14,25 @@ extern "C" {
 
 // ------------------------------------------------------------------ the single-query passes
 
-// What a pass does with a record's distance; all three take a MatchSink (a match sink, topk_sink,
-// hist_sink)
-enum SelectMode { kSelMatch, kSelTopk, kSelHist };
+// The kernel_stats name of a family's select pass; NULL for a mode the family has no pass for.
+static const char *pass_name(Pass p, const char *match, const char *topk, const char *hist = nullptr) {
+    switch (p) {
+    case Pass::Match: return match;
+    case Pass::Topk: return topk;
+    case Pass::Hist: return hist;
+    default: return nullptr;
+    }
+}
 
 // One single-query template pass over r on the device stream, timed under its mode's name: the MFMA
 // kernel on a TILES database (the engine's qfrag), the LANES kernel otherwise (its qtab).
 static int launch_template_select(iris_device *d, const iris_db *db, const void *qtab, const void *qfrag, LaunchRange r,
-                                  SelectMode mode, const MatchSink &sink) {
-    static const char *const names[] = {"template_match", "template_topk", "template_hist"};
-    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
-    return timed(d, names[mode], r.n, [&] {
-        switch (mode) {
-        case kSelMatch:
-            return tiles ? launch_template_mfma_match(d->hooks, d->stream, db->data, qfrag, r, sink)
-                         : launch_template_match(d->stream, db->data, qtab, r, sink);
-        case kSelTopk:
-            return tiles ? launch_template_mfma_topk(d->hooks, d->stream, db->data, qfrag, r, sink)
-                         : launch_template_topk(d->stream, db->data, qtab, r, sink);
-        default:
-            return tiles ? launch_template_mfma_hist(d->hooks, d->stream, db->data, qfrag, r, sink)
-                         : launch_template_hist(d->stream, db->data, qtab, r, sink);
-        }
+                                  Pass p, const MatchSink &sink) {
+    const char *name = pass_name(p, "template_match", "template_topk", "template_hist");
+    if (!name) return fail(IRIS_E_ARG, "no template pass of that mode");
+    return timed(d, name, r.n, [&] {
+        return db->k.layout == IRIS_LAYOUT_TILES ? launch_template_mfma(p, d->hooks, d->stream, db->data, qfrag, r, sink)
+                                                 : launch_template(p, d->stream, db->data, qtab, r, sink);
     });
 }
 
@@ -45,19 +42,18 @@ static int launch_template_select(iris_device *d, const iris_db *db, const void 
 // enqueued -- a caller that launches again (the rerun of an overflowing list) while the workspace
 // is still theirs keeps it, and they are not computed twice.
 static int masks_single_launch(iris_device *d, const iris_engine *c, const iris_db *db, LaunchRange r,
-                               const uint16_t *const *shares, uint32_t parts, SelectMode mode, const MatchSink &sink,
+                               const uint16_t *const *shares, uint32_t parts, Pass p, const MatchSink &sink,
                                const uint16_t **den) {
-    const bool match = mode == kSelMatch;
-    if (db->k.layout == IRIS_LAYOUT_TILES)
-        return timed(d, match ? "masks_match" : "masks_topk", r.n, [&] {
-            return match ? launch_masks_match(d->hooks, d->stream, db->data, c->qfrag, r, shares, parts, sink)
-                         : launch_masks_topk(d->hooks, d->stream, db->data, c->qfrag, r, shares, parts, sink);
+    const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
+    const char *name = pass_name(p, tiles ? "masks_match" : "resolver_match", tiles ? "masks_topk" : "resolver_topk");
+    if (!name) return fail(IRIS_E_ARG, "no masks pass of that mode");
+    if (tiles)
+        return timed(d, name, r.n, [&] {
+            return launch_masks_resolve(p, d->hooks, d->stream, db->data, c->qfrag, r, shares, parts, sink);
         });
     if (!*den) CHK(enqueue_masks_denoms(c, db, r, den));
-    return timed(d, match ? "resolver_match" : "resolver_topk", r.n, [&] {
-        return match ? launch_resolver_match(d->stream, shares, parts, *den, r.n, sink)
-                     : launch_resolver_topk(d->stream, shares, parts, *den, r.n, sink);
-    });
+    return timed(d, name, r.n,
+                 [&] { return launch_resolver(p, d->stream, shares, parts, *den, r.n, sink); });
 }
 
 // The pass of a pipelined match (kShareMatch) or top-k (kShareTopk) call over r into ms, on the
@@ -68,6 +64,7 @@ static int masks_single_launch(iris_device *d, const iris_engine *c, const iris_
 static int select_pass_enqueue(iris_device *d, const iris_db *db, LaunchRange r, const void *qtab, const void *qfrag,
                                const iris_template_t *query, ShareKind kind, const MatchSink &ms, bool shared) {
     const bool match = kind == kShareMatch;
+    const Pass p = match ? Pass::Match : Pass::Topk;
     if (shared && db->k.layout == IRIS_LAYOUT_TILES && share_search_ok(d->hooks, r)) {
         ShareJoin j;
         CHK(share_join(d, d->share_last, db, r.first, r.n, mfma_search_partials(d->hooks, r), query, nullptr, kind, nullptr,
@@ -76,14 +73,14 @@ static int select_pass_enqueue(iris_device *d, const iris_db *db, LaunchRange r,
         // a match pass's counter: share_join zeroes it on the sharing stream, but only with a ring entry
         if (match && !j.sp) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
         CHK(timed(d, match ? "template_match" : "template_topk", r.n, [&] {
-            return (match ? launch_template_share_match : launch_template_share_topk)(
-                d->hooks, d->stream, db->data, qfrag, r, ms, j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
+            return launch_template_share(p, d->hooks, d->stream, db->data, qfrag, r, ms, nullptr,
+                                         j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
         }));
         return share_launched(d, j);
     }
     d->share_last = -1;  // only the device's latest pass can host
     if (match) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
-    return launch_template_select(d, db, qtab, qfrag, r, match ? kSelMatch : kSelTopk, ms);
+    return launch_template_select(d, db, qtab, qfrag, r, p, ms);
 }
 
 // ------------------------------------------------------------------ threshold matching
@@ -234,7 +231,7 @@ int iris_template_matches(iris_engine_t *e, const iris_db_t *db, uint64_t first,
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
     return matches_run(d, n, index_base + first, threshold, out, cap, count, [&](const MatchSink &ms) {
-        return launch_template_select(d, db, e->qtab, e->qfrag, r, kSelMatch, ms);
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Match, ms);
     });
 }
 
@@ -369,7 +366,7 @@ int iris_resolver_matches(iris_device_t *d, const uint16_t *const *shares, uint3
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
     return matches_run(d, n, index_base, threshold, out, cap, count, [&](const MatchSink &ms) {
-        return timed(d, "resolver_match", n, [&] { return launch_resolver_match(d->stream, shares, parts, denoms, n, ms); });
+        return timed(d, "resolver_match", n, [&] { return launch_resolver(Pass::Match, d->stream, shares, parts, denoms, n, ms); });
     });
 }
 
@@ -390,7 +387,7 @@ int iris_resolver_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t 
     const LaunchRange r{first, n};
     const uint16_t *den = nullptr;
     return matches_run(d, n, index_base, threshold, out, cap, count, [&](const MatchSink &ms) {
-        return masks_single_launch(d, e, db, r, shares_device, parts, kSelMatch, ms, &den);
+        return masks_single_launch(d, e, db, r, shares_device, parts, Pass::Match, ms, &den);
     });
 }
 
@@ -441,7 +438,7 @@ int iris_template_topk(iris_engine_t *e, const iris_db_t *db, uint64_t first, ui
     const LaunchRange r{first, n};
     const uint64_t units = n ? template_topk_lists(d, db, r) : 0;
     return topk_run(d, n, index_base + first, k, out, count, units, [&](const MatchSink &ts) {
-        return launch_template_select(d, db, e->qtab, e->qfrag, r, kSelTopk, ts);
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Topk, ts);
     });
 }
 
@@ -510,7 +507,7 @@ int iris_resolver_topk(iris_device_t *d, const uint16_t *const *shares, uint32_t
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
     return topk_run(d, n, index_base, k, out, count, resolver_topk_units(n), [&](const MatchSink &ts) {
-        return timed(d, "resolver_topk", n, [&] { return launch_resolver_topk(d->stream, shares, parts, denoms, n, ts); });
+        return timed(d, "resolver_topk", n, [&] { return launch_resolver(Pass::Topk, d->stream, shares, parts, denoms, n, ts); });
     });
 }
 
@@ -532,7 +529,7 @@ int iris_resolver_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t fir
     const uint64_t units = db->k.layout != IRIS_LAYOUT_TILES ? resolver_topk_units(n) : n ? masks_topk_units(d->hooks, r) : 0;
     const uint16_t *den = nullptr;
     return topk_run(d, n, index_base, k, out, count, units, [&](const MatchSink &ts) {
-        return masks_single_launch(d, e, db, r, shares_device, parts, kSelTopk, ts, &den);
+        return masks_single_launch(d, e, db, r, shares_device, parts, Pass::Topk, ts, &den);
     });
 }
 
@@ -596,7 +593,7 @@ static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k,
 // iris_resolver_batch_search_masks' top-k sibling, with iris_resolver_batch_matches_masks' dispatch:
 // TILES ranges the batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass
 // of masks_batch_kernel<BATCH_TOPK> ("masks_batch_topk") storing every wave's list per query, a
-// single left-over query one launch_masks_topk on its slab; other TILES ranges one launch_masks_topk
+// single left-over query one fused single-query pass on its slab; other TILES ranges one such pass
 // per query; LANES the masks kernel into the workspace and the resolver top-k kernel per query.
 int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
                                    const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base, uint32_t k,
@@ -618,8 +615,8 @@ int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64
         if (u.m > 1) {
             units.push_back(TopkUnit{u.q0, u.m, masks_batch_topk_units(d->hooks, w.r, u.m), [=](Partial *lists, uint64_t stride) {
                 return timed(d, "masks_batch_topk", n * u.m, [&] {
-                    return launch_masks_batch_topk(d->hooks, d->stream, db->data, u.frags, u.m, w.r, shares_device, parts,
-                                                   u.q0, lists, stride, k);
+                    return launch_masks_batch(Pass::Topk, d->hooks, d->stream, db->data, u.frags, u.m, w.r,
+                                              {shares_device, parts, u.q0, lists, stride, k});
                 });
             }});
         } else {
@@ -628,7 +625,7 @@ int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64
             units.push_back(TopkUnit{u.q0, 1, lists, [=](Partial *buf, uint64_t) {
                 const uint16_t *sl[8], *den = nullptr;
                 w.slabs(u.q0, shares_device, parts, sl);
-                return masks_single_launch(d, u.one, db, w.r, sl, parts, kSelTopk, topk_sink(buf, k), &den);
+                return masks_single_launch(d, u.one, db, w.r, sl, parts, Pass::Topk, topk_sink(buf, k), &den);
             }});
         }
     }
@@ -638,7 +635,7 @@ int iris_resolver_batch_topk_masks(iris_engine_t *e, const iris_db_t *db, uint64
 // iris_resolver_batch_search_masks' threshold sibling, and that call's dispatch: TILES ranges the
 // batch kernel runs walk the queries in groups of kMasksBatchG, each group one pass of
 // masks_batch_kernel<BATCH_MATCH> ("masks_batch_match") appending to the group's sinks, a single
-// left-over query one launch_masks_match; other TILES ranges one launch_masks_match per query; LANES
+// left-over query one fused single-query pass; other TILES ranges one such pass per query; LANES
 // the masks kernel into the workspace and the resolver match kernel per query.  A launch unit -- a
 // group or a single query -- is what matches_run_units runs again when one of its lists overflows.
 int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
@@ -659,8 +656,8 @@ int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uin
         if (u.m > 1) {
             units.push_back(MatchUnit{u.q0, u.m, [=](const MatchSink *ms) {
                 return timed(d, "masks_batch_match", n * u.m, [&] {
-                    return launch_masks_batch_match(d->hooks, d->stream, db->data, u.frags, u.m, w.r, shares_device, parts,
-                                                    u.q0, ms);
+                    return launch_masks_batch(Pass::Match, d->hooks, d->stream, db->data, u.frags, u.m, w.r,
+                                              {shares_device, parts, u.q0, ms});
                 });
             }});
         } else {
@@ -668,7 +665,7 @@ int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uin
             units.push_back(MatchUnit{u.q0, 1, [=](const MatchSink *ms) {
                 const uint16_t *sl[8], *den = nullptr;
                 w.slabs(u.q0, shares_device, parts, sl);
-                return masks_single_launch(d, u.one, db, w.r, sl, parts, kSelMatch, ms[0], &den);
+                return masks_single_launch(d, u.one, db, w.r, sl, parts, Pass::Match, ms[0], &den);
             }});
         }
     }
@@ -703,7 +700,7 @@ int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t 
         for (uint32_t q = 0; n && q < nq; ++q) {
             const iris_engine *c = e->sub[q];
             units.push_back(MatchUnit{q, 1, [=](const MatchSink *ms) {
-                return launch_template_select(d, db, c->qtab, c->qfrag, r, kSelMatch, ms[0]);
+                return launch_template_select(d, db, c->qtab, c->qfrag, r, Pass::Match, ms[0]);
             }});
         }
         return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, nullptr, kBatchMatchBudget);
@@ -729,8 +726,8 @@ int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t 
         HIPCHK(hipMemcpyAsync((void *)(dsinks + q0), stage, mp * sizeof(MatchSink), hipMemcpyHostToDevice, d->stream));
         const BatchGeometry geo = batch_geometry(d->hooks, r, m);
         return timed(d, "template_batch_match", n * m, [&] {
-            return launch_batch_match(d->hooks, d->stream, db->data, (const char *)e->qfrag + q0 * tile_bytes, r, geo,
-                                      dsinks + q0);
+            return launch_batch(Pass::Match, d->hooks, d->stream, db->data, (const char *)e->qfrag + q0 * tile_bytes, r, geo,
+                                dsinks + q0);
         });
     };
     for (uint32_t q0 = 0; n && q0 < nq; q0 += bq) {
@@ -768,7 +765,7 @@ int iris_template_batch_topk(iris_engine_t *e, const iris_db_t *db, uint64_t fir
         for (uint32_t q = 0; n && q < nq; ++q) {
             const iris_engine *c = e->sub[q];
             units.push_back(TopkUnit{q, 1, lists, [=](Partial *buf, uint64_t) {
-                return launch_template_select(d, db, c->qtab, c->qfrag, r, kSelTopk, topk_sink(buf, k));
+                return launch_template_select(d, db, c->qtab, c->qfrag, r, Pass::Topk, topk_sink(buf, k));
             }});
         }
         return topk_run_units(d, n, base, k, out, counts, nq, units);
@@ -777,7 +774,7 @@ int iris_template_batch_topk(iris_engine_t *e, const iris_db_t *db, uint64_t fir
         const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
         units.push_back(TopkUnit{0, nq, batch_topk_units(geo), [=](Partial *lists, uint64_t stride) {
             return timed(d, "template_batch_topk", n * nq, [&] {
-                return launch_batch_topk(d->hooks, d->stream, db->data, e->qfrag, r, geo, lists, stride, k);
+                return launch_batch(Pass::Topk, d->hooks, d->stream, db->data, e->qfrag, r, geo, {lists, stride, k});
             });
         }, geo.nqg * geo.qper - nq});
     }
@@ -858,7 +855,7 @@ int iris_template_histogram(iris_engine_t *e, const iris_db_t *db, uint64_t firs
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
     return hist_run(d, n, nbins, bins, invalid, 1, [&](uint32_t, const MatchSink &hs) {
-        return launch_template_select(d, db, e->qtab, e->qfrag, r, kSelHist, hs);
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Hist, hs);
     });
 }
 
@@ -882,7 +879,7 @@ int iris_template_batch_histogram(iris_engine_t *e, const iris_db_t *db, uint64_
     const LaunchRange r{first, n};
     if (!e->sub.empty())
         return hist_run(d, n, nbins, bins, invalid, nq, [&](uint32_t q, const MatchSink &hs) {
-            return launch_template_select(d, db, e->sub[q]->qtab, e->sub[q]->qfrag, r, kSelHist, hs);
+            return launch_template_select(d, db, e->sub[q]->qtab, e->sub[q]->qfrag, r, Pass::Hist, hs);
         });
     if (n == 0) return hist_empty(nq, nbins, bins, invalid);
     const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
@@ -892,7 +889,7 @@ int iris_template_batch_histogram(iris_engine_t *e, const iris_db_t *db, uint64_
     uint64_t *cnt = (uint64_t *)d->match_count.p;
     HIPCHK(hipMemsetAsync(cnt, 0, rows * words * sizeof(uint64_t), d->stream));
     CHK(timed(d, "template_batch_hist", n * nq,
-              [&] { return launch_batch_hist(d->hooks, d->stream, db->data, e->qfrag, r, geo, cnt, nbins); }));
+              [&] { return launch_batch(Pass::Hist, d->hooks, d->stream, db->data, e->qfrag, r, geo, {cnt, nbins}); }));
     HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
     CHK(sync(d));
     return hist_finish(d, n, nbins, nq, bins, invalid);

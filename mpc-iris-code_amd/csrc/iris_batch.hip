@@ -536,57 +536,37 @@ BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq) {
     return g;
 }
 
-int launch_batch(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r, const BatchGeometry &g,
-                 Partial *partials, Partial *out, uint64_t idx_base) {
-    if (r.n == 0) return 0;
-    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4> : batch_lds_kernel<8, 2, 2, 2>;
-    hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
-                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G, partials);
-    if (hipGetLastError() != hipSuccess) return -1;
-    hipLaunchKernelGGL(batch_reduce_kernel, dim3(g.nqg * g.qper), dim3(256), 0, (hipStream_t)stream, partials, g.G, out,
-                       idx_base);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// The threshold-match form of that pass: g = batch_geometry of the queries qtiles holds, sinks = the
-// device array of their g.nqg * g.qper MatchSinks (counters zeroed on the stream by the caller).
-// One launch, no reduce.
-int launch_batch_match(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
-                       const BatchGeometry &g, const MatchSink *sinks) {
-    if (r.n == 0) return 0;
-    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_MATCH> : batch_lds_kernel<8, 2, 2, 2, BL_MATCH>;
-    hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
-                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G, sinks);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// The histogram form of that pass: counts = the device array of g.nqg * g.qper rows of nbins + 1
-// counters.  One launch, no reduce.
-int launch_batch_hist(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
-                      const BatchGeometry &g, uint64_t *counts, uint32_t nbins) {
-    if (r.n == 0) return 0;
-    if (nbins == 0 || nbins > kHistMaxBins || (nbins & (nbins - 1))) return -1;
-    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_HIST> : batch_lds_kernel<8, 2, 2, 2, BL_HIST>;
-    hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
-                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G,
-                       BatchHistRows{counts, nbins});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// The top-k form of that pass: every wave of the grid stores its k best records of query q of g
-// (g.nqg * g.qper queries, in qtiles' order) at lists + q * stride + unit * k;
-// batch_topk_units = the lists per query.  One launch, no reduce; nothing needs zeroing.
 uint64_t batch_topk_units(const BatchGeometry &g) { return (uint64_t)g.G * 8; }
 
-int launch_batch_topk(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
-                      const BatchGeometry &g, Partial *lists, uint64_t stride, uint32_t k) {
-    if (r.n == 0) return 0;
-    if (k == 0 || k > kTopkMax || stride < batch_topk_units(g) * k) return -1;
-    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, BL_TOPK> : batch_lds_kernel<8, 2, 2, 2, BL_TOPK>;
+// The one launch of batch_lds_kernel: `out` is the mode's operand (the partials, the device sinks,
+// BatchTopkLists or BatchHistRows), the shape IRIS_BATCH_KERNEL's.
+template <int MODE>
+static int batch_pass(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                      const BatchGeometry &g, typename BatchOut<MODE>::type out) {
+    auto kern = batch_kernel_choice(h) == 2 ? batch_lds_kernel<8, 1, 4, 4, MODE> : batch_lds_kernel<8, 2, 2, 2, MODE>;
     hipLaunchKernelGGL(kern, dim3(g.nqg * g.G), dim3(64 * 8), 0, (hipStream_t)stream, (const uint4 *)db,
-                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G,
-                       BatchTopkLists{lists, stride, k});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+                       (const uint4 *)qtiles, g.tile0, g.ntiles, r.first, r.first + r.n, g.nqg, g.G, out);
+    return check_launch();
+}
+
+int launch_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                 const BatchGeometry &g, const BatchPassOut &o) {
+    if (r.n == 0) return 0;
+    switch (p) {
+    case Pass::Search:
+        if (batch_pass<BL_SEARCH>(h, stream, db, qtiles, r, g, o.partials) != 0) return -1;
+        hipLaunchKernelGGL(batch_reduce_kernel, dim3(g.nqg * g.qper), dim3(256), 0, (hipStream_t)stream, o.partials, g.G,
+                           o.out, o.idx_base);
+        return check_launch();
+    case Pass::Match: return batch_pass<BL_MATCH>(h, stream, db, qtiles, r, g, o.sinks);
+    case Pass::Topk:
+        if (o.k == 0 || o.k > kTopkMax || o.stride < batch_topk_units(g) * o.k) return -1;
+        return batch_pass<BL_TOPK>(h, stream, db, qtiles, r, g, BatchTopkLists{o.lists, o.stride, o.k});
+    case Pass::Hist:
+        if (o.nbins == 0 || o.nbins > kHistMaxBins || (o.nbins & (o.nbins - 1))) return -1;
+        return batch_pass<BL_HIST>(h, stream, db, qtiles, r, g, BatchHistRows{o.counts, o.nbins});
+    default: return -1;
+    }
 }
 
 }  // namespace iris

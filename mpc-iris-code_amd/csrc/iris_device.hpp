@@ -22,6 +22,11 @@ static inline uint64_t resident_blocks(int per_cu) {
     return (uint64_t)n * per_cu;
 }
 
+// The template kind's TILES record plumbing (iris_mfma.hip), launched with the other kinds' from
+// launch_*_tiles_kind (iris_engines_mfma.hip): grid-stride loops over n * 2 * kPlaneGroups items
+__global__ void __launch_bounds__(256) pack_tiles_kernel(const uint32_t *__restrict__ staging, uint4 *__restrict__ db, uint64_t t_first, uint64_t n);
+__global__ void __launch_bounds__(256) unpack_tiles_kernel(const uint4 *__restrict__ db, uint32_t *__restrict__ staging, uint64_t t_first, uint64_t n);
+__global__ void __launch_bounds__(256) generate_tiles_kernel(uint4 *__restrict__ db, uint64_t t_first, uint64_t n, uint64_t key, uint64_t global_index0);
 
 typedef unsigned int u32x4_nt __attribute__((ext_vector_type(4)));
 

@@ -370,7 +370,7 @@ int launch_masks_mfma(const Hooks &h, void *stream, const void *db, const void *
         auto kern = packed ? masks_split_kernel<kMasksSplitKS, true> : masks_split_kernel<kMasksSplitKS>;
         hipLaunchKernelGGL(kern, dim3((uint32_t)ntiles), dim3(64 * kMasksSplitKS), 0, (hipStream_t)stream,
                            (const uint4 *)db, (const uint4 *)qfrag, tiles_of(r, 1).tile0, r.first, r.first + r.n, out, s);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        return check_launch();
     }
     const int tpw = tiles_per_wave(h, ntiles, kMasksTiles);
     const Tiles t = tiles_of(r, tpw);
@@ -380,7 +380,7 @@ int launch_masks_mfma(const Hooks &h, void *stream, const void *db, const void *
     hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, out,
                        MaskResolve{});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r) {
@@ -388,57 +388,13 @@ uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r) {
     return (uint32_t)std::min<uint64_t>(t.grid, resident_blocks(masks_blocks_per_cu<MASKS_RESOLVE>()));
 }
 
-int launch_masks_resolve(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                         const uint16_t *const *shares, uint32_t parts, double *dist_out, Partial *partials) {
-    if (r.n == 0) return 0;
-    if (parts == 0 || parts > 8) return -1;
-    const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles);
-    const Tiles t = tiles_of(r, tpw);
-    const uint64_t grid = masks_resolve_partials(h, r);
-    MaskResolve rs{};
-    rs.aligned = true;
-    for (uint32_t p = 0; p < parts; ++p) {
-        rs.shares[p] = shares[p];
-        rs.aligned &= ((uintptr_t)shares[p] & 15) == 0;
-    }
-    rs.parts = parts;
-    rs.dist_out = dist_out;
-    rs.partials = partials;
-    auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_RESOLVE, 1> : masks_mfma_kernel<MASKS_RESOLVE>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, rs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// launch_masks_resolve's dispatch and grid with the MASKS_MATCH epilogue
-int launch_masks_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                       const uint16_t *const *shares, uint32_t parts, const MatchSink &ms) {
-    if (r.n == 0) return 0;
-    if (parts == 0 || parts > 8) return -1;
-    const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles);
-    const Tiles t = tiles_of(r, tpw);
-    const uint64_t grid = masks_resolve_partials(h, r);
-    MaskResolve rs{};
-    rs.aligned = true;
-    for (uint32_t p = 0; p < parts; ++p) {
-        rs.shares[p] = shares[p];
-        rs.aligned &= ((uintptr_t)shares[p] & 15) == 0;
-    }
-    rs.parts = parts;
-    rs.match = ms;
-    auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_MATCH, 1> : masks_mfma_kernel<MASKS_MATCH>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, rs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 uint64_t masks_topk_units(const Hooks &h, LaunchRange r) { return (uint64_t)masks_resolve_partials(h, r) * kWaveSlots; }
 
-// launch_masks_resolve's dispatch and grid with the MASKS_TOPK epilogue
-int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                      const uint16_t *const *shares, uint32_t parts, const MatchSink &ts) {
+// The one dispatch of masks_mfma_kernel's resolving modes: masks_resolve_partials' grid, one or
+// kResolveTiles tiles per wave, the parts' alignment found once.
+template <int MODE>
+static int masks_resolve_pass(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                              const uint16_t *const *shares, uint32_t parts, const PassOut &o) {
     if (r.n == 0) return 0;
     if (parts == 0 || parts > 8) return -1;
     const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles);
@@ -451,12 +407,25 @@ int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *
         rs.aligned &= ((uintptr_t)shares[p] & 15) == 0;
     }
     rs.parts = parts;
-    rs.match = ts;
-    auto kern = tpw == 1 ? masks_mfma_kernel<MASKS_TOPK, 1> : masks_mfma_kernel<MASKS_TOPK>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
+    rs.dist_out = o.dist_out;
+    rs.partials = o.partials;
+    rs.match = o.sink;
+    auto kern = tpw == 1 ? masks_mfma_kernel<MODE, 1> : masks_mfma_kernel<MODE>;
+    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
                        (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
                        (uint16_t *)nullptr, rs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
+}
+
+int launch_masks_resolve(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                         const uint16_t *const *shares, uint32_t parts, const PassOut &o) {
+    if (r.n != 0 && !o.fits(p)) return -1;
+    switch (p) {
+    case Pass::Search: return masks_resolve_pass<MASKS_RESOLVE>(h, stream, db, qfrag, r, shares, parts, o);
+    case Pass::Match: return masks_resolve_pass<MASKS_MATCH>(h, stream, db, qfrag, r, shares, parts, o);
+    case Pass::Topk: return masks_resolve_pass<MASKS_TOPK>(h, stream, db, qfrag, r, shares, parts, o);
+    default: return -1;
+    }
 }
 
 // ------------------------------------------------------------------ shares (i8)
@@ -708,14 +677,14 @@ int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void 
                            dim3((uint32_t)((t.ntiles + kSharesSplitT - 1) / kSharesSplitT)), dim3(64 * kSharesSplitKS), 0,
                            (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, qsum, t.tile0, t.ntiles, r.first,
                            r.first + r.n, out, s);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+        return check_launch();
     }
     const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kSharesTiles);
     const Tiles t = tiles_of(r, tpw);
     auto kern = tpw == 1 ? shares_mfma_kernel<1> : shares_mfma_kernel<>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)db,
                        (const uint4 *)qfrag, qsum, t.tile0, t.ntiles, r.first, r.first + r.n, out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 // ------------------------------------------------------------------ TILES plumbing (masks, shares)
@@ -816,50 +785,51 @@ __global__ void __launch_bounds__(256) generate_shares_tiles(uint4 *__restrict__
     }
 }
 
-static int plumb_grid(uint64_t total) {
-    uint64_t b = (total + 255) / 256;
-    if (b > 256ull * 64) b = 256ull * 64;
-    return (int)(b ? b : 1);
-}
-
+// A TILES database's record plumbing, every kind (the template kernels: iris_mfma.hip)
 int launch_pack_tiles_kind(void *stream, int kind, const void *staging, void *db, uint64_t t_first, uint64_t n) {
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (kind == IRIS_KIND_TEMPLATES) return launch_pack_tiles(stream, staging, db, t_first, n);
-    if (kind == IRIS_KIND_MASKS)
-        hipLaunchKernelGGL(pack_masks_tiles, dim3(plumb_grid(n * kMaskChunks / 2)), dim3(256), 0, s,
+    if (kind == IRIS_KIND_TEMPLATES)
+        hipLaunchKernelGGL(pack_tiles_kernel, dim3(grid_stride_blocks(n * 2 * kPlaneGroups)), dim3(256), 0, s,
+                           (const uint32_t *)staging, (uint4 *)db, t_first, n);
+    else if (kind == IRIS_KIND_MASKS)
+        hipLaunchKernelGGL(pack_masks_tiles, dim3(grid_stride_blocks(n * kMaskChunks / 2)), dim3(256), 0, s,
                            (const uint32_t *)staging, (uint4 *)db, t_first, n, 0);
     else
-        hipLaunchKernelGGL(pack_shares_tiles, dim3(plumb_grid(n * 2 * kShareChunks)), dim3(256), 0, s,
+        hipLaunchKernelGGL(pack_shares_tiles, dim3(grid_stride_blocks(n * 2 * kShareChunks)), dim3(256), 0, s,
                            (const uint32_t *)staging, (uint4 *)db, t_first, n, 0);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_unpack_tiles_kind(void *stream, int kind, const void *db, void *staging, uint64_t t_first, uint64_t n) {
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (kind == IRIS_KIND_TEMPLATES) return launch_unpack_tiles(stream, db, staging, t_first, n);
-    if (kind == IRIS_KIND_MASKS)
-        hipLaunchKernelGGL(pack_masks_tiles, dim3(plumb_grid(n * kMaskChunks / 2)), dim3(256), 0, s,
+    if (kind == IRIS_KIND_TEMPLATES)
+        hipLaunchKernelGGL(unpack_tiles_kernel, dim3(grid_stride_blocks(n * 2 * kPlaneGroups)), dim3(256), 0, s,
+                           (const uint4 *)db, (uint32_t *)staging, t_first, n);
+    else if (kind == IRIS_KIND_MASKS)
+        hipLaunchKernelGGL(pack_masks_tiles, dim3(grid_stride_blocks(n * kMaskChunks / 2)), dim3(256), 0, s,
                            (const uint32_t *)staging, (uint4 *)db, t_first, n, 1);
     else
-        hipLaunchKernelGGL(pack_shares_tiles, dim3(plumb_grid(n * 2 * kShareChunks)), dim3(256), 0, s,
+        hipLaunchKernelGGL(pack_shares_tiles, dim3(grid_stride_blocks(n * 2 * kShareChunks)), dim3(256), 0, s,
                            (const uint32_t *)staging, (uint4 *)db, t_first, n, 1);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_generate_tiles_kind(void *stream, int kind, void *db, uint64_t t_first, uint64_t n, uint64_t seed,
                                uint64_t global_index0) {
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (kind == IRIS_KIND_TEMPLATES) return launch_generate_tiles(stream, db, t_first, n, seed, global_index0);
-    if (kind == IRIS_KIND_MASKS)
-        hipLaunchKernelGGL(generate_masks_tiles, dim3(plumb_grid(n * kMaskChunks / 2)), dim3(256), 0, s, (uint4 *)db,
+    if (kind == IRIS_KIND_TEMPLATES)
+        hipLaunchKernelGGL(generate_tiles_kernel, dim3(grid_stride_blocks(n * 2 * kPlaneGroups)), dim3(256), 0, s,
+                           (uint4 *)db, t_first, n, gen_key(seed, 0), global_index0);
+    else if (kind == IRIS_KIND_MASKS)
+        hipLaunchKernelGGL(generate_masks_tiles, dim3(grid_stride_blocks(n * kMaskChunks / 2)), dim3(256), 0, s, (uint4 *)db,
                            t_first, n, gen_key(seed, 0), global_index0);
     else
-        hipLaunchKernelGGL(generate_shares_tiles, dim3(plumb_grid(n * 2 * kShareChunks)), dim3(256), 0, s,
+        hipLaunchKernelGGL(generate_shares_tiles, dim3(grid_stride_blocks(n * 2 * kShareChunks)), dim3(256), 0, s,
                            (uint4 *)db, t_first, n, gen_key(seed, 1), global_index0);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 }  // namespace iris

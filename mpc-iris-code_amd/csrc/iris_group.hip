@@ -1109,8 +1109,8 @@ int iris_group_template_batch_search(iris_group_db_t *gdb, const iris_template_t
                 const LaunchRange r{0, gdb->count[s]};
                 const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
                 rc = timed(d, "template_batch", r.n * nq, [&] {
-                    return launch_batch(d->hooks, d->stream, gdb->shards[s]->data, e->qfrag, r, geo, (Partial *)d->partials.p,
-                                        sbuf + (size_t)j * stride, gdb->first[s]);
+                    return launch_batch(Pass::Search, d->hooks, d->stream, gdb->shards[s]->data, e->qfrag, r, geo,
+                                        {(Partial *)d->partials.p, sbuf + (size_t)j * stride, gdb->first[s]});
                 });
             }
         }

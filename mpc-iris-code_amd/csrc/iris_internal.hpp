@@ -235,42 +235,90 @@ void read_hooks(Hooks *h);
 size_t format_hooks(const Hooks &h, char *buf, size_t len);
 
 // ---------------------------------------------------------------- launchers
-// (defined in iris_kernels.hip; all asynchronous on `stream`)
+// All asynchronous on `stream`; 0, or -1 for a refused argument or a failed launch.  Grouped by
+// kernel family: a family's launcher sits with the functions that size its outputs (*_partials,
+// *_units), the predicates its callers ask first (*_ok) and its operand structs.
 struct LaunchRange {
     uint64_t first;  // first record index of the range
     uint64_t n;      // records in the range
 };
 
+// What a pass over a range does with each record's best rotation.  A family's launcher takes the
+// pass as a value and picks its kernel's own mode constant; one it has no kernel for is refused.
+//   Counts: the 31 numerators and denominators of every record
+//   Search: the closest record -- one Partial per workgroup, which a reduce folds -- and,
+//           if asked, every record's distance
+//   Match:  every record under a threshold, appended to a MatchSink
+//   Topk:   the k closest records of every unit (a wave that holds candidates), into topk_sink lists
+//   Hist:   the distribution of the distances, into hist_sink counters
+enum class Pass { Counts, Search, Match, Topk, Hist };
+
+// The operands of a single-query pass; what its mode does not write stays null.
+struct PassOut {
+    uint16_t *num_out = nullptr, *den_out = nullptr;  // Counts: [n][31] each (either may be null)
+    double *dist_out = nullptr;                       // Search: null, or n distances
+    Partial *partials = nullptr;                      // Search: the family's *_partials() records
+    MatchSink sink{};                                 // Match, Topk, Hist: counters zeroed on the stream by the caller
+    PassOut(uint16_t *num, uint16_t *den) : num_out(num), den_out(den) {}
+    PassOut(double *dist, Partial *parts) : dist_out(dist), partials(parts) {}
+    PassOut(const MatchSink &s) : sink(s) {}
+    // whether the operands are the ones mode p writes (the launchers refuse a pass whose are not)
+    bool fits(Pass p) const {
+        const bool counts = num_out || den_out, search = partials || dist_out;
+        return p == Pass::Counts ? !search : p == Pass::Search ? partials && !counts : !counts && !search;
+    }
+};
+
+int check_launch();                        // 0 if the launch just made was accepted, else -1
+int grid_stride_blocks(uint64_t total);    // workgroups of 256 for a grid-stride loop over `total` items
+
+// -- record plumbing: reference records <-> a database's layout, every kind (LANES: iris_kernels.hip;
+// TILES: launch_*_tiles_kind, iris_engines_mfma.hip)
 int launch_pack(void *stream, const KindInfo &k, const void *staging, void *db, uint64_t t_first, uint64_t n);
-// per-engine query tables built on the device from the query (iris_query.hip)
-// q, qmask: host
+int launch_unpack(void *stream, const KindInfo &k, const void *db, void *staging, uint64_t t_first, uint64_t n);
+int launch_generate(void *stream, const KindInfo &k, void *db, uint64_t t_first, uint64_t n, uint64_t seed,
+                    uint64_t global_index0);
+int launch_pack_tiles_kind(void *stream, int kind, const void *staging, void *db, uint64_t t_first, uint64_t n);
+int launch_unpack_tiles_kind(void *stream, int kind, const void *db, void *staging, uint64_t t_first, uint64_t n);
+int launch_generate_tiles_kind(void *stream, int kind, void *db, uint64_t t_first, uint64_t n, uint64_t seed,
+                               uint64_t global_index0);
+
+// -- per-engine query tables built on the device from the query (iris_query.hip); q, qmask: host
 int launch_query_template(void *stream, const void *q, uint32_t *tab, uint32_t *frag);
 int launch_query_masks(void *stream, const void *qmask, uint32_t *tab, uint32_t *frag);
 int launch_query_shares(void *stream, const void *q, uint32_t *tab, uint32_t *frag);
 int launch_query_tiles(void *stream, const void *queries, uint32_t nq, uint32_t nqp, uint32_t *tiles);
-// rounds: ChaCha8 / 12 / 20 (anything else: -1)
+
+// -- share preparation (iris_prepare.hip); rounds: ChaCha8 / 12 / 20 (anything else: -1)
+constexpr int kMaxPrepParties = 64;
 int launch_prepare_shares(void *stream, const void *templates, uint64_t m, uint64_t g0, const uint8_t key[32],
                           uint64_t nonce, uint32_t rounds, uint32_t parties, void *shares);
-constexpr int kMaxPrepParties = 64;
 int launch_prepare_shares_tiles(void *stream, const void *templates, uint64_t m, uint64_t g0, const uint8_t key[32],
                                 uint64_t nonce, uint32_t rounds, uint32_t parties, void *const *dbs,
                                 const uint64_t *t_first);
 int launch_prepare_direct(void *stream, const void *tdb, uint64_t t_first, uint64_t m, uint64_t g0,
                           const uint8_t key[32], uint64_t nonce, uint32_t rounds, uint32_t parties,
                           void *const *dbs, const uint64_t *s_first, void *masks, uint64_t m_first);
-int launch_unpack(void *stream, const KindInfo &k, const void *db, void *staging, uint64_t t_first, uint64_t n);
-int launch_generate(void *stream, const KindInfo &k, void *db, uint64_t t_first, uint64_t n, uint64_t seed,
-                    uint64_t global_index0);
-int launch_template_counts(void *stream, const void *db, const void *qtab, LaunchRange r, uint16_t *num_out,
-                           uint16_t *den_out);
-int launch_template_mfma_counts(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *num_out,
-                                uint16_t *den_out);
-// Fused finish of a small search (grids of at most kFusedReduceMax workgroups): the last
-// workgroup to finish reduces the partials and writes the winner (idx + idx_base) to dst;
-// ticket is a zeroed 4-KB device block (a two-level ticket) that the kernel leaves zeroed.  done != null (dst in
-// coherent host memory): dst is written through to host memory and, once those stores have
-// completed, seq is stored to *done (coherent host memory) -- a blocking caller spins on
-// that word instead of waiting for the end of the kernel and the runtime's completion signal.
+
+// -- template passes, LANES (template_kernel, iris_kernels.hip): one workgroup per 4 blocks of 64
+// records, every mode.  *n_partials (if given) = search_partials(r), set for an empty range too;
+// an empty range launches nothing.
+uint32_t search_partials(LaunchRange r);      // partials a search writes
+uint64_t template_topk_units(LaunchRange r);  // lists a top-k pass writes
+int launch_template(Pass p, void *stream, const void *db, const void *qtab, LaunchRange r, const PassOut &o,
+                    uint32_t *n_partials = nullptr);
+
+// -- template passes, TILES (template_mfma_kernel, iris_mfma.hip): every mode runs the form its
+// range asks for -- the K-split on small ranges, else one or four tiles per wave (IRIS_TILES_PER_WAVE
+// pins one) -- on the same grid.  *n_partials (if given) = mfma_search_partials(h, r), set for an
+// empty range too; an empty range launches nothing.
+// fin (a search only, and only where fused_search_ok(): else -1): the fused finish of a small search
+// (grids of at most kFusedReduceMax workgroups): the last workgroup to finish reduces the partials
+// and writes the winner (idx + idx_base) to dst; ticket is a zeroed 4-KB device block (a two-level
+// ticket) that the kernel leaves zeroed.  done != null (dst in coherent host memory): dst is written
+// through to host memory and, once those stores have completed, seq is stored to *done (coherent
+// host memory) -- a blocking caller spins on that word instead of waiting for the end of the kernel
+// and the runtime's completion signal.
 struct FusedFinish {
     uint32_t *ticket;
     Partial *dst;
@@ -280,17 +328,23 @@ struct FusedFinish {
 };
 constexpr uint32_t kFusedReduceMax = 4096;
 bool fused_search_ok(const Hooks &h, LaunchRange r);
-int launch_template_mfma_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, double *dist_out,
-                                Partial *partials, uint32_t *n_partials, const FusedFinish *fin = nullptr);
-uint32_t mfma_search_partials(const Hooks &h, LaunchRange r);
-// Shared passes (iris_template_search_async): while a pass streams the database, a
-// later search of the same range may register as its guest; every workgroup that starts after that
-// computes both queries for its 16 tiles from one read of them, writes both partials and marks its
-// tile group in the guest's done array, and the guest's own launch skips the groups marked there.
+uint32_t mfma_search_partials(const Hooks &h, LaunchRange r);  // partials a search writes
+uint64_t mfma_topk_units(const Hooks &h, LaunchRange r);       // lists a top-k pass writes
+int launch_template_mfma(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                         const PassOut &o, uint32_t *n_partials = nullptr, const FusedFinish *fin = nullptr);
+
+// -- shared template passes, TILES (template_share_kernel, iris_mfma.hip): while a
+// pass streams the database, a later pass of the same mode and range may register as its guest;
+// every workgroup that starts after that computes both queries for its 16 tiles from one read of
+// them, writes both results and marks its tile group in the guest's done array, and the guest's
+// own launch skips the groups marked there.  A search's results are partials, a match pass's the
+// hits appended to each query's sink, a top-k pass's each wave's list at unit blockIdx.x * 4 + wave
+// of each query's topk_sink (mfma_topk_units(h, r) units; k may differ).  A pass hosts passes of
+// its own mode only: the caller keeps them apart.
 // The slot is device memory, zeroed before the hosting pass's launch and written once by
-// launch_share_publish (the fields, then ready with agent-scope release).  Nothing else is read
-// while its writer runs: done words and a guest's partials reach their readers (the guest's own
-// launch and reduce, later on the device stream) with the end of the hosting kernel.
+// launch_share_publish* (the fields, then ready with agent-scope release).  Nothing else is read
+// while its writer runs: done words and what a pass wrote for its guest reach their readers (the
+// guest's own launch and what follows it on the device stream) with the end of the hosting kernel.
 struct GuestSlot {
     uint32_t ready;
     uint32_t pad;
@@ -301,43 +355,47 @@ struct GuestSlot {
 };
 // whether a range runs the form that can share: 4 tiles per wave, no K-split, separate reduce
 bool share_search_ok(const Hooks &h, LaunchRange r);
-// The sharing form of the search: slot = this pass's guest slot (NULL: never hosts), own_done =
-// NULL or the words an earlier pass set for the tile groups it computed for this query, count =
-// NULL or a device counter of tile groups carried for guests.
-int launch_template_share_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                                 Partial *partials, uint32_t *n_partials, const GuestSlot *slot,
-                                 const uint32_t *own_done, unsigned long long *count);
-// The sharing form of iris_template_matches_async (the same ranges, slot, own_done and count): every
-// tile group's hits are appended to ms, the guest's to its slot's sink.  A match pass hosts match
-// passes only, a search searches only: the caller keeps them apart.
-int launch_template_share_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                                const MatchSink &ms, const GuestSlot *slot, const uint32_t *own_done,
-                                unsigned long long *count);
-// The sharing form of iris_template_topk_async (the same ranges, slot, own_done and count): every
-// wave stores its k best of the tile group at unit blockIdx.x * 4 + wave of ts (topk_sink) -- the
-// units launch_template_mfma_topk numbers, mfma_topk_units(h, r) of them -- and the guest's at the
-// same unit of its slot's sink (topk_sink(lists, k): k may differ).  A top-k pass hosts top-k passes only.
-int launch_template_share_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                               const MatchSink &ts, const GuestSlot *slot, const uint32_t *own_done,
-                               unsigned long long *count);
-// a match pass's registration, and a top-k pass's (sink = topk_sink(lists, k))
-int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done);
+// Search, Match or Topk where share_search_ok() (else -1): slot = this pass's guest slot (NULL:
+// never hosts), own_done = NULL or the words an earlier pass set for the tile groups it computed
+// for this query, count = NULL or a device counter of tile groups carried for guests.
+int launch_template_share(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                          const PassOut &o, uint32_t *n_partials, const GuestSlot *slot, const uint32_t *own_done,
+                          unsigned long long *count);
 // zeroes a pass's guest slot and, if given, its done array of n words
 int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n);
+// a search's registration; a match pass's, and a top-k pass's (sink = topk_sink(lists, k))
 int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done);
+int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done);
 // test hook IRIS_SEARCH_SHARE_DELAY_US: a one-thread kernel that spins for `ticks` of the wall clock
 int launch_share_delay(void *stream, uint64_t ticks);
-// nq = 2 queries per streamed pass; partials [nq][*n_partials]
+
+// -- two-query search rounds (template_multi_kernel): nq = 2 queries per streamed pass; partials [nq][*n_partials]
 uint32_t multi_search_partials(LaunchRange r, int nq);
 int launch_template_multi_search(void *stream, const void *db, const void *const *qfrags, int nq, LaunchRange r,
                                  Partial *partials, uint32_t *n_partials);
-int launch_pack_tiles(void *stream, const void *staging, void *db, uint64_t t_first, uint64_t n);
-int launch_unpack_tiles(void *stream, const void *db, void *staging, uint64_t t_first, uint64_t n);
-int launch_generate_tiles(void *stream, void *db, uint64_t t_first, uint64_t n, uint64_t seed, uint64_t global_index0);
-int launch_pack_tiles_kind(void *stream, int kind, const void *staging, void *db, uint64_t t_first, uint64_t n);
-int launch_unpack_tiles_kind(void *stream, int kind, const void *db, void *staging, uint64_t t_first, uint64_t n);
-int launch_generate_tiles_kind(void *stream, int kind, void *db, uint64_t t_first, uint64_t n, uint64_t seed,
-                               uint64_t global_index0);
+
+// -- what follows a pass (iris_kernels.hip)
+// consumes partials; the winner's idx (range-relative) is offset by idx_base
+int launch_reduce(void *stream, Partial *partials, uint32_t n_partials, Partial *out, uint64_t idx_base = 0);
+// group search merge: out[q] = best of recv[s * stride + q], s < shards (indices already global)
+int launch_group_merge(void *stream, const Partial *recv, uint32_t shards, uint32_t nq, uint32_t stride, Partial *out);
+// dst[q][i] = sum over c < copies of src[q][c][i], q < nq, i < words (dst: device or pinned host memory)
+int launch_hist_reduce(void *stream, const uint64_t *src, uint32_t words, uint32_t copies, uint32_t nq, uint64_t *dst);
+// folds the `units` lists of k a top-k pass wrote at `lists` level by level (kTopkFanIn lists per
+// workgroup, ping-pong between `lists` and `spare`, which holds topk_spare_lists(units) lists) and
+// writes the final k records to `out`
+inline uint64_t topk_spare_lists(uint64_t units) { return (units + kTopkFanIn - 1) / kTopkFanIn; }
+int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t units, uint32_t k, Partial *out);
+// one level, `slots` queries that share `units` at a time (blockIdx.y): slot s reads src + s * src_stride
+// and writes its topk_spare_lists(units) lists at dst + s * dst_stride
+int launch_topk_merge_level(void *stream, const Partial *src, uint64_t units, uint32_t k, Partial *dst, uint32_t slots,
+                            uint64_t src_stride, uint64_t dst_stride);
+
+// -- MasksEngine and DistanceEngine rows, LANES (iris_kernels.hip)
+int launch_masks(void *stream, const void *db, const void *qtab, LaunchRange r, uint16_t *out);
+int launch_shares(void *stream, const void *db, const void *qtab, LaunchRange r, uint16_t *out);
+
+// -- MasksEngine and DistanceEngine rows, TILES (iris_engines_mfma.hip)
 // Completion word of a blocking device-output engine call: the kernel's last workgroup, once
 // every workgroup's rows are stored, stores seq into the coherent host word done (ticket: the
 // device's zeroed 4-KB ticket block, left zeroed).  The launcher sets armed when the kernel it
@@ -352,76 +410,6 @@ struct DoneSignal {
 // 32 B, then r.n escape rows of 31 u16 (no completion word)
 int launch_masks_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,
                       DoneSignal *sig = nullptr, bool packed = false);
-uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r);
-int launch_masks_resolve(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                         const uint16_t *const *shares, uint32_t parts, double *dist_out, Partial *partials);
-uint32_t resolver_partials(uint64_t n);
-// Threshold-match passes (iris_*_matches): the sibling search's streaming loop and dispatch, with
-// the MatchSink append as epilogue (ms.count zeroed on the stream by the caller).
-int launch_template_mfma_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                               const MatchSink &ms);
-int launch_template_match(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ms);
-int launch_resolver_match(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
-                          const MatchSink &ms);
-int launch_masks_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                       const uint16_t *const *shares, uint32_t parts, const MatchSink &ms);
-// Top-k passes (iris_*_topk): the sibling search's streaming loop and dispatch with the wave-
-// resident list (topk_insert, iris_device.hpp) as epilogue; *_topk_units is the number of lists
-// the pass writes.  launch_topk_merge folds `units` lists of k at `lists` level by level
-// (kTopkFanIn lists per workgroup, ping-pong between `lists` and `spare`, which holds
-// topk_spare_lists(units) lists) and writes the final k records to `out`.
-uint64_t mfma_topk_units(const Hooks &h, LaunchRange r);
-uint64_t template_topk_units(LaunchRange r);
-uint64_t resolver_topk_units(uint64_t n);
-uint64_t masks_topk_units(const Hooks &h, LaunchRange r);
-int launch_template_mfma_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                              const MatchSink &ts);
-int launch_template_topk(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ts);
-int launch_resolver_topk(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
-                         const MatchSink &ts);
-int launch_masks_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                      const uint16_t *const *shares, uint32_t parts, const MatchSink &ts);
-// Histogram passes (iris_*_histogram): the sibling search's streaming loop and dispatch with the
-// LDS histogram as epilogue; hs = hist_sink(counters, nbins, copies), the counters zeroed on the
-// stream by the caller.  No partials and no second pass: a histogram always fits.
-int launch_template_mfma_hist(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                              const MatchSink &hs);
-int launch_template_hist(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &hs);
-// dst[q][i] = sum over c < copies of src[q][c][i], q < nq, i < words (dst: device or pinned host memory)
-int launch_hist_reduce(void *stream, const uint64_t *src, uint32_t words, uint32_t copies, uint32_t nq, uint64_t *dst);
-inline uint64_t topk_spare_lists(uint64_t units) { return (units + kTopkFanIn - 1) / kTopkFanIn; }
-int launch_topk_merge(void *stream, Partial *lists, Partial *spare, uint64_t units, uint32_t k, Partial *out);
-// one level, `slots` queries that share `units` at a time (blockIdx.y): slot s reads src + s * src_stride
-// and writes its topk_spare_lists(units) lists at dst + s * dst_stride
-int launch_topk_merge_level(void *stream, const Partial *src, uint64_t units, uint32_t k, Partial *dst, uint32_t slots,
-                            uint64_t src_stride, uint64_t dst_stride);
-struct BatchGeometry {
-    uint64_t tile0, ntiles;
-    uint32_t nqg, G;  // query groups, workgroups per query group
-    uint32_t qper;    // queries per query group (nqg * qper results; at most the engine's padding)
-};
-BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq);
-uint32_t batch_query_group();  // padding unit of a batched engine's queries
-int launch_batch(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r, const BatchGeometry &g,
-                 Partial *partials, Partial *out, uint64_t idx_base = 0);
-// the threshold-match form of that pass (batch_lds_kernel<..., BL_MATCH>): sinks = DEVICE array of one
-// MatchSink per query of g (g.nqg * g.qper, in qtiles' order; a padding query's has cap 0)
-int launch_batch_match(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
-                       const BatchGeometry &g, const MatchSink *sinks);
-// the top-k form of that pass (batch_lds_kernel<..., BL_TOPK>): every wave of the grid stores its k
-// best records of query q of g (g.nqg * g.qper queries, in qtiles' order; a padding query's lists
-// stay empty) at lists + q * stride + unit * k; batch_topk_units = the lists per query
-uint64_t batch_topk_units(const BatchGeometry &g);
-int launch_batch_topk(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
-                      const BatchGeometry &g, Partial *lists, uint64_t stride, uint32_t k);
-// the histogram form of that pass (batch_lds_kernel<..., BL_HIST>): counts = DEVICE array [query of g]
-// [nbins + 1] of u64 (g.nqg * g.qper rows, in qtiles' order, zeroed on the stream by the caller);
-// every workgroup adds its non-zero words once, after its walk.  A padding query's row counts
-// every record as invalid; the host ignores it.
-int launch_batch_hist(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
-                      const BatchGeometry &g, uint64_t *counts, uint32_t nbins);
-int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
-                    double *dist_out, Partial *partials);
 int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,
                        DoneSignal *sig = nullptr);
 // nq DistanceEngine queries in one pass over a TILES share database (iris_shares_batch.hip):
@@ -435,11 +423,60 @@ struct SharesBatchForms {
 };
 int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t nq,
                         LaunchRange r, uint16_t *out, DoneSignal *sig = nullptr, SharesBatchForms *forms = nullptr);
-// Several MasksEngine queries in one pass over a TILES masks database (iris_masks_batch.hip).
+
+// -- the fused resolver step, TILES (masks_mfma_kernel's resolving modes, iris_engines_mfma.hip): the
+// masks pass whose rows are the denominators of shares[0..parts) (1..8 device arrays of r.n rows,
+// summed), decoded in place of being stored.  Search, Match or Topk; every mode runs the same grid,
+// masks_resolve_partials(h, r) workgroups at one or four tiles per wave; an empty range launches nothing.
+uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r);  // partials a search writes
+uint64_t masks_topk_units(const Hooks &h, LaunchRange r);        // lists a top-k pass writes
+int launch_masks_resolve(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                         const uint16_t *const *shares, uint32_t parts, const PassOut &o);
+
+// -- the resolver, denominators given (resolver_kernel, iris_resolver.hip): rows i < n of shares[0..parts)
+// (1..8) summed and decoded against denoms.  Search, Match or Topk; one workgroup per 256 rows in
+// every mode; n == 0 launches nothing.
+uint32_t resolver_partials(uint64_t n);    // partials a search writes
+uint64_t resolver_topk_units(uint64_t n);  // lists a top-k pass writes
+int launch_resolver(Pass p, void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                    const PassOut &o);
+
+// -- template batch passes, TILES (batch_lds_kernel, iris_batch.hip): the queries of g (g.nqg *
+// g.qper, in qtiles' order, padding queries included) against r in one GEMM pass of the shape
+// IRIS_BATCH_KERNEL picks, g.nqg * g.G workgroups in every mode; an empty range launches nothing.
+struct BatchGeometry {
+    uint64_t tile0, ntiles;
+    uint32_t nqg, G;  // query groups, workgroups per query group
+    uint32_t qper;    // queries per query group (nqg * qper results; at most the engine's padding)
+};
+BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq);
+uint32_t batch_query_group();  // padding unit of a batched engine's queries
+uint64_t batch_topk_units(const BatchGeometry &g);  // lists per query a top-k pass writes (its waves)
+// A mode's operands (the others stay unset):
+struct BatchPassOut {
+    Partial *partials = nullptr, *out = nullptr;  // Search: g.G partials per query, which a reduce launched with
+    uint64_t idx_base = 0;                        //   the pass folds into out[query] (idx + idx_base)
+    const MatchSink *sinks = nullptr;             // Match: DEVICE array of one sink per query (a padding query's has cap 0)
+    Partial *lists = nullptr;                     // Topk: query q's wave `unit` stores its k best at lists + q * stride
+    uint64_t stride = 0;                          //   + unit * k (a padding query's lists stay empty); k 1..kTopkMax,
+    uint32_t k = 0;                               //   stride >= batch_topk_units(g) * k
+    uint64_t *counts = nullptr;                   // Hist: DEVICE rows [query][nbins + 1] of u64, zeroed on the stream by
+    uint32_t nbins = 0;                           //   the caller (a padding query's row counts every record invalid);
+                                                  //   nbins a power of two up to kHistMaxBins
+    BatchPassOut(Partial *parts, Partial *res, uint64_t base = 0) : partials(parts), out(res), idx_base(base) {}
+    BatchPassOut(const MatchSink *device_sinks) : sinks(device_sinks) {}
+    BatchPassOut(Partial *l, uint64_t s, uint32_t kk) : lists(l), stride(s), k(kk) {}
+    BatchPassOut(uint64_t *c, uint32_t bins) : counts(c), nbins(bins) {}
+};
+int launch_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
+                 const BatchGeometry &g, const BatchPassOut &o);
+
+// -- masks batch passes, TILES (masks_batch_kernel, iris_masks_batch.hip): m = 2..kMasksBatchG
+// MasksEngine queries in one pass, the same slots, tiles per wave and grid in every mode.
 constexpr int kMasksBatchG = 4;  // queries per pass
 // The fused resolver step of a pass: shares[p] = participant p's query-major device array (nq slabs of
-// r.n * 31 u16), q0 = the pass's first query (its slab), dist_out = NULL or nq * r.n doubles
-// (query-major); query q0 + s writes masks_batch_partials() partials at partials + s * stride.
+// r.n * 31 u16), q0 = the pass's first query (its slab); a search: dist_out = NULL or nq * r.n doubles
+// (query-major), and query q0 + s writes masks_batch_partials() partials at partials + s * stride.
 struct MasksBatchResolve {
     const uint16_t *const *shares;
     uint32_t parts;
@@ -450,31 +487,26 @@ struct MasksBatchResolve {
 };
 bool masks_batch_runs(const Hooks &h, LaunchRange r);  // whether a range runs the batch kernel (else single-query launches)
 uint32_t masks_batch_partials(const Hooks &h, LaunchRange r);  // upper bound of a query's partials
-// m = 2..kMasksBatchG queries; rs == NULL: rows of query s to out + s * r.n * 31; *np: partials written per query
-int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
-                       uint16_t *out, const MasksBatchResolve *rs, uint32_t *np = nullptr);
-// the threshold-match form of that pass: query s reads slab q0 + s of every part and appends to sinks[s]
-// (m sinks, each with its own buffer region and counter; counters zeroed on the stream by the caller)
-int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
-                             LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0,
-                             const MatchSink *sinks);
-// the top-k form of that pass: every wave stores its k best records of query s (slab q0 + s of every
-// part) at lists + s * stride + wave * k; masks_batch_topk_units = the lists per query (the grid's waves)
-uint64_t masks_batch_topk_units(const Hooks &h, LaunchRange r, uint32_t m);
-int launch_masks_batch_topk(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
-                            LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0, Partial *lists,
-                            uint64_t stride, uint32_t k);
-int launch_template_search(void *stream, const void *db, const void *qtab, LaunchRange r, double *dist_out,
-                           Partial *partials, uint32_t *n_partials);
-// consumes partials; the winner's idx (range-relative) is offset by idx_base
-int launch_reduce(void *stream, Partial *partials, uint32_t n_partials, Partial *out, uint64_t idx_base = 0);
-// group search merge: out[q] = best of recv[s * stride + q], s < shards (indices already global)
-int launch_group_merge(void *stream, const Partial *recv, uint32_t shards, uint32_t nq, uint32_t stride, Partial *out);
-int launch_masks(void *stream, const void *db, const void *qtab, LaunchRange r, uint16_t *out);
-int launch_shares(void *stream, const void *db, const void *qtab, LaunchRange r, uint16_t *out);
-
-// number of partial records launch_template_search writes for a range
-uint32_t search_partials(LaunchRange r);
+uint64_t masks_batch_topk_units(const Hooks &h, LaunchRange r, uint32_t m);  // lists per query a top-k pass writes
+// A mode's operands, by constructor (launch_masks_batch refuses operands that are not its mode's):
+struct MasksBatchOut {
+    uint16_t *rows = nullptr;         // Search, no resolver step: rows of query s to rows + s * r.n * 31
+    bool resolve = false;             // every other form: the fused resolver step rs
+    MasksBatchResolve rs{};
+    uint32_t *np = nullptr;           // Search with rs: *np = partials written per query
+    const MatchSink *sinks = nullptr; // Match: sinks[s] is query s's (counters zeroed on the stream by the caller)
+    Partial *lists = nullptr;         // Topk: every wave stores its k best of query s at lists + s * stride
+    uint64_t stride = 0;              //   + wave * k (masks_batch_topk_units lists per query); k 1..kTopkMax
+    uint32_t k = 0;
+    MasksBatchOut(uint16_t *out) : rows(out) {}
+    MasksBatchOut(const MasksBatchResolve &r, uint32_t *n_partials) : resolve(true), rs(r), np(n_partials) {}
+    MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, const MatchSink *match_sinks)
+        : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, sinks(match_sinks) {}
+    MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, Partial *l, uint64_t s, uint32_t kk)
+        : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, lists(l), stride(s), k(kk) {}
+};
+int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                       LaunchRange r, const MasksBatchOut &o);
 
 // ---------------------------------------------------------------- host helpers (iris_host.cpp)
 void bits_rotated(const uint64_t *in, int amount, uint64_t *out);

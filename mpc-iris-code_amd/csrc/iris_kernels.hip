@@ -500,7 +500,7 @@ __global__ void __launch_bounds__(256) generate_kernel(uint4 *__restrict__ db, u
 
 // ------------------------------------------------------------------ launchers
 
-static int grid_stride_blocks(uint64_t total) {
+int grid_stride_blocks(uint64_t total) {
     uint64_t b = (total + 255) / 256;
     const uint64_t cap = 256ull * 64;  // 64 workgroups per CU
     if (b > cap) b = cap;
@@ -508,11 +508,11 @@ static int grid_stride_blocks(uint64_t total) {
     return (int)b;
 }
 
+int check_launch() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+
 static PackParams pack_params(const KindInfo &k) {
     return PackParams{k.groups, k.planes, k.rec_dwords, k.plane_src[0], k.plane_src[1]};
 }
-
-static int check_launch() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 int launch_pack(void *stream, const KindInfo &k, const void *staging, void *db, uint64_t t_first, uint64_t n) {
     if (n == 0) return 0;
@@ -556,44 +556,31 @@ static BlockRange block_range(LaunchRange r) {
 
 uint32_t search_partials(LaunchRange r) { return (uint32_t)block_range(r).grid; }
 
-int launch_template_counts(void *stream, const void *db, const void *qtab, LaunchRange r, uint16_t *num_out,
-                           uint16_t *den_out) {
-    if (r.n == 0) return 0;
+template <int MODE>
+static int lanes_pass(void *stream, const void *db, const void *qtab, LaunchRange r, const PassOut &o, uint32_t *n_partials) {
     const BlockRange b = block_range(r);
-    hipLaunchKernelGGL(template_kernel<MODE_COUNTS>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n, num_out,
-                       den_out, (double *)nullptr, (Partial *)nullptr, MatchSink{});
+    if (n_partials) *n_partials = (uint32_t)b.grid;  // an empty range's too
+    if (r.n == 0) return 0;
+    hipLaunchKernelGGL(template_kernel<MODE>, dim3((uint32_t)b.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n, o.num_out,
+                       o.den_out, o.dist_out, o.partials, o.sink);
     return check_launch();
 }
 
-int launch_template_search(void *stream, const void *db, const void *qtab, LaunchRange r, double *dist_out,
-                           Partial *partials, uint32_t *n_partials) {
-    const BlockRange b = block_range(r);
-    *n_partials = (uint32_t)b.grid;
-    if (r.n == 0) return 0;
-    hipLaunchKernelGGL(template_kernel<MODE_SEARCH>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials, MatchSink{});
-    return check_launch();
+int launch_template(Pass p, void *stream, const void *db, const void *qtab, LaunchRange r, const PassOut &o,
+                    uint32_t *n_partials) {
+    if (r.n != 0 && !o.fits(p)) return -1;
+    switch (p) {
+    case Pass::Counts: return lanes_pass<MODE_COUNTS>(stream, db, qtab, r, o, n_partials);
+    case Pass::Search: return lanes_pass<MODE_SEARCH>(stream, db, qtab, r, o, n_partials);
+    case Pass::Match: return lanes_pass<MODE_MATCH>(stream, db, qtab, r, o, n_partials);
+    case Pass::Topk: return lanes_pass<MODE_TOPK>(stream, db, qtab, r, o, n_partials);
+    case Pass::Hist: return lanes_pass<MODE_HIST>(stream, db, qtab, r, o, n_partials);
+    }
+    return -1;
 }
 
-int launch_template_match(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ms) {
-    if (r.n == 0) return 0;
-    const BlockRange b = block_range(r);
-    hipLaunchKernelGGL(template_kernel<MODE_MATCH>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, ms);
-    return check_launch();
-}
-
-int launch_template_hist(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &hs) {
-    if (r.n == 0) return 0;
-    const BlockRange b = block_range(r);
-    hipLaunchKernelGGL(template_kernel<MODE_HIST>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, hs);
-    return check_launch();
-}
+uint64_t template_topk_units(LaunchRange r) { return block_range(r).grid * kWaveSlots; }
 
 // one thread per counter word and query (blockIdx.y): the sum of its copies
 __global__ void __launch_bounds__(256) hist_reduce_kernel(const uint64_t *__restrict__ src, uint32_t words,
@@ -610,17 +597,6 @@ int launch_hist_reduce(void *stream, const uint64_t *src, uint32_t words, uint32
     if (words == 0 || copies == 0 || nq == 0 || nq > 65535) return -1;
     hipLaunchKernelGGL(hist_reduce_kernel, dim3((words + 255) / 256, nq), dim3(256), 0, (hipStream_t)stream, src, words,
                        copies, dst);
-    return check_launch();
-}
-
-uint64_t template_topk_units(LaunchRange r) { return block_range(r).grid * kWaveSlots; }
-
-int launch_template_topk(void *stream, const void *db, const void *qtab, LaunchRange r, const MatchSink &ts) {
-    if (r.n == 0) return 0;
-    const BlockRange b = block_range(r);
-    hipLaunchKernelGGL(template_kernel<MODE_TOPK>, dim3((uint32_t)b.grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint32_t *)qtab, b.blk0, b.nblk, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, ts);
     return check_launch();
 }
 

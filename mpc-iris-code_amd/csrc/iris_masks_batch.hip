@@ -346,7 +346,7 @@ int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const 
     auto kern = t.tpw == 1 ? masks_batch_kernel<G, 1, MODE> : masks_batch_kernel<G, batch_big_tiles<G>(), MODE>;
     hipLaunchKernelGGL(kern, dim3(t.grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)db, a, t.tile0, t.ntiles,
                        r.first, r.first + r.n);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 template <int G>  // mode = BATCH_*: BATCH_OUT writes `out`, the others read rs, BATCH_MATCH and BATCH_TOPK fill sinks
@@ -402,48 +402,36 @@ bool masks_batch_runs(const Hooks &h, LaunchRange r) {
 // the most partials per query a pass over r writes (the grid at one tile per wave)
 uint32_t masks_batch_partials(const Hooks &h, LaunchRange r) { return r.n ? batch_tiles(h, r, 1).grid : 0; }
 
-// m = 2 .. kMasksBatchG queries (qfrags[s]: a MasksEngine's compact fragments) over [r.first, r.first +
-// r.n) of a TILES masks database in one pass.  rs == NULL: query s's rows go to out + s * r.n * 31;
-// otherwise the fused resolver step, see MasksBatchResolve; *np = the partials each query's run then holds.
-int launch_masks_batch(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m, LaunchRange r,
-                       uint16_t *out, const MasksBatchResolve *rs, uint32_t *np) {
-    if (np) *np = 0;
-    if (r.n == 0) return 0;
-    if (m < 2 || m > (uint32_t)kMasksBatchG) return -1;
-    if (rs && (rs->parts == 0 || rs->parts > 8)) return -1;
-    return launch_mode(rs ? BATCH_RESOLVE : BATCH_OUT, h, stream, db, qfrags, m, r, out, rs, np, nullptr);
-}
-
-// The threshold-match form of the same pass (launch_masks_batch's slots, tiles per wave and grid):
-// query s decodes slab q0 + s of every part and appends its records below sinks[s].threshold to
-// sinks[s]; the counters are zeroed on the stream by the caller.
-int launch_masks_batch_match(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
-                             LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0,
-                             const MatchSink *sinks) {
-    if (r.n == 0) return 0;
-    if (m < 2 || m > (uint32_t)kMasksBatchG || parts == 0 || parts > 8 || !sinks) return -1;
-    const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
-    return launch_mode(BATCH_MATCH, h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
-}
-
 // the lists each query of a top-k pass over r writes: one per wave of the grid (launch_slots')
 uint64_t masks_batch_topk_units(const Hooks &h, LaunchRange r, uint32_t m) {
     if (r.n == 0) return 0;
     return (uint64_t)batch_tiles(h, r, m == 2 ? batch_big_tiles<2>() : batch_big_tiles<kMasksBatchG>()).grid * kWaveSlots;
 }
 
-// The top-k form of the same pass (launch_masks_batch's slots, tiles per wave and grid): query s
-// decodes slab q0 + s of every part and every wave stores its k best records of that query at
-// lists + s * stride + wave * k (masks_batch_topk_units lists per query); nothing needs zeroing.
-int launch_masks_batch_topk(const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
-                            LaunchRange r, const uint16_t *const *shares, uint32_t parts, uint32_t q0, Partial *lists,
-                            uint64_t stride, uint32_t k) {
+// m = 2 .. kMasksBatchG queries (qfrags[s]: a MasksEngine's compact fragments) over [r.first, r.first +
+// r.n) of a TILES masks database in one pass: the same slots, tiles per wave and grid in every mode
+// (MasksBatchOut has the operands of each).
+int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
+                       LaunchRange r, const MasksBatchOut &o) {
+    if (o.np) *o.np = 0;
     if (r.n == 0) return 0;
-    if (m < 2 || m > (uint32_t)kMasksBatchG || parts == 0 || parts > 8 || !lists || k == 0 || k > kTopkMax) return -1;
-    const MasksBatchResolve rs{shares, parts, q0, nullptr, nullptr, 0};
-    MatchSink sinks[kMasksBatchG];
-    for (uint32_t s = 0; s < m; ++s) sinks[s] = topk_sink(lists + s * stride, k);
-    return launch_mode(BATCH_TOPK, h, stream, db, qfrags, m, r, nullptr, &rs, nullptr, sinks);
+    if (m < 2 || m > (uint32_t)kMasksBatchG) return -1;
+    const MasksBatchResolve *rs = o.resolve ? &o.rs : nullptr;
+    if (rs && (rs->parts == 0 || rs->parts > 8)) return -1;
+    MatchSink ts[kMasksBatchG];
+    switch (p) {
+    case Pass::Search:
+        if (o.sinks || o.lists || (!rs && !o.rows)) return -1;
+        return launch_mode(rs ? BATCH_RESOLVE : BATCH_OUT, h, stream, db, qfrags, m, r, o.rows, rs, o.np, nullptr);
+    case Pass::Match:
+        if (!rs || !o.sinks) return -1;
+        return launch_mode(BATCH_MATCH, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, o.sinks);
+    case Pass::Topk:
+        if (!rs || !o.lists || o.k == 0 || o.k > kTopkMax) return -1;
+        for (uint32_t s = 0; s < m; ++s) ts[s] = topk_sink(o.lists + s * o.stride, o.k);
+        return launch_mode(BATCH_TOPK, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, ts);
+    default: return -1;
+    }
 }
 
 }  // namespace iris

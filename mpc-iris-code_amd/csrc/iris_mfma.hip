@@ -982,6 +982,8 @@ __global__ void share_delay_kernel(uint64_t ticks) {
 }
 
 // ------------------------------------------------------------------ TILES layout plumbing
+// (declared in iris_device.hpp; launch_*_tiles_kind, iris_engines_mfma.hip, launches these three on
+// grid_stride_blocks(n * 2 * kPlaneGroups) workgroups of 256, the `total` of their loops)
 
 // reference Template record (pattern dwords 0..399, mask dwords 400..799) ->
 // TILES uint4 of (record t, chunk pair g, half h)
@@ -1051,36 +1053,9 @@ __global__ void __launch_bounds__(256) generate_tiles_kernel(uint4 *__restrict__
     }
 }
 
-static int tiles_grid(uint64_t total) {
-    uint64_t b = (total + 255) / 256;
-    if (b > 256ull * 64) b = 256ull * 64;
-    return (int)(b ? b : 1);
-}
-
-int launch_pack_tiles(void *stream, const void *staging, void *db, uint64_t t_first, uint64_t n) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(pack_tiles_kernel, dim3(tiles_grid(n * 2 * kPlaneGroups)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint32_t *)staging, (uint4 *)db, t_first, n);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_unpack_tiles(void *stream, const void *db, void *staging, uint64_t t_first, uint64_t n) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(unpack_tiles_kernel, dim3(tiles_grid(n * 2 * kPlaneGroups)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (uint32_t *)staging, t_first, n);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_generate_tiles(void *stream, void *db, uint64_t t_first, uint64_t n, uint64_t seed, uint64_t global_index0) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(generate_tiles_kernel, dim3(tiles_grid(n * 2 * kPlaneGroups)), dim3(256), 0,
-                       (hipStream_t)stream, (uint4 *)db, t_first, n, gen_key(seed, 0), global_index0);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 struct TileRange {
     uint64_t tile0, ntiles, grid;
-    bool fusable = false;  // small enough for the in-kernel reduce
+    bool fusable;  // small enough for the search's in-kernel reduce
     int tiles_per_wave;
     int ksplit;  // 4: a tile's 4 waves split K (ranges of at most kSplitTiles tiles)
 };
@@ -1093,6 +1068,8 @@ constexpr uint64_t kSmallTiles = 4 * kWaveSlots * 256 * 2;
 // one tile's K instead.
 constexpr uint64_t kSplitTiles = 1024;
 
+// The form and grid of every single-query pass: one workgroup per 16 tiles (a persistent grid
+// measured slower), 4 tiles on small ranges, kSplitT under the K-split.
 static TileRange tile_range(const Hooks &h, LaunchRange r) {
     TileRange t;
     t.tile0 = r.first / kTileRecs;
@@ -1109,23 +1086,120 @@ static TileRange tile_range(const Hooks &h, LaunchRange r) {
     if (t.ksplit > 1) {
         t.tiles_per_wave = kSplitT;
         t.grid = (t.ntiles + kSplitT - 1) / kSplitT;  // kSplitT tiles per workgroup
-        return t;
+    } else {
+        const uint64_t waves = (t.ntiles + t.tiles_per_wave - 1) / t.tiles_per_wave;
+        t.grid = (waves + kWaveSlots - 1) / kWaveSlots;
     }
-    const uint64_t waves = (t.ntiles + t.tiles_per_wave - 1) / t.tiles_per_wave;
-    t.grid = (waves + kWaveSlots - 1) / kWaveSlots;
-    return t;
-}
-
-// the search's form of tile_range: one workgroup per 16 tiles (a persistent grid measured
-// slower)
-static TileRange search_range(const Hooks &h, LaunchRange r) {
-    TileRange t = tile_range(h, r);
     t.fusable = t.grid <= (uint64_t)kFusedReduceMax;
     return t;
 }
 
 // partial records a search writes
-uint32_t mfma_search_partials(const Hooks &h, LaunchRange r) { return (uint32_t)search_range(h, r).grid; }
+uint32_t mfma_search_partials(const Hooks &h, LaunchRange r) { return (uint32_t)tile_range(h, r).grid; }
+
+// lists a top-k pass writes: one per wave that holds sums (a workgroup's one tile group under the K-split)
+uint64_t mfma_topk_units(const Hooks &h, LaunchRange r) {
+    const TileRange t = tile_range(h, r);
+    return t.grid * (uint64_t)(t.ksplit > 1 ? 1 : kWaveSlots);
+}
+
+// test hook: IRIS_FUSED_REDUCE=0 runs small searches with the separate reduce kernel
+bool fused_search_ok(const Hooks &h, LaunchRange r) { return h.fused_reduce && r.n != 0 && tile_range(h, r).fusable; }
+
+bool share_search_ok(const Hooks &h, LaunchRange r) {
+    if (r.n == 0 || fused_search_ok(h, r)) return false;
+    const TileRange t = tile_range(h, r);
+    return t.ksplit == 1 && t.tiles_per_wave == kMfmaTiles;
+}
+
+// The one dispatch of template_mfma_kernel: the K-split form on small ranges, else one or four
+// tiles per wave; a search with a fused finish runs the FUSED instance of the same form.
+template <int MODE>
+static int mfma_pass(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, const PassOut &o,
+                     uint32_t *n_partials, const FusedFinish *fin) {
+    const TileRange t = tile_range(h, r);
+    if (n_partials) *n_partials = (uint32_t)t.grid;  // an empty range's too
+    if (r.n == 0) return 0;
+    auto kern = t.ksplit > 1 ? template_mfma_kernel<MODE, kSplitT, 4>
+                : t.tiles_per_wave == 1 ? template_mfma_kernel<MODE, 1> : template_mfma_kernel<MODE>;
+    if (fin) {
+        if (MODE != MF_SEARCH || !t.fusable) return -1;  // the caller asks fused_search_ok() first
+        if constexpr (MODE == MF_SEARCH)
+            kern = t.ksplit > 1 ? template_mfma_kernel<MODE, kSplitT, 4, true>
+                   : t.tiles_per_wave == 1 ? template_mfma_kernel<MODE, 1, 1, true>
+                                           : template_mfma_kernel<MODE, kMfmaTiles, 1, true>;
+    }
+    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
+                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, o.num_out,
+                       o.den_out, o.dist_out, o.partials, fin ? *fin : FusedFinish{}, o.sink);
+    return check_launch();
+}
+
+int launch_template_mfma(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                         const PassOut &o, uint32_t *n_partials, const FusedFinish *fin) {
+    if (r.n != 0 && !o.fits(p)) return -1;
+    switch (p) {
+    case Pass::Counts: return mfma_pass<MF_COUNTS>(h, stream, db, qfrag, r, o, n_partials, fin);
+    case Pass::Search: return mfma_pass<MF_SEARCH>(h, stream, db, qfrag, r, o, n_partials, fin);
+    case Pass::Match: return mfma_pass<MF_MATCH>(h, stream, db, qfrag, r, o, n_partials, fin);
+    case Pass::Topk: return mfma_pass<MF_TOPK>(h, stream, db, qfrag, r, o, n_partials, fin);
+    case Pass::Hist: return mfma_pass<MF_HIST>(h, stream, db, qfrag, r, o, n_partials, fin);
+    }
+    return -1;
+}
+
+// The one launch of template_share_kernel (tile_range's 4-tiles-per-wave grid; `out` is the
+// partials array of a search and the sink of a match or a top-k pass).
+template <int MODE>
+static int share_pass(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, const PassOut &o,
+                      uint32_t *n_partials, const GuestSlot *slot, const uint32_t *own_done, unsigned long long *count) {
+    if (!share_search_ok(h, r)) return -1;  // the caller asks first
+    const TileRange t = tile_range(h, r);
+    if (n_partials) *n_partials = (uint32_t)t.grid;
+    // test hook: a pass that is nobody's guest carries its guest in even tile groups only (the
+    // guest's own launch then computes the odd ones, and carries its own guest there)
+    const bool even_only = h.search_share_even && !own_done;
+    std::conditional_t<MODE == SH_SEARCH, Partial *, MatchSink> out;
+    if constexpr (MODE == SH_SEARCH) out = o.partials;
+    else out = o.sink;
+    hipLaunchKernelGGL(template_share_kernel<MODE>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
+                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
+                       r.first + r.n, out, slot, own_done, count, (uint32_t)even_only);
+    return check_launch();
+}
+
+int launch_template_share(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
+                          const PassOut &o, uint32_t *n_partials, const GuestSlot *slot, const uint32_t *own_done,
+                          unsigned long long *count) {
+    if (!o.fits(p)) return -1;
+    switch (p) {
+    case Pass::Search: return share_pass<SH_SEARCH>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
+    case Pass::Match: return share_pass<SH_MATCH>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
+    case Pass::Topk: return share_pass<SH_TOPK>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
+    default: return -1;  // counts and histograms have no sharing form
+    }
+}
+
+int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n) {
+    const uint32_t words = done ? (n ? n : 1) : 1;
+    hipLaunchKernelGGL(share_prepare_kernel, dim3((words + 255) / 256), dim3(256), 0, (hipStream_t)stream, slot, done, n);
+    return check_launch();
+}
+
+int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done) {
+    hipLaunchKernelGGL(share_publish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, partials, done);
+    return check_launch();
+}
+
+int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done) {
+    hipLaunchKernelGGL(share_publish_match_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, sink, done);
+    return check_launch();
+}
+
+int launch_share_delay(void *stream, uint64_t ticks) {
+    hipLaunchKernelGGL(share_delay_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ticks);
+    return check_launch();
+}
 
 uint32_t multi_search_partials(LaunchRange r, int nq) {
     const uint64_t tile0 = r.first / kTileRecs, tile1 = (r.first + r.n + kTileRecs - 1) / kTileRecs;
@@ -1143,156 +1217,7 @@ int launch_template_multi_search(void *stream, const void *db, const void *const
     for (int i = 0; i < nq; ++i) qf.q[i] = (const uint4 *)qfrags[i];
     hipLaunchKernelGGL(template_multi_kernel<2>, dim3(*n_partials), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)db, qf, tile0, tile1 - tile0, r.first, r.first + r.n, partials);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_template_mfma_counts(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *num_out,
-                                uint16_t *den_out) {
-    if (r.n == 0) return 0;
-    const TileRange t = tile_range(h, r);
-    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_COUNTS, kSplitT, 4>
-                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_COUNTS, 1> : template_mfma_kernel<MF_COUNTS>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n, num_out,
-                       den_out, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, MatchSink{});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_template_mfma_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, double *dist_out,
-                                Partial *partials, uint32_t *n_partials, const FusedFinish *fin) {
-    const TileRange t = search_range(h, r);
-    *n_partials = (uint32_t)t.grid;
-    if (r.n == 0) return 0;
-    const bool fused = fin && t.fusable;
-    if (fin && !fused) return -1;  // the caller asks fused_search_ok() first
-    auto kern = fused ? (t.ksplit > 1 ? template_mfma_kernel<MF_SEARCH, kSplitT, 4, true>
-                         : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_SEARCH, 1, 1, true>
-                                                 : template_mfma_kernel<MF_SEARCH, kMfmaTiles, 1, true>)
-                      : (t.ksplit > 1 ? template_mfma_kernel<MF_SEARCH, kSplitT, 4>
-                         : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_SEARCH, 1> : template_mfma_kernel<MF_SEARCH>);
-    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, dist_out, partials, fin ? *fin : FusedFinish{},
-                       MatchSink{});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-bool share_search_ok(const Hooks &h, LaunchRange r) {
-    if (r.n == 0 || fused_search_ok(h, r)) return false;
-    const TileRange t = search_range(h, r);
-    return t.ksplit == 1 && t.tiles_per_wave == kMfmaTiles;
-}
-
-int launch_template_share_search(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                                 Partial *partials, uint32_t *n_partials, const GuestSlot *slot,
-                                 const uint32_t *own_done, unsigned long long *count) {
-    if (!share_search_ok(h, r)) return -1;  // the caller asks first
-    const TileRange t = search_range(h, r);
-    *n_partials = (uint32_t)t.grid;
-    // test hook: a pass that is nobody's guest carries its guest in even tile groups only (the
-    // guest's own launch then computes the odd ones, and carries its own guest there)
-    const bool even_only = h.search_share_even && !own_done;
-    hipLaunchKernelGGL(template_share_kernel<SH_SEARCH>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
-                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
-                       r.first + r.n, partials, slot, own_done, count, (uint32_t)even_only);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_template_share_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                                const MatchSink &ms, const GuestSlot *slot, const uint32_t *own_done,
-                                unsigned long long *count) {
-    if (!share_search_ok(h, r)) return -1;  // the caller asks first
-    const TileRange t = search_range(h, r);
-    const bool even_only = h.search_share_even && !own_done;  // as the search's
-    hipLaunchKernelGGL(template_share_kernel<SH_MATCH>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
-                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
-                       r.first + r.n, ms, slot, own_done, count, (uint32_t)even_only);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_template_share_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                               const MatchSink &ts, const GuestSlot *slot, const uint32_t *own_done,
-                               unsigned long long *count) {
-    if (!share_search_ok(h, r)) return -1;  // the caller asks first
-    const TileRange t = search_range(h, r);
-    const bool even_only = h.search_share_even && !own_done;  // as the search's
-    hipLaunchKernelGGL(template_share_kernel<SH_TOPK>, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0,
-                       (hipStream_t)stream, (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first,
-                       r.first + r.n, ts, slot, own_done, count, (uint32_t)even_only);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t n) {
-    const uint32_t words = done ? (n ? n : 1) : 1;
-    hipLaunchKernelGGL(share_prepare_kernel, dim3((words + 255) / 256), dim3(256), 0, (hipStream_t)stream, slot, done, n);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done) {
-    hipLaunchKernelGGL(share_publish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, partials, done);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done) {
-    hipLaunchKernelGGL(share_publish_match_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, sink, done);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_share_delay(void *stream, uint64_t ticks) {
-    hipLaunchKernelGGL(share_delay_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ticks);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// the search's dispatch (K-split form on small ranges, else one or four tiles per wave), MF_MATCH epilogue
-int launch_template_mfma_match(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                               const MatchSink &ms) {
-    if (r.n == 0) return 0;
-    const TileRange t = tile_range(h, r);
-    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_MATCH, kSplitT, 4>
-                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_MATCH, 1> : template_mfma_kernel<MF_MATCH>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, ms);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// the search's dispatch, MF_HIST epilogue
-int launch_template_mfma_hist(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                              const MatchSink &hs) {
-    if (r.n == 0) return 0;
-    const TileRange t = tile_range(h, r);
-    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_HIST, kSplitT, 4>
-                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_HIST, 1> : template_mfma_kernel<MF_HIST>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, hs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// lists a top-k pass writes: one per wave that holds sums (a workgroup's one tile group under the K-split)
-uint64_t mfma_topk_units(const Hooks &h, LaunchRange r) {
-    const TileRange t = tile_range(h, r);
-    return t.grid * (uint64_t)(t.ksplit > 1 ? 1 : kWaveSlots);
-}
-
-// the search's dispatch without the fused finish, MF_TOPK epilogue
-int launch_template_mfma_topk(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
-                              const MatchSink &ts) {
-    if (r.n == 0) return 0;
-    const TileRange t = tile_range(h, r);
-    auto kern = t.ksplit > 1 ? template_mfma_kernel<MF_TOPK, kSplitT, 4>
-                : t.tiles_per_wave == 1 ? template_mfma_kernel<MF_TOPK, 1> : template_mfma_kernel<MF_TOPK>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(64 * kWaveSlots), 0, (hipStream_t)stream,
-                       (const uint4 *)db, (const uint4 *)qfrag, t.tile0, t.ntiles, r.first, r.first + r.n,
-                       (uint16_t *)nullptr, (uint16_t *)nullptr, (double *)nullptr, (Partial *)nullptr, FusedFinish{}, ts);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// test hook: IRIS_FUSED_REDUCE=0 runs small searches with the separate reduce kernel
-bool fused_search_ok(const Hooks &h, LaunchRange r) {
-    if (!h.fused_reduce) return false;
-    if (r.n == 0) return false;
-    return search_range(h, r).fusable;
+    return check_launch();
 }
 
 }  // namespace iris

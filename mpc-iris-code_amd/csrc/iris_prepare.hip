@@ -267,7 +267,7 @@ int launch_prepare_direct(void *stream, const void *tdb, uint64_t t_first, uint6
     if (!kern) return -1;
     hipLaunchKernelGGL(kern, dim3((uint32_t)((m + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
                        (const uint4 *)tdb, t_first, m, g0, k, nonce, parties, d, (uint4 *)masks, m_first);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_prepare_shares_tiles(void *stream, const void *templates, uint64_t m, uint64_t g0, const uint8_t key[32],
@@ -285,21 +285,18 @@ int launch_prepare_shares_tiles(void *stream, const void *templates, uint64_t m,
     if (!kern) return -1;
     hipLaunchKernelGGL(kern, dim3((uint32_t)((m + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
                        (const uint32_t *)templates, m, g0, k, nonce, parties, d);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_prepare_shares(void *stream, const void *templates, uint64_t m, uint64_t g0, const uint8_t key[32],
                           uint64_t nonce, uint32_t rounds, uint32_t parties, void *shares) {
     if (m == 0) return 0;
     const ChachaKey k = load_key(key);
-    const uint64_t total = m * kBlocks;
-    uint64_t grid = (total + 255) / 256;
-    if (grid > 256ull * 64) grid = 256ull * 64;
     const auto kern = by_rounds(rounds, prepare_shares_kernel<4>, prepare_shares_kernel<6>, prepare_shares_kernel<10>);
     if (!kern) return -1;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(kern, dim3(grid_stride_blocks(m * kBlocks)), dim3(256), 0, (hipStream_t)stream,
                        (const uint32_t *)templates, m, g0, k, nonce, parties, (uint16_t *)shares);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 }  // namespace iris

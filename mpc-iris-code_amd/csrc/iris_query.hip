@@ -199,7 +199,7 @@ int launch_query_template(void *stream, const void *q, uint32_t *tab, uint32_t *
     memcpy(a.mask, ((const iris_template_t *)q)->mask, sizeof(a.mask));
     hipLaunchKernelGGL(query_template_kernel, dim3(kPlaneDwords * 32 / 256), dim3(256), 0, (hipStream_t)stream, a,
                        tab, (uint4 *)frag);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_query_masks(void *stream, const void *qmask, uint32_t *tab, uint32_t *frag) {
@@ -207,20 +207,20 @@ int launch_query_masks(void *stream, const void *qmask, uint32_t *tab, uint32_t 
     memcpy(a.mask, qmask, sizeof(a.mask));
     hipLaunchKernelGGL(query_masks_kernel, dim3(kPlaneDwords * 32 / 256), dim3(256), 0, (hipStream_t)stream, a, tab,
                        frag);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_query_shares(void *stream, const void *q, uint32_t *tab, uint32_t *frag) {
     hipLaunchKernelGGL(query_shares_kernel, dim3(32), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)q, tab,
                        frag);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 int launch_query_tiles(void *stream, const void *queries, uint32_t nq, uint32_t nqp, uint32_t *tiles) {
     if (nqp == 0) return 0;
     hipLaunchKernelGGL(query_tiles_kernel, dim3(nqp), dim3(256), 0, (hipStream_t)stream,
                        (const iris_template_t *)queries, nq, (uint4 *)tiles);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return check_launch();
 }
 
 }  // namespace iris

@@ -143,42 +143,30 @@ uint32_t resolver_partials(uint64_t n) {
     return (uint32_t)((n + kWaveRows * kWaveSlots - 1) / (kWaveRows * kWaveSlots));
 }
 
-int launch_resolver(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
-                    double *dist_out, Partial *partials) {
-    if (n == 0) return 0;
-    if (parts == 0 || parts > (uint32_t)kMaxParts) return -1;
-    ResolverArgs a{};
-    for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
-    a.parts = parts;
-    hipLaunchKernelGGL(resolver_kernel<false>, dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a, denoms, n,
-                       dist_out, partials, MatchSink{});
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_resolver_match(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
-                          const MatchSink &ms) {
-    if (n == 0) return 0;
-    if (parts == 0 || parts > (uint32_t)kMaxParts) return -1;
-    ResolverArgs a{};
-    for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
-    a.parts = parts;
-    hipLaunchKernelGGL(resolver_kernel<true>, dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a, denoms, n,
-                       (double *)nullptr, (Partial *)nullptr, ms);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 uint64_t resolver_topk_units(uint64_t n) { return (uint64_t)resolver_partials(n) * kWaveSlots; }
 
-int launch_resolver_topk(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
-                         const MatchSink &ts) {
+template <bool MATCH, bool TOPK>
+static int resolver_pass(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                         const PassOut &o) {
     if (n == 0) return 0;
     if (parts == 0 || parts > (uint32_t)kMaxParts) return -1;
     ResolverArgs a{};
     for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
     a.parts = parts;
-    hipLaunchKernelGGL((resolver_kernel<false, true>), dim3(resolver_partials(n)), dim3(256), 0, (hipStream_t)stream, a,
-                       denoms, n, (double *)nullptr, (Partial *)nullptr, ts);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    hipLaunchKernelGGL((resolver_kernel<MATCH, TOPK>), dim3(resolver_partials(n)), dim3(64 * kWaveSlots), 0,
+                       (hipStream_t)stream, a, denoms, n, o.dist_out, o.partials, o.sink);
+    return check_launch();
+}
+
+int launch_resolver(Pass p, void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
+                    const PassOut &o) {
+    if (n != 0 && !o.fits(p)) return -1;
+    switch (p) {
+    case Pass::Search: return resolver_pass<false, false>(stream, shares, parts, denoms, n, o);
+    case Pass::Match: return resolver_pass<true, false>(stream, shares, parts, denoms, n, o);
+    case Pass::Topk: return resolver_pass<false, true>(stream, shares, parts, denoms, n, o);
+    default: return -1;
+    }
 }
 
 }  // namespace iris

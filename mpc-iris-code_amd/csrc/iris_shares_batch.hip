@@ -373,7 +373,7 @@ int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void
                                dim3((uint32_t)((ntiles + per_block - 1) / per_block)), dim3(256), 0, (hipStream_t)stream,
                                (const uint4 *)db, qs, t0, ntiles, r.first, r.first + r.n);
         }
-        if (hipGetLastError() != hipSuccess) return -1;
+        if (check_launch() != 0) return -1;
         if (forms) {
             (split ? forms->split : forms->large) += 1;
             (split ? forms->split_queries : forms->large_queries) += m;
