@@ -22,42 +22,20 @@
 
 namespace iris {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 constexpr int kBatchBQ = 4;                       // query padding unit of a batched engine
 constexpr int kTileU4 = kPlaneGroups * 64;        // 6400 uint4 per tile
-
-__device__ __forceinline__ v16f mfma4(const v8i &a, const v8i &b, const v16f &c) {
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 127, 0, 127);
-}
 
 // one workgroup per query: reduce its G partials
 __global__ void __launch_bounds__(256) batch_reduce_kernel(const Partial *__restrict__ partials, uint32_t G,
                                                            Partial *__restrict__ out, uint64_t idx_base) {
     const uint32_t q = blockIdx.x;
-    Partial c;
-    c.num = 0;
-    c.den = 0;
-    c.rot = 0;
-    c.pad = 0;
-    c.idx = ~0ull;
+    Partial b = partial_none();
     for (uint32_t i = threadIdx.x; i < G; i += blockDim.x) {
         const Partial p = partials[(uint64_t)q * G + i];
-        if (partial_better_dev(p, c)) c = p;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const Partial o = partial_shfl_xor(c, off);
-        if (partial_better_dev(o, c)) c = o;
+        if (partial_better_dev(p, b)) b = p;
     }
     __shared__ Partial sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Partial b = sh[0];
-        for (int i = 1; i < 4; ++i)
-            if (partial_better_dev(sh[i], b)) b = sh[i];
+    if (block_argmin(b, sh, 4)) {
         if (b.den != 0) b.idx += idx_base;
         out[q] = b;
     }
@@ -314,10 +292,10 @@ __global__ void __launch_bounds__(64 * NW, 1)
                 const v8i a_d = {(int)fa[qi].x, (int)fa[qi].y, (int)fa[qi].z, (int)fa[qi].w, 0, 0, 0, 0};
                 const v8i a_e = {(int)fe[qi].x, (int)fe[qi].y, (int)fe[qi].z, (int)fe[qi].w, 0, 0, 0, 0};
 #pragma unroll
-                for (int t = 0; t < WT; ++t) den[qi][t] = mfma4(a_d, bd[t], den[qi][t]);
+                for (int t = 0; t < WT; ++t) den[qi][t] = mfma_fp4(a_d, bd[t], den[qi][t]);
                 if (nb) na[qi] = frag(b + 1, 0, qi);
 #pragma unroll
-                for (int t = 0; t < WT; ++t) sacc[qi][t] = mfma4(a_e, be[t], sacc[qi][t]);
+                for (int t = 0; t < WT; ++t) sacc[qi][t] = mfma_fp4(a_e, be[t], sacc[qi][t]);
                 if (nb) ne[qi] = frag(b + 1, 1, qi);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -487,11 +465,7 @@ __global__ void __launch_bounds__(64 * NW, 1)
                     c.rot = (int)(run_jr[qi] & 31u);
                     c.idx = (tile0 + trel) * 32 + (lane & 31) - first;
                 }
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) {
-                    const Partial o = partial_shfl_xor(c, off);
-                    if (partial_better_rot(o, c)) c = o;
-                }
+                c = wave_argmin(c, RotationOrder());
                 if (lane == qi) best = c;
             }
             wave_best = best;
@@ -521,9 +495,8 @@ uint32_t batch_query_group() { return kBatchBQ; }
 
 BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq) {
     BatchGeometry g;
-    g.tile0 = r.first / 32;
-    const uint64_t tile1 = (r.first + r.n + 31) / 32;
-    g.ntiles = tile1 - g.tile0;
+    g.tile0 = tile_span(r).tile0;
+    g.ntiles = tile_span(r).ntiles;
     const int kc = batch_kernel_choice(h);
     g.qper = kc == 4 ? 2 : 4;  // queries per query group
     g.nqg = (nq + g.qper - 1) / g.qper;

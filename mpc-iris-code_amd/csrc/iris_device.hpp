@@ -22,13 +22,66 @@ static inline uint64_t resident_blocks(int per_cu) {
     return (uint64_t)n * per_cu;
 }
 
+// Tiles per wave for a range of `ntiles` tiles: `big`, unless that leaves fewer waves
+// than the chip holds at two workgroups per CU — then one, for 8x / 4x / 2x the waves
+// (a participant-sized chunk of 20k records is only 625 tiles).  IRIS_TILES_PER_WAVE=1|4
+// pins the small or the big variant (tests run both).
+static inline int tiles_per_wave(const Hooks &h, uint64_t ntiles, int big) {
+    if (h.tiles_per_wave) return h.tiles_per_wave == 1 ? 1 : big;
+    return ntiles / big < (uint64_t)resident_blocks(2) * kWaveSlots ? 1 : big;
+}
+
 // The template kind's TILES record plumbing (iris_mfma.hip), launched with the other kinds' from
 // launch_*_tiles_kind (iris_engines_mfma.hip): grid-stride loops over n * 2 * kPlaneGroups items
 __global__ void __launch_bounds__(256) pack_tiles_kernel(const uint32_t *__restrict__ staging, uint4 *__restrict__ db, uint64_t t_first, uint64_t n);
 __global__ void __launch_bounds__(256) unpack_tiles_kernel(const uint4 *__restrict__ db, uint32_t *__restrict__ staging, uint64_t t_first, uint64_t n);
 __global__ void __launch_bounds__(256) generate_tiles_kernel(uint4 *__restrict__ db, uint64_t t_first, uint64_t n, uint64_t key, uint64_t global_index0);
 
+// ---------------------------------------------------------------- primitives of the MFMA kernels
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4_nt __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kTile = 32;  // records of a TILES tile: the N of one 32x32 MFMA
+
+// 16-B nontemporal load: a database stream that this launch reads once
+__device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
+    const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+// 16-B copies through a vector type (a uint4 struct copy between address spaces is a memcpy that
+// keeps its register copy in scratch memory)
+__device__ __forceinline__ uint4 load16(const uint4 *p) {
+    const u32x4 v = *(const u32x4 *)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store16(uint4 *p, const uint4 &v) { *(u32x4 *)p = u32x4{v.x, v.y, v.z, v.w}; }
+
+__device__ __forceinline__ v16f mfma_fp4(const v8i &a, const v8i &b, const v16f &c) {
+    // cbsz = blgp = 4: both operands e2m1; scales 127 = 2^0 (e8m0)
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 127, 0, 127);
+}
+__device__ __forceinline__ v16i mfma_i8(const uint4 &a, const uint4 &b, const v16i &c) {
+    const v4i av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w};
+    const v4i bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w};
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, c, 0, 0, 0);
+}
+
+// MasksEngine operands of one 64-bit chunk: A from a compact query word, B from one dword of a mask
+// tile (8 masks' nibbles) -- kMaskFragUint4, kMaskTileUint4 in iris_internal.hpp
+__device__ __forceinline__ v8i mask_a(uint32_t w) {
+    return v8i{(int)(w & 0x44444444u), (int)(w & 0x22222222u), (int)(w & 0x11111111u), (int)((w >> 3) & 0x11111111u),
+               0, 0, 0, 0};
+}
+__device__ __forceinline__ v8i mask_b(uint32_t x) {
+    return v8i{(int)(x & 0x11111111u), (int)(x & 0x22222222u), (int)(x & 0x44444444u), (int)((x >> 1) & 0x44444444u),
+               0, 0, 0, 0};
+}
+__device__ __forceinline__ void mask_chunk(uint32_t x, const v8i &a, v16f &acc) { acc = mfma_fp4(a, mask_b(x), acc); }
 
 // 16-B store written through the XCD's L2 (sc1: the line leaves L2 and is dropped there; the same
 // cost as a plain 16-B store, MI355X_MICROARCH.md "stores of each flavour").
@@ -186,6 +239,57 @@ __device__ __forceinline__ Partial partial_shfl_xor(const Partial &c, int off) {
     return o;
 }
 
+__device__ __forceinline__ Partial partial_of(uint32_t num, uint32_t den, int rot, uint64_t idx) {
+    Partial p;
+    p.num = num;
+    p.den = den;
+    p.rot = rot;
+    p.pad = 0;
+    p.idx = idx;
+    return p;
+}
+__device__ __forceinline__ Partial partial_none() { return partial_of(0, 0, 0, ~0ull); }
+
+// The wave's best candidate in every lane: the 64-lane butterfly under `better` (the search order
+// unless given: the LANES kernels and the batch kernel's rotation tie-break bring their own).
+struct SearchOrder {
+    __device__ __forceinline__ bool operator()(const Partial &a, const Partial &b) const { return partial_better_dev(a, b); }
+};
+struct RotationOrder {  // then the lower rotation: two candidates of one template
+    __device__ __forceinline__ bool operator()(const Partial &a, const Partial &b) const { return partial_better_rot(a, b); }
+};
+template <class Better = SearchOrder>
+__device__ __forceinline__ Partial wave_argmin(Partial c, Better better = Better()) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const Partial o = partial_shfl_xor(c, off);
+        if (better(o, c)) c = o;
+    }
+    return c;
+}
+// One thread's fold of n waves' bests sh[0 .. n) into b
+template <class Better = SearchOrder>
+__device__ __forceinline__ void fold_waves(Partial &b, const Partial *sh, int n, Better better = Better()) {
+    b = sh[0];
+    for (int w = 1; w < n; ++w)
+        if (better(sh[w], b)) b = sh[w];
+}
+// The workgroup's best of one candidate per thread (every thread calls this, sh: one entry per wave):
+// each wave's butterfly, lane 0 of each wave to sh[], a barrier, and thread 0 folds the waves' bests
+// into c.  True in thread 0 only.  nwaves: a constant (a workgroup sized at run time folds by
+// hand, so that its wave count is not kept across the barrier).
+template <class Better = SearchOrder>
+__device__ __forceinline__ bool block_argmin(Partial &c, Partial *sh, int nwaves, Better better = Better()) {
+    c = wave_argmin(c, better);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+    Partial b;
+    fold_waves(b, sh, nwaves, better);
+    c = b;
+    return true;
+}
+
 // One template's best rotation from a 32x32 MFMA C tile: lane l holds rows
 // k = (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 0..15, of template l & 31, and
 // frac(r, num, den) yields row r's fraction.  Exact order (u32 cross-
@@ -216,16 +320,6 @@ __device__ __forceinline__ void best_rotation(int lane, F frac, uint32_t &bn, ui
         bd = pd;
         br = pr;
     }
-}
-
-__device__ __forceinline__ Partial partial_none() {
-    Partial p;
-    p.num = 0;
-    p.den = 0;
-    p.rot = 0;
-    p.pad = 0;
-    p.idx = ~0ull;
-    return p;
 }
 
 // Threshold matching (MatchSink, iris_internal.hpp).  The decision is the f64 comparison the
@@ -435,18 +529,13 @@ __device__ __forceinline__ void fold_partials_last(Partial *partials, const Part
         const Partial p = read_partial(&partials[i]);
         if (partial_better_dev(p, c)) c = p;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const Partial o = partial_shfl_xor(c, off);
-        if (partial_better_dev(o, c)) c = o;
-    }
+    c = wave_argmin(c);
     __shared__ Partial sw[16];
     if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
-        Partial b = sw[0];
-        for (uint32_t w = 1; w < (blockDim.x + 63) / 64; ++w)
-            if (partial_better_dev(sw[w], b)) b = sw[w];
+        Partial b;
+        fold_waves(b, sw, (int)((blockDim.x + 63) / 64));
         if (b.den != 0) b.idx += fin.idx_base;
         __hip_atomic_store(fin.ticket, 0u, __ATOMIC_RELAXED, IRIS_FUSED_SCOPE);  // for the next launch
         if (fin.done) {

@@ -16,17 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
-#include "iris_device.hpp"
+#include "iris_engines_device.hpp"
 
 namespace iris {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kTile = 32;
 // tiles per wave: 7 for the [u16;31] output (longer groups, fewer store bursts than 4:
 // round 2 measured 8 at 2.88-2.98 vs 2.98-3.03 ms per 10M for 4; but 8 tiles need 29 VGPRs
 // of scratch spills at two waves per SIMD, and 7 -- 252 VGPRs, none spilled -- runs 2.894-2.896
@@ -50,43 +43,17 @@ template <int MODE>
 constexpr int masks_blocks_per_cu() { return !masks_resolving(MODE) ? kMasksBlocksPerCu : kResolveBlocksPerCu; }
 constexpr int kSharesTiles = 2;
 
-__device__ __forceinline__ uint4 nt_load(const uint4 *p) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
 struct Tiles {
     uint64_t tile0, ntiles, grid;
 };
 
 static Tiles tiles_of(LaunchRange r, int per_wave) {
-    Tiles t;
-    t.tile0 = r.first / kTile;
-    const uint64_t tile1 = (r.first + r.n + kTile - 1) / kTile;
-    t.ntiles = tile1 - t.tile0;
-    const uint64_t waves = (t.ntiles + per_wave - 1) / per_wave;
-    t.grid = (waves + kWaveSlots - 1) / kWaveSlots;
-    return t;
+    const TileSpan s = tile_span(r);
+    const uint64_t waves = (s.ntiles + per_wave - 1) / per_wave;
+    return Tiles{s.tile0, s.ntiles, (waves + kWaveSlots - 1) / kWaveSlots};
 }
 
 // ------------------------------------------------------------------ masks (fp4)
-
-__device__ __forceinline__ v16f mfma_fp4(const v8i &a, const v8i &b, const v16f &c) {
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 127, 0, 127);
-}
-
-// x: one dword of a mask tile (8 masks' nibbles); w: the compact query word of
-// the same chunk (see kMaskFragUint4)
-__device__ __forceinline__ v8i mask_a(uint32_t w) {
-    return v8i{(int)(w & 0x44444444u), (int)(w & 0x22222222u), (int)(w & 0x11111111u), (int)((w >> 3) & 0x11111111u),
-               0, 0, 0, 0};
-}
-
-__device__ __forceinline__ void mask_chunk(uint32_t x, const v8i &a, v16f &acc) {
-    const v8i b = {(int)(x & 0x11111111u), (int)(x & 0x22222222u), (int)(x & 0x44444444u),
-                   (int)((x >> 1) & 0x44444444u), 0, 0, 0, 0};
-    acc = mfma_fp4(a, b, acc);
-}
 
 // Fused resolver operands (MASKS_RESOLVE): the participants' [n][31] u16
 // outputs, row i = record first + i (src/main.rs:597-607).
@@ -148,65 +115,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
     };
-    // resolver epilogue of one tile (records t0 .. t0+31 of the database)
-    auto resolve_tile = [&](uint64_t t0, bool tv, const v16f &den) {
-        const bool full = tv && t0 >= first && t0 + 32 <= end && ((t0 - first) & 7) == 0 && rs.aligned;
-        const uint64_t e0 = (t0 - first) * kRot;  // first share element of the tile (when full)
-        if (full) {  // wave-uniform: 124 16-B words per share array
-            typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-            for (int i = lane; i < 32 * kRot / 8; i += 64) {
-                // plain loads (nontemporal measured the same, 2.75-2.79 ms per 10M either way)
-                u16x8 v = *(const u16x8 *)(rs.shares[0] + e0 + 8 * i);
-                for (uint32_t p = 1; p < rs.parts; ++p) v += *(const u16x8 *)(rs.shares[p] + e0 + 8 * i);
-                *(u16x8 *)&lds[8 * i] = v;
-            }
-        } else {
-            for (int i = lane; i < 32 * kRot; i += 64) {
-                const uint64_t tg = t0 + (uint64_t)(i / kRot);
-                uint16_t v = 0;
-                if (tv && tg >= first && tg < end) {
-                    const uint64_t e = (tg - first) * kRot + (uint64_t)(i % kRot);
-                    for (uint32_t p = 0; p < rs.parts; ++p) v = (uint16_t)(v + rs.shares[p][e]);
-                }
-                lds[i] = v;
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed
-        __builtin_amdgcn_wave_barrier();
-        const int h = lane >> 5;
-        uint32_t bn, bd;
-        int br;
-        best_rotation(lane, [&](int r, uint32_t &u, uint32_t &d) {
-            const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-            d = (uint32_t)den[r] & 0xFFFFu;  // the MasksEngine output value (u16)
-            u = k < kRot ? (uint32_t)((uint16_t)(d - lds[(lane & 31) * kRot + k]) >> 1) : 0;  // src/lib.rs:104
-        }, bn, bd, br);
-        const uint64_t tg = t0 + (lane & 31);
-        const bool valid = tv && tg >= first && tg < end;
-        if constexpr (MODE == MASKS_MATCH) {
-            const bool hit[1] = {match_hit(rs.match, valid && h == 0, bn, bd)};
-            const uint32_t hn[1] = {bn}, hd[1] = {bd};
-            const int hr[1] = {br};
-            const uint64_t hi[1] = {tg - first};
-            append_matches<1>(rs.match, lane, hit, hn, hd, hr, hi);
-            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
-            return;
-        }
-        if (valid && rs.dist_out && h == 0) rs.dist_out[tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
-        Partial c;
-        c.num = bn;
-        c.den = valid ? bd : 0;
-        c.rot = br;
-        c.pad = 0;
-        c.idx = tg - first;
-        if constexpr (MODE == MASKS_TOPK) {  // best: this lane's entry of the wave's list
-            topk_insert(best, (uint32_t)rs.match.cap, lane, c, h == 0);
-            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
-            return;
-        }
-        if (partial_better_dev(c, best)) best = c;
-        __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
-    };
+    const ResolveView view{rs.shares, rs.parts, 0, rs.aligned, rs.match, rs.dist_out, best};
     if (total) {
         zero();
         struct Stage {
@@ -220,7 +129,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const uint64_t rel = (tw + t < ntiles) ? tw + t : ntiles - 1;
-                st.d[t] = nt_load(db + (tile0 + rel) * (uint64_t)kMaskTileUint4 + g * 64 + lane);
+                st.d[t] = nt_load16(db + (tile0 + rel) * (uint64_t)kMaskTileUint4 + g * 64 + lane);
             }
             st.w = sq[g * 64 + lane];
             __builtin_amdgcn_sched_barrier(0);
@@ -247,7 +156,8 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
                         store_tile_packed((uint8_t *)out, out + (end - first) * 16, (tile0 + tw + t) * kTile, first, end,
                                           tw + t < ntiles, lane, [&](int r) { return (uint32_t)acc[t][r]; });
                     else
-                        resolve_tile((tile0 + tw + t) * kTile, tw + t < ntiles, acc[t]);
+                        resolve_tile<MODE == MASKS_MATCH, MODE == MASKS_TOPK>(view, lds, lane, (tile0 + tw + t) * kTile,
+                                                                             tw + t < ntiles, acc[t], first, end);
                 }
                 zero();
             }
@@ -267,20 +177,8 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
     }
     if constexpr (MODE == MASKS_TOPK) topk_store(rs.match, wave, lane, best);  // every wave of the grid: one list
     if constexpr (MODE == MASKS_RESOLVE) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const Partial o = partial_shfl_xor(best, off);
-            if (partial_better_dev(o, best)) best = o;
-        }
         __shared__ Partial sh_best[kWaveSlots];
-        if (lane == 0) sh_best[threadIdx.x >> 6] = best;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            Partial b = sh_best[0];
-            for (int w = 1; w < kWaveSlots; ++w)
-                if (partial_better_dev(sh_best[w], b)) b = sh_best[w];
-            rs.partials[blockIdx.x] = b;
-        }
+        if (block_argmin(best, sh_best, kWaveSlots)) rs.partials[blockIdx.x] = best;
     }
 }
 
@@ -292,7 +190,6 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
 // persistent kernel's ~25 dependent ones; the slices' counts (exact integers in f32)
 // meet in LDS and wave 0 writes the tile's rows.
 constexpr int kMasksSplitKS = 10;
-constexpr uint64_t kMasksSplitTiles = 1024;
 
 template <int KS, bool PACKED = false>
 __global__ void __launch_bounds__(64 * KS)
@@ -308,7 +205,7 @@ __global__ void __launch_bounds__(64 * KS)
     const uint4 *qp = qfrag + (uint64_t)slice * kG * 64 + lane;
     uint4 d[kG], w[kG];
 #pragma unroll
-    for (int g = 0; g < kG; ++g) d[g] = nt_load(dp + g * 64);
+    for (int g = 0; g < kG; ++g) d[g] = nt_load16(dp + g * 64);
 #pragma unroll
     for (int g = 0; g < kG; ++g) w[g] = qp[g * 64];
     v16f acc;
@@ -346,20 +243,11 @@ __global__ void __launch_bounds__(64 * KS)
     }
 }
 
-// Tiles per wave for a range of `ntiles` tiles: `big`, unless that leaves fewer waves
-// than the chip holds at two workgroups per CU — then one, for 8x / 4x / 2x the waves
-// (a participant-sized chunk of 20k records is only 625 tiles).  IRIS_TILES_PER_WAVE=1|4
-// pins the small or the big variant (tests run both).
-static int tiles_per_wave(const Hooks &h, uint64_t ntiles, int big) {
-    if (h.tiles_per_wave) return h.tiles_per_wave == 1 ? 1 : big;
-    return ntiles / big < (uint64_t)resident_blocks(2) * kWaveSlots ? 1 : big;
-}
-
 int launch_masks_mfma(const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r, uint16_t *out,
                       DoneSignal *sig, bool packed) {
     if (sig) sig->armed = false;
     if (r.n == 0) return 0;
-    const uint64_t ntiles = tiles_of(r, 1).ntiles;
+    const uint64_t ntiles = tile_span(r).ntiles;
     // the K-split form for small ranges (IRIS_TILES_PER_WAVE pins the persistent kernel for tests)
     if (ntiles <= kMasksSplitTiles && !h.tiles_per_wave) {
         DoneSignal s{};
@@ -369,7 +257,7 @@ int launch_masks_mfma(const Hooks &h, void *stream, const void *db, const void *
         }
         auto kern = packed ? masks_split_kernel<kMasksSplitKS, true> : masks_split_kernel<kMasksSplitKS>;
         hipLaunchKernelGGL(kern, dim3((uint32_t)ntiles), dim3(64 * kMasksSplitKS), 0, (hipStream_t)stream,
-                           (const uint4 *)db, (const uint4 *)qfrag, tiles_of(r, 1).tile0, r.first, r.first + r.n, out, s);
+                           (const uint4 *)db, (const uint4 *)qfrag, tile_span(r).tile0, r.first, r.first + r.n, out, s);
         return check_launch();
     }
     const int tpw = tiles_per_wave(h, ntiles, kMasksTiles);
@@ -384,7 +272,7 @@ int launch_masks_mfma(const Hooks &h, void *stream, const void *db, const void *
 }
 
 uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r) {
-    const Tiles t = tiles_of(r, tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles));
+    const Tiles t = tiles_of(r, tiles_per_wave(h, tile_span(r).ntiles, kResolveTiles));
     return (uint32_t)std::min<uint64_t>(t.grid, resident_blocks(masks_blocks_per_cu<MASKS_RESOLVE>()));
 }
 
@@ -397,7 +285,7 @@ static int masks_resolve_pass(const Hooks &h, void *stream, const void *db, cons
                               const uint16_t *const *shares, uint32_t parts, const PassOut &o) {
     if (r.n == 0) return 0;
     if (parts == 0 || parts > 8) return -1;
-    const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kResolveTiles);
+    const int tpw = tiles_per_wave(h, tile_span(r).ntiles, kResolveTiles);
     const Tiles t = tiles_of(r, tpw);
     const uint64_t grid = masks_resolve_partials(h, r);
     MaskResolve rs{};
@@ -430,20 +318,12 @@ int launch_masks_resolve(Pass p, const Hooks &h, void *stream, const void *db, c
 
 // ------------------------------------------------------------------ shares (i8)
 
-__device__ __forceinline__ v16i mfma_i8(const uint4 &a, const uint4 &b, const v16i &c) {
-    const v4i av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w};
-    const v4i bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w};
-    return __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, c, 0, 0, 0);
-}
-
 template <int T = kSharesTiles>
 __global__ void __launch_bounds__(256, 2)
     shares_mfma_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, const int2 *__restrict__ qsum,
                        uint64_t tile0, uint64_t ntiles, uint64_t first, uint64_t end, uint16_t *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * kWaveSlots + (threadIdx.x >> 6);
-    constexpr int kSteps = kShareChunks / 2;  // steps of 2 chunks
-    constexpr int g0 = 0;
     const uint64_t tw = wave * T;
     if (tw >= ntiles) return;
     v16i s1[T], s2[T];
@@ -460,72 +340,13 @@ __global__ void __launch_bounds__(256, 2)
         const uint64_t rel = (tw + t < ntiles) ? tw + t : ntiles - 1;
         dp[t] = db + (tile0 + rel) * (uint64_t)kShareTileUint4 + lane;
     }
-    const uint4 *qp = qfrag + lane;  // chunk c: lo [(2c) * 64 + lane], hi [(2c+1) * 64 + lane]
-    struct Stage {
-        uint4 lo[T][2], hi[T][2];
-        uint4 qlo[2], qhi[2];
-    };
-    auto load = [&](Stage &st, int g) {
-        g = g0 + (g < kSteps ? g : kSteps - 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = 2 * g + i;
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                st.lo[t][i] = nt_load(dp[t] + (2 * c) * 64);
-                st.hi[t][i] = nt_load(dp[t] + (2 * c + 1) * 64);
-            }
-            st.qlo[i] = qp[(2 * c) * 64];
-            st.qhi[i] = qp[(2 * c + 1) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto compute = [&](const Stage &st) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                s1[t] = mfma_i8(st.qlo[i], st.lo[t][i], s1[t]);
-                s2[t] = mfma_i8(st.qlo[i], st.hi[t][i], s2[t]);
-                s2[t] = mfma_i8(st.qhi[i], st.lo[t][i], s2[t]);
-            }
-    };
-    Stage sa, sb, sc;
-    load(sa, 0);
-    load(sb, 1);
-    int g = 0;
-#pragma unroll 1
-    for (; g + 3 <= kSteps; g += 3) {
-        load(sc, g + 2);
-        compute(sa);
-        load(sa, g + 3);
-        compute(sb);
-        load(sb, g + 4);
-        compute(sc);
-    }
-    // kSteps = 3q + {0, 1, 2} (200 = 66 * 3 + 2)
-    if (g < kSteps) compute(sa);
-    if (g + 1 < kSteps) compute(sb);
+    shares_accumulate<kShareChunks / 2>(dp, qfrag + lane, 0, s1, s2);  // steps of 2 chunks
 
-    // row 31 (lane t + 32, register 15) holds sum e'_lo in S1 and sum e'_hi + sum e'_lo in S2
-    const int h = lane >> 5;
-    const int src = (lane & 31) + 32;
     __shared__ __attribute__((aligned(16))) uint16_t sh_out[kWaveSlots][1024];
     uint16_t *lds = sh_out[threadIdx.x >> 6];
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const int elo = __shfl(s1[t][15], src);
-        const int ehi = __shfl(s2[t][15], src) - elo;
-        store_tile_rows(out, lds, (tile0 + tw + t) * kTile, first, end, tw + t < ntiles, lane, [&](int r) {
-            const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int2 qs = qsum[k < kRot ? k : 0];  // (sum q'_lo, sum q'_hi) of row k
-            // the 16384 * K terms vanish mod 2^16 (K = 12800)
-            const uint32_t lo = (uint32_t)s1[t][r] + 128u * (uint32_t)elo + 128u * (uint32_t)qs.x;
-            const uint32_t cross = (uint32_t)s2[t][r] + 128u * (uint32_t)ehi + 128u * (uint32_t)qs.x +
-                                   128u * (uint32_t)elo + 128u * (uint32_t)qs.y;
-            return (uint16_t)(lo + 256u * cross);
-        });
-    }
+    for (int t = 0; t < T; ++t)
+        store_query_tile(out, lds, qsum, s1[t], s2[t], (tile0 + tw + t) * kTile, first, end, tw + t < ntiles, lane);
 }
 
 // Small ranges (the participant's 20 000-record chunks, src/main.rs:427-431): a workgroup of
@@ -538,7 +359,6 @@ __global__ void __launch_bounds__(256, 2)
 // form (up to 10 slices through an HBM workspace + a combine launch) 109 + 4 us
 constexpr int kSharesSplitT = 1;
 constexpr int kSharesSplitKS = 2;
-constexpr uint64_t kSharesSplitTiles = 4096;
 
 template <int T, int KS>
 __global__ void __launch_bounds__(64 * KS, 2)
@@ -550,7 +370,6 @@ __global__ void __launch_bounds__(64 * KS, 2)
     const int lane = threadIdx.x & 63;
     const int slice = threadIdx.x >> 6;
     const uint64_t tw = (uint64_t)blockIdx.x * T;
-    const int g0 = slice * kSteps;
     v16i s1[T], s2[T];
 #pragma unroll
     for (int t = 0; t < T; ++t)
@@ -565,89 +384,18 @@ __global__ void __launch_bounds__(64 * KS, 2)
         const uint64_t rel = (tw + t < ntiles) ? tw + t : ntiles - 1;
         dp[t] = db + (tile0 + rel) * (uint64_t)kShareTileUint4 + lane;
     }
-    const uint4 *qp = qfrag + lane;
-    struct Stage {
-        uint4 lo[T][2], hi[T][2];
-        uint4 qlo[2], qhi[2];
-    };
-    auto load = [&](Stage &st, int g) {
-        g = g0 + (g < kSteps ? g : kSteps - 1);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = 2 * g + i;
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                st.lo[t][i] = nt_load(dp[t] + (2 * c) * 64);
-                st.hi[t][i] = nt_load(dp[t] + (2 * c + 1) * 64);
-            }
-            st.qlo[i] = qp[(2 * c) * 64];
-            st.qhi[i] = qp[(2 * c + 1) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto compute = [&](const Stage &st) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                s1[t] = mfma_i8(st.qlo[i], st.lo[t][i], s1[t]);
-                s2[t] = mfma_i8(st.qlo[i], st.hi[t][i], s2[t]);
-                s2[t] = mfma_i8(st.qhi[i], st.lo[t][i], s2[t]);
-            }
-    };
-    Stage sa, sb, sc;
-    load(sa, 0);
-    load(sb, 1);
-    int g = 0;
-#pragma unroll 1
-    for (; g + 3 <= kSteps; g += 3) {
-        load(sc, g + 2);
-        compute(sa);
-        load(sa, g + 3);
-        compute(sb);
-        load(sb, g + 4);
-        compute(sc);
-    }
-    if (g < kSteps) compute(sa);
-    if (g + 1 < kSteps) compute(sb);
+    shares_accumulate<kSteps>(dp, qfrag + lane, slice * kSteps, s1, s2);
 
-    __shared__ int red[KS - 1][T][2][16][64];
+    __shared__ SliceSums<KS, T> red;
     __shared__ __attribute__((aligned(16))) uint16_t sh_out[1024];
-    if (slice != 0) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                red[slice - 1][t][0][i][lane] = s1[t][i];
-                red[slice - 1][t][1][i][lane] = s2[t][i];
-            }
-    }
+    if (slice != 0) slice_put<KS, T>(red, slice, lane, s1, s2);
     __syncthreads();
     if (slice != 0) return;
 #pragma unroll
-    for (int k = 0; k < KS - 1; ++k)
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                s1[t][i] += red[k][t][0][i][lane];
-                s2[t][i] += red[k][t][1][i][lane];
-            }
-    // row 31 (lane t + 32, register 15) holds sum e'_lo in S1 and sum e'_hi + sum e'_lo in S2
-    const int h = lane >> 5;
-    const int src = (lane & 31) + 32;
-#pragma unroll
     for (int t = 0; t < T; ++t) {
-        const int elo = __shfl(s1[t][15], src);
-        const int ehi = __shfl(s2[t][15], src) - elo;
-        store_tile_rows(out, sh_out, (tile0 + tw + t) * kTile, first, end, tw + t < ntiles, lane, [&](int r) {
-            const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int2 qs = qsum[k < kRot ? k : 0];  // (sum q'_lo, sum q'_hi) of row k
-            const uint32_t lo = (uint32_t)s1[t][r] + 128u * (uint32_t)elo + 128u * (uint32_t)qs.x;
-            const uint32_t cross = (uint32_t)s2[t][r] + 128u * (uint32_t)ehi + 128u * (uint32_t)qs.x +
-                                   128u * (uint32_t)elo + 128u * (uint32_t)qs.y;
-            return (uint16_t)(lo + 256u * cross);
-        }, sig.done != nullptr);
+        slice_add<KS, T>(red, t, lane, s1[t], s2[t]);
+        store_query_tile(out, sh_out, qsum, s1[t], s2[t], (tile0 + tw + t) * kTile, first, end, tw + t < ntiles, lane,
+                         sig.done != nullptr);
     }
     if (sig.done) {  // wave 0 stored the workgroup's rows: once they are performed, take the ticket
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -666,7 +414,7 @@ int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void 
     if (sig) sig->armed = false;
     if (r.n == 0) return 0;
     const int2 *qsum = (const int2 *)((const uint4 *)qfrag + kShareFragUint4);
-    if (shares_lds_split(h, tiles_of(r, 1).ntiles)) {
+    if (shares_lds_split(h, tile_span(r).ntiles)) {
         const Tiles t = tiles_of(r, 1);
         DoneSignal s{};
         if (sig) {
@@ -679,7 +427,7 @@ int launch_shares_mfma(const Hooks &h, void *stream, const void *db, const void 
                            r.first + r.n, out, s);
         return check_launch();
     }
-    const int tpw = tiles_per_wave(h, tiles_of(r, 1).ntiles, kSharesTiles);
+    const int tpw = tiles_per_wave(h, tile_span(r).ntiles, kSharesTiles);
     const Tiles t = tiles_of(r, tpw);
     auto kern = tpw == 1 ? shares_mfma_kernel<1> : shares_mfma_kernel<>;
     hipLaunchKernelGGL(kern, dim3((uint32_t)t.grid), dim3(256), 0, (hipStream_t)stream, (const uint4 *)db,

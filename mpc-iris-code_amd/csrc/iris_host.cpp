@@ -13,6 +13,11 @@
 
 namespace iris {
 
+TileSpan tile_span(LaunchRange r) {
+    const uint64_t tile0 = r.first / 32;
+    return TileSpan{tile0, (r.first + r.n + 31) / 32 - tile0};
+}
+
 static inline int wrap_col(int c) {
     c %= IRIS_COLS;
     return c < 0 ? c + IRIS_COLS : c;

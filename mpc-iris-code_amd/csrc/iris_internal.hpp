@@ -242,6 +242,16 @@ struct LaunchRange {
     uint64_t first;  // first record index of the range
     uint64_t n;      // records in the range
 };
+// The 32-record tiles of a TILES database that a range touches: its first tile and their number
+// (the first and the last may be partial).  iris_host.cpp: plain host code, tested on the CPU.
+struct TileSpan {
+    uint64_t tile0, ntiles;
+};
+TileSpan tile_span(LaunchRange r);
+// Up to this many tiles a range runs its engine's K-split form, single-query and batched alike
+// (the resolver's and the participants' 20 000-record chunks are 625 tiles).
+constexpr uint64_t kMasksSplitTiles = 1024;
+constexpr uint64_t kSharesSplitTiles = 4096;
 
 // What a pass over a range does with each record's best rotation.  A family's launcher takes the
 // pass as a value and picks its kernel's own mode constant; one it has no kernel for is refused.

@@ -91,26 +91,10 @@ __device__ __forceinline__ bool better(const Partial &a, const Partial &b) {
     return a.idx < b.idx;
 }
 
-__device__ __forceinline__ Partial shfl_xor_partial(const Partial &c, int off) {
-    Partial o;
-    o.num = __shfl_xor(c.num, off);
-    o.den = __shfl_xor(c.den, off);
-    o.rot = __shfl_xor(c.rot, off);
-    o.pad = 0;
-    const uint32_t lo = __shfl_xor((uint32_t)c.idx, off);
-    const uint32_t hi = __shfl_xor((uint32_t)(c.idx >> 32), off);
-    o.idx = ((uint64_t)hi << 32) | lo;
-    return o;
-}
-
-__device__ __forceinline__ Partial wave_best(Partial c) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const Partial o = shfl_xor_partial(c, off);
-        if (better(o, c)) c = o;
-    }
-    return c;
-}
+// the order of the shared argmin helpers (iris_device.hpp) in this file
+struct LanesOrder {
+    __device__ __forceinline__ bool operator()(const Partial &a, const Partial &b) const { return better(a, b); }
+};
 
 // ------------------------------------------------------------------ template kernel
 
@@ -175,11 +159,7 @@ __global__ void __launch_bounds__(256, 5)
         // first (lowest r) rotation wins ties — f64 quotients of distinct
         // fractions n/d with n,d <= 12800 are distinct, so this equals the
         // reference's fold(INF, f64::min) over (n as f64)/(d as f64).
-        Partial c;
-        c.num = 0;
-        c.den = 0;
-        c.rot = 0;
-        c.pad = 0;
+        Partial c = partial_none();
         c.idx = o;
 #pragma unroll
         for (int r = 0; r < kRot; ++r) {
@@ -217,17 +197,8 @@ __global__ void __launch_bounds__(256, 5)
         }
         if (valid && dist_out) dist_out[o] = c.den ? (double)c.num / (double)c.den : __builtin_inf();
 
-        c = wave_best(c);
         __shared__ Partial sh[kWaveSlots];
-        if (lane == 0) sh[wslot] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            Partial b = sh[0];
-#pragma unroll
-            for (int w = 1; w < kWaveSlots; ++w)
-                if (better(sh[w], b)) b = sh[w];
-            partials[blockIdx.x] = b;
-        }
+        if (block_argmin(c, sh, kWaveSlots, LanesOrder())) partials[blockIdx.x] = c;
     }
 }
 
@@ -316,26 +287,18 @@ __global__ void __launch_bounds__(256, 8)
 // workgroup) first go through reduce_stage_kernel below.
 __global__ void __launch_bounds__(1024) reduce_kernel(const Partial *__restrict__ partials, uint32_t n,
                                                       Partial *__restrict__ out, uint32_t stride, uint64_t idx_base) {
-    Partial c;
-    c.num = 0;
-    c.den = 0;
-    c.rot = 0;
-    c.pad = 0;
-    c.idx = ~0ull;
+    Partial c = partial_none();
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
         const Partial p = partials[(uint64_t)i * stride];
         if (better(p, c)) c = p;
     }
-    c = wave_best(c);
+    c = wave_argmin(c, LanesOrder());
     __shared__ Partial sh[16];
-    const int wslot = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[wslot] = c;
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
-        Partial b = sh[0];
-        const int nw = (blockDim.x + 63) / 64;
-        for (int w = 1; w < nw; ++w)
-            if (better(sh[w], b)) b = sh[w];
+        Partial b;
+        fold_waves(b, sh, (blockDim.x + 63) / 64, LanesOrder());
         if (b.den != 0) b.idx += idx_base;  // range-relative -> caller's index space
         *out = b;
     }
@@ -349,12 +312,7 @@ __global__ void __launch_bounds__(256) group_merge_kernel(const Partial *__restr
                                                           uint32_t stride, Partial *__restrict__ out) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nq) return;
-    Partial c;
-    c.num = 0;
-    c.den = 0;
-    c.rot = 0;
-    c.pad = 0;
-    c.idx = ~0ull;
+    Partial c = partial_none();
     for (uint32_t s = 0; s < S; ++s) {
         const Partial p = recv[(uint64_t)s * stride + q];
         if (better(p, c)) c = p;
@@ -409,26 +367,14 @@ constexpr uint32_t kReduceChunk = 1024;  // partials per first-stage workgroup
 __global__ void __launch_bounds__(256) reduce_stage_kernel(Partial *__restrict__ partials, uint32_t n) {
     const uint64_t base = (uint64_t)blockIdx.x * kReduceChunk;
     const uint32_t m = (uint32_t)min<uint64_t>(kReduceChunk, n - base);
-    Partial c;
-    c.num = 0;
-    c.den = 0;
-    c.rot = 0;
-    c.pad = 0;
-    c.idx = ~0ull;
+    Partial c = partial_none();
     for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
         const Partial p = partials[base + i];
         if (better(p, c)) c = p;
     }
-    c = wave_best(c);
+    // block_argmin's barrier: every read of the chunk is done before its first slot is overwritten
     __shared__ Partial sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-    __syncthreads();  // every read of the chunk is done before its first slot is overwritten
-    if (threadIdx.x == 0) {
-        Partial b = sh[0];
-        for (int w = 1; w < 4; ++w)
-            if (better(sh[w], b)) b = sh[w];
-        partials[base] = b;
-    }
+    if (block_argmin(c, sh, 4, LanesOrder())) partials[base] = c;
 }
 
 // ------------------------------------------------------------------ pack / unpack / generate

@@ -24,45 +24,15 @@
 
 #include <algorithm>
 
-#include "iris_device.hpp"
+#include "iris_engines_device.hpp"
 
 namespace iris {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kTile = 32;
 constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
 
 enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2, BATCH_TOPK = 3 };
-
-__device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ uint4 load16(const uint4 *p) {
-    const u32x4 v = *(const u32x4 *)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ v16f mfma_fp4(const v8i &a, const v8i &b, const v16f &c) {
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 127, 0, 127);
-}
-
-// the A operand of a compact query word and the B operand of a mask tile dword (kMaskFragUint4,
-// kMaskTileUint4 in iris_internal.hpp): the expansions of masks_mfma_kernel
-__device__ __forceinline__ v8i mask_a(uint32_t w) {
-    return v8i{(int)(w & 0x44444444u), (int)(w & 0x22222222u), (int)(w & 0x11111111u), (int)((w >> 3) & 0x11111111u),
-               0, 0, 0, 0};
-}
-__device__ __forceinline__ v8i mask_b(uint32_t x) {
-    return v8i{(int)(x & 0x11111111u), (int)(x & 0x22222222u), (int)(x & 0x44444444u), (int)((x >> 1) & 0x44444444u),
-               0, 0, 0, 0};
-}
 
 __device__ __forceinline__ uint32_t dword_of(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
@@ -124,67 +94,6 @@ __global__ void __launch_bounds__(256, 2)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[g][t][i] = 0.f;
     };
-    // resolver epilogue of one tile (records t0 .. t0+31 of the database) for slot g: resolve_tile of
-    // masks_mfma_kernel, with the slot's slab of every share array; alignment is the slab's own
-    auto resolve_tile = [&](int g, uint64_t t0, bool tv, const v16f &den, Partial &bq) {
-        const bool full = tv && t0 >= first && t0 + 32 <= end && ((t0 - first) & 7) == 0 && ((a.aligned >> g) & 1u);
-        const uint64_t s0 = a.slab[g];
-        const uint64_t e0 = s0 + (t0 - first) * kRot;  // first share element of the tile (when full)
-        if (full) {  // wave-uniform: 124 16-B words per share array
-            typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-            for (int i = lane; i < 32 * kRot / 8; i += 64) {
-                u16x8 v = *(const u16x8 *)(a.shares[0] + e0 + 8 * i);
-                for (uint32_t p = 1; p < a.parts; ++p) v += *(const u16x8 *)(a.shares[p] + e0 + 8 * i);
-                *(u16x8 *)&lds[8 * i] = v;
-            }
-        } else {
-            for (int i = lane; i < 32 * kRot; i += 64) {
-                const uint64_t tg = t0 + (uint64_t)(i / kRot);
-                uint16_t v = 0;
-                if (tv && tg >= first && tg < end) {
-                    const uint64_t e = s0 + (tg - first) * kRot + (uint64_t)(i % kRot);
-                    for (uint32_t p = 0; p < a.parts; ++p) v = (uint16_t)(v + a.shares[p][e]);
-                }
-                lds[i] = v;
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed
-        __builtin_amdgcn_wave_barrier();
-        const int h = lane >> 5;
-        uint32_t bn, bd;
-        int br;
-        best_rotation(lane, [&](int r, uint32_t &u, uint32_t &d) {
-            const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-            d = (uint32_t)den[r] & 0xFFFFu;  // the MasksEngine output value (u16)
-            u = k < kRot ? (uint32_t)((uint16_t)(d - lds[(lane & 31) * kRot + k]) >> 1) : 0;  // src/lib.rs:104
-        }, bn, bd, br);
-        const uint64_t tg = t0 + (lane & 31);
-        const bool valid = tv && tg >= first && tg < end;
-        if constexpr (MODE == BATCH_MATCH) {
-            const bool hit[1] = {match_hit(a.match[g], valid && h == 0, bn, bd)};
-            const uint32_t hn[1] = {bn}, hd[1] = {bd};
-            const int hr[1] = {br};
-            const uint64_t hi[1] = {tg - first};
-            append_matches<1>(a.match[g], lane, hit, hn, hd, hr, hi);
-            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
-            return;
-        }
-        if constexpr (MODE == BATCH_RESOLVE)
-            if (valid && a.dist[g] && h == 0) a.dist[g][tg - first] = bd ? (double)bn / (double)bd : __builtin_inf();
-        Partial c;
-        c.num = bn;
-        c.den = valid ? bd : 0;
-        c.rot = br;
-        c.pad = 0;
-        c.idx = tg - first;
-        if constexpr (MODE == BATCH_TOPK) {  // bq: this lane's entry of the slot's list
-            topk_insert(bq, (uint32_t)a.match[g].cap, lane, c, h == 0);
-            __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
-            return;
-        }
-        if (partial_better_dev(c, bq)) bq = c;
-        __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
-    };
     if (total) {
         zero();
         // the mask tiles (HBM) are loaded two steps ahead through three register stages, the query
@@ -241,7 +150,11 @@ __global__ void __launch_bounds__(256, 2)
                                                 [&](int r) { return (uint16_t)(uint32_t)acc[g][t][r]; });
                                 __builtin_amdgcn_wave_barrier();  // the LDS rows are read before the next tile's
                             } else {
-                                resolve_tile(g, (tile0 + tw + t) * kTile, tw + t < ntiles, acc[g][t], best[g]);
+                                // slot g's slab of every share array; alignment is the slab's own
+                                const ResolveView view{a.shares, a.parts, a.slab[g], ((a.aligned >> g) & 1u) != 0, a.match[g],
+                                                       MODE == BATCH_RESOLVE ? a.dist[g] : nullptr, best[g]};
+                                resolve_tile<MODE == BATCH_MATCH, MODE == BATCH_TOPK>(view, lds, lane, (tile0 + tw + t) * kTile,
+                                                                                     tw + t < ntiles, acc[g][t], first, end);
                             }
                         }
                     }
@@ -280,19 +193,14 @@ __global__ void __launch_bounds__(256, 2)
         __shared__ Partial sh_best[G][kWaveSlots];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const Partial o = partial_shfl_xor(best[g], off);
-                if (partial_better_dev(o, best[g])) best[g] = o;
-            }
+            best[g] = wave_argmin(best[g]);
             if (lane == 0) sh_best[g][threadIdx.x >> 6] = best[g];
         }
         __syncthreads();
         if (threadIdx.x < G && (int)threadIdx.x < a.valid) {
             const int g = threadIdx.x;
-            Partial b = sh_best[g][0];
-            for (int w = 1; w < kWaveSlots; ++w)
-                if (partial_better_dev(sh_best[g][w], b)) b = sh_best[g][w];
+            Partial b;
+            fold_waves(b, sh_best[g], kWaveSlots);
             Partial *dst = a.partials[0];
 #pragma unroll
             for (int i = 1; i < G; ++i)
@@ -305,8 +213,8 @@ __global__ void __launch_bounds__(256, 2)
 namespace {
 
 // Tiles per wave, G x T = 8 (128 accumulators): 2 for four queries, 4 for two, or 1 where that
-// would leave fewer waves than the chip holds at two workgroups per CU (the rule of the
-// single-query kernels' tiles_per_wave); IRIS_TILES_PER_WAVE pins either for tests.  Measured on
+// would leave fewer waves than the chip holds at two workgroups per CU (tiles_per_wave,
+// iris_device.hpp); IRIS_TILES_PER_WAVE pins either for tests.  Measured on
 // one box, interleaved, 10M masks: two queries 3.60 ms at 4 tiles against 3.83 at 2 (resolve
 // form 4.17 against 4.42); the resolve form of four queries 7.40 ms at 2 tiles against 8.65 at 1.
 // VGPRs (no scratch in any instantiation): rows form 98 / 242 for two queries at 1 / 4 tiles,
@@ -316,12 +224,6 @@ namespace {
 // profiles/r14_masks_batch_topk.txt), so this mode takes the resolve form's choice unchanged.
 template <int G>
 constexpr int batch_big_tiles() { return G == 2 ? 4 : 2; }
-constexpr uint64_t kMasksBatchSplitTiles = 1024;  // = kMasksSplitTiles (iris_engines_mfma.hip)
-
-int batch_tiles_per_wave(const Hooks &h, uint64_t ntiles, int big) {
-    if (h.tiles_per_wave) return h.tiles_per_wave == 1 ? 1 : big;
-    return ntiles / big < (uint64_t)resident_blocks(2) * kWaveSlots ? 1 : big;
-}
 
 struct BatchTiles {
     uint64_t tile0, ntiles;
@@ -333,9 +235,9 @@ struct BatchTiles {
 // walks more than one tile group
 BatchTiles batch_tiles(const Hooks &h, LaunchRange r, int big) {
     BatchTiles t;
-    t.tile0 = r.first / kTile;
-    t.ntiles = (r.first + r.n + kTile - 1) / kTile - t.tile0;
-    t.tpw = batch_tiles_per_wave(h, t.ntiles, big);
+    t.tile0 = tile_span(r).tile0;
+    t.ntiles = tile_span(r).ntiles;
+    t.tpw = tiles_per_wave(h, t.ntiles, big);
     const uint64_t waves = (t.ntiles + t.tpw - 1) / t.tpw;
     t.grid = (uint32_t)std::min<uint64_t>((waves + kWaveSlots - 1) / kWaveSlots, resident_blocks(2));
     return t;
@@ -395,8 +297,7 @@ int launch_mode(int mode, const Hooks &h, void *stream, const void *db, const vo
 // query through the K-split and fused resolve kernels: no K-split batch form is shipped.
 bool masks_batch_runs(const Hooks &h, LaunchRange r) {
     if (r.n == 0) return false;
-    const uint64_t ntiles = (r.first + r.n + kTile - 1) / kTile - r.first / kTile;
-    return ntiles > kMasksBatchSplitTiles || h.tiles_per_wave != 0;  // the hook pins the batch kernel for tests
+    return tile_span(r).ntiles > kMasksSplitTiles || h.tiles_per_wave != 0;  // the hook pins the batch kernel for tests
 }
 
 // the most partials per query a pass over r writes (the grid at one tile per wave)

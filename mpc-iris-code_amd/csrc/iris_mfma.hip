@@ -29,10 +29,6 @@
 
 namespace iris {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int kTileRecs = 32;
 constexpr int kTileUint4 = kPlaneGroups * 64;  // 6400 uint4 = 102400 B per tile
 constexpr int kMfmaTiles = 4;    // tiles per wave (128 templates)
 constexpr int kMfmaWgs = 2;      // workgroups per CU the register budget allows
@@ -40,11 +36,6 @@ constexpr int kSplitStages = 6;  // load ring depth of the K-split (small-range)
 // tiles per workgroup of the K-split form: every query-fragment load (2 per chunk pair and
 // wave, from L2) feeds this many tiles -- at 1 the query stream is twice the template stream
 constexpr int kSplitT = 2;
-
-__device__ __forceinline__ v16f mfma_fp4(const v8i &a, const v8i &b, const v16f &c) {
-    // cbsz = blgp = 4: both operands e2m1; scales 127 = 2^0 (e8m0)
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 127, 0, 127);
-}
 
 // Query-side den operand from the enc operand: |enc| as fp4 1.0, doubled to
 // 2.0 in the dwords whose template-side value is 0.5 (fragment dwords 1, 3).
@@ -67,12 +58,6 @@ __device__ __forceinline__ void chunk_step(uint32_t x0, uint32_t x1, const QFrag
                     (int)((x1 << 1) & 0xAAAAAAAAu), 0, 0, 0, 0};
     den = mfma_fp4(q.am, bm, den);
     s = mfma_fp4(q.ae, be, s);
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 stream_load(const uint4 *p) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
 }
 
 // MF_MATCH: every record of the range whose best rotation's f64 distance is below ms.threshold
@@ -134,7 +119,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         auto load = [&](Stage &st, int g) {
             g = (g < kG ? g : kG - 1) + g0;
 #pragma unroll
-            for (int t = 0; t < T; ++t) st.d[t] = stream_load(dp[t] + g * 64);
+            for (int t = 0; t < T; ++t) st.d[t] = nt_load16(dp[t] + g * 64);
             st.q0 = qp[(2 * g) * 64];
             st.q1 = qp[(2 * g + 1) * 64];
             // keep this stage's loads together and ahead of the compute that
@@ -234,7 +219,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     }
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        const uint64_t t0 = (tile0 + twe + t) * kTileRecs;  // global index of the tile's first template
+        const uint64_t t0 = (tile0 + twe + t) * kTile;  // global index of the tile's first template
         const bool tv = active && (twe + t < ntiles) && slice == 0;
         if constexpr (MODE == MF_COUNTS) {
             __shared__ __attribute__((aligned(16))) uint16_t sh_out[W][1024];
@@ -274,12 +259,7 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                 continue;
             }
             if (valid && dist_out && h == 0) dist_out[o] = bd ? (double)bn / (double)bd : __builtin_inf();
-            Partial c;
-            c.num = bn;
-            c.den = valid ? bd : 0;
-            c.rot = br;
-            c.pad = 0;
-            c.idx = o;
+            const Partial c = partial_of(bn, valid ? bd : 0, br, o);
             if (partial_better_dev(c, best)) best = c;
         }
     }
@@ -294,33 +274,16 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     if constexpr (MODE == MF_TOPK) {
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            Partial c;
-            c.num = hn[t];
-            c.den = hd[t];
-            c.rot = hr[t];
-            c.pad = 0;
-            c.idx = (tile0 + twe + t) * kTileRecs + (lane & 31) - first;
-            topk_insert(best, (uint32_t)ms.cap, lane, c, true);
+            topk_insert(best, (uint32_t)ms.cap, lane,
+                        partial_of(hn[t], hd[t], hr[t], (tile0 + twe + t) * kTile + (lane & 31) - first), true);
         }
         if (slice == 0) topk_store(ms, wave_e, lane, best);
     }
     if constexpr (MODE == MF_SEARCH) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const Partial ot = partial_shfl_xor(best, off);
-            if (partial_better_dev(ot, best)) best = ot;
-        }
         __shared__ Partial sh[W];
-        if (lane == 0) sh[wslot] = best;
-        __syncthreads();
-        Partial b = sh[0];
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int w = 1; w < W; ++w)
-                if (partial_better_dev(sh[w], b)) b = sh[w];
-            if constexpr (!FUSED) partials[blockIdx.x] = b;
-        }
-        if constexpr (FUSED) fold_partials_last(partials, b, fin);
+        const bool folded = block_argmin(best, sh, W);  // thread 0: the workgroup's winner
+        if constexpr (FUSED) fold_partials_last(partials, best, fin);
+        else if (folded) partials[blockIdx.x] = best;
     }
 }
 
@@ -371,7 +334,7 @@ __global__ void __launch_bounds__(256, 2)
         auto load = [&](Stage &st, int g) {
             g = g < kPlaneGroups ? g : kPlaneGroups - 1;
 #pragma unroll
-            for (int t = 0; t < T; ++t) st.d[t] = stream_load(dp[t] + g * 64);
+            for (int t = 0; t < T; ++t) st.d[t] = nt_load16(dp[t] + g * 64);
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) {
                 st.q[qi][0] = qf.q[qi][(2 * g) * 64 + lane];
@@ -411,7 +374,7 @@ __global__ void __launch_bounds__(256, 2)
     for (int qi = 0; qi < NQ; ++qi) best[qi] = partial_none();
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+        const uint64_t tg = (tile0 + tw + t) * kTile + (lane & 31);
         const bool valid = active && (tw + t < ntiles) && tg >= first && tg < end;
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
@@ -421,32 +384,21 @@ __global__ void __launch_bounds__(256, 2)
                 dd = (uint32_t)den[qi][t][r];
                 nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);
             }, bn, bd, br);
-            Partial c;
-            c.num = bn;
-            c.den = valid ? bd : 0;
-            c.rot = br;
-            c.pad = 0;
-            c.idx = tg - first;
+            const Partial c = partial_of(bn, valid ? bd : 0, br, tg - first);
             if (partial_better_dev(c, best[qi])) best[qi] = c;
         }
     }
     __shared__ Partial sh[NQ][kWaveSlots];
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const Partial ot = partial_shfl_xor(best[qi], off);
-            if (partial_better_dev(ot, best[qi])) best[qi] = ot;
-        }
+        best[qi] = wave_argmin(best[qi]);
         if (lane == 0) sh[qi][wslot] = best[qi];
     }
     __syncthreads();
     if (threadIdx.x < NQ) {
         const int qi = threadIdx.x;
-        Partial b = sh[qi][0];
-#pragma unroll
-        for (int w = 1; w < kWaveSlots; ++w)
-            if (partial_better_dev(sh[qi][w], b)) b = sh[qi][w];
+        Partial b;
+        fold_waves(b, sh[qi], kWaveSlots);
         partials[(uint64_t)qi * gridDim.x + blockIdx.x] = b;
     }
 }
@@ -473,7 +425,7 @@ __device__ __forceinline__ void round_candidates(const v16f (&den)[NQ][T], const
                                                  Partial (&best)[NQ]) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+        const uint64_t tg = (tile0 + tw + t) * kTile + (lane & 31);
         const bool valid = (tw + t < ntiles) && tg >= first && tg < end;
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
@@ -483,12 +435,7 @@ __device__ __forceinline__ void round_candidates(const v16f (&den)[NQ][T], const
                 dd = (uint32_t)den[qi][t][r];
                 nn = (uint32_t)(((int)dd - (int)s[qi][t][r]) >> 1);  // num = (den - S) / 2
             }, bn, bd, br);
-            Partial c;
-            c.num = bn;
-            c.den = valid ? bd : 0;
-            c.rot = br;
-            c.pad = 0;
-            c.idx = tg - first;
+            const Partial c = partial_of(bn, valid ? bd : 0, br, tg - first);
             if (partial_better_dev(c, best[qi])) best[qi] = c;
         }
     }
@@ -517,7 +464,7 @@ __device__ __forceinline__ void round_matches(const v16f (&den)[NQ][T], const v1
         uint64_t hi[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+            const uint64_t tg = (tile0 + tw + t) * kTile + (lane & 31);
             const bool valid = (tw + t < ntiles) && tg >= first && tg < end;
             best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
                 dd = (uint32_t)den[qi][t][r];
@@ -548,7 +495,7 @@ __device__ __forceinline__ void round_topk(const v16f (&den)[NQ][T], const v16f 
         int hr[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            const uint64_t tg = (tile0 + tw + t) * kTileRecs + (lane & 31);
+            const uint64_t tg = (tile0 + tw + t) * kTile + (lane & 31);
             const bool valid = (tw + t < ntiles) && tg >= first && tg < end;
             best_rotation(lane, [&](int r, uint32_t &nn, uint32_t &dd) {
                 dd = (uint32_t)den[qi][t][r];
@@ -558,13 +505,8 @@ __device__ __forceinline__ void round_topk(const v16f (&den)[NQ][T], const v16f 
         }
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            Partial c;
-            c.num = hn[t];
-            c.den = hd[t];
-            c.rot = hr[t];
-            c.pad = 0;
-            c.idx = (tile0 + tw + t) * kTileRecs + (lane & 31) - first;
-            topk_insert(list[qi], k[qi], lane, c, true);
+            topk_insert(list[qi], k[qi], lane,
+                        partial_of(hn[t], hd[t], hr[t], (tile0 + tw + t) * kTile + (lane & 31) - first), true);
         }
     }
 }
@@ -598,7 +540,7 @@ __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const 
         auto load = [&](Stage &st, int g) {
             g = g < kPlaneGroups ? g : kPlaneGroups - 1;
 #pragma unroll
-            for (int t = 0; t < T; ++t) st.d[t] = stream_load(dp[t] + g * 64);
+            for (int t = 0; t < T; ++t) st.d[t] = nt_load16(dp[t] + g * 64);
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) {
                 st.q[qi][0] = frag_load(qf[qi] + (2 * g) * 64 + lane);
@@ -687,7 +629,7 @@ __device__ __forceinline__ void staged_round(const uint4 *__restrict__ db, const
     auto load = [&](Stage &st, int g) {
         g = g < kPlaneGroups ? g : kPlaneGroups - 1;
 #pragma unroll
-        for (int t = 0; t < T; ++t) st.d[t] = stream_load(dp[t] + g * 64);
+        for (int t = 0; t < T; ++t) st.d[t] = nt_load16(dp[t] + g * 64);
         st.f = frag_load(fp + (2 * g) * 64);
         __builtin_amdgcn_sched_barrier(0);  // as in template_mfma_kernel: the stage's loads stay together
     };
@@ -743,11 +685,7 @@ template <int NQ, int N>
 __device__ __forceinline__ void share_stash(Partial (&best)[NQ], int lane, int pos, Partial *sh) {
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const Partial ot = partial_shfl_xor(best[qi], off);
-            if (partial_better_dev(ot, best[qi])) best[qi] = ot;
-        }
+        best[qi] = wave_argmin(best[qi]);
         if (lane == 0) sh[qi * N + pos] = best[qi];
     }
 }
@@ -759,10 +697,8 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
     __syncthreads();
     if (threadIdx.x < NQ) {
         const int qi = threadIdx.x;
-        Partial b = sh[qi * N];
-#pragma unroll
-        for (int w = 1; w < N; ++w)
-            if (partial_better_dev(sh[qi * N + w], b)) b = sh[qi * N + w];
+        Partial b;
+        fold_waves(b, sh + qi * N, N);
         const GlobalPartial o = out[qi] + blockIdx.x;
         o->num = b.num;
         o->den = b.den;
@@ -1003,7 +939,7 @@ __global__ void __launch_bounds__(256) pack_tiles_kernel(const uint32_t *__restr
         v.y = xpack(em0 >> 16, ep0 >> 16);
         v.z = xpack(em1 & 0xFFFFu, ep1 & 0xFFFFu);
         v.w = xpack(em1 >> 16, ep1 >> 16);
-        db[(t / kTileRecs) * (uint64_t)kTileUint4 + (uint64_t)g * 64 + (t % kTileRecs) + 32 * h] = v;
+        db[(t / kTile) * (uint64_t)kTileUint4 + (uint64_t)g * 64 + (t % kTile) + 32 * h] = v;
     }
 }
 
@@ -1015,7 +951,7 @@ __global__ void __launch_bounds__(256) unpack_tiles_kernel(const uint4 *__restri
         const uint64_t i = tid % n, gh = tid / n;
         const int g = (int)(gh >> 1), h = (int)(gh & 1);
         const uint64_t t = t_first + i;
-        const uint4 v = db[(t / kTileRecs) * (uint64_t)kTileUint4 + (uint64_t)g * 64 + (t % kTileRecs) + 32 * h];
+        const uint4 v = db[(t / kTile) * (uint64_t)kTileUint4 + (uint64_t)g * 64 + (t % kTile) + 32 * h];
         uint32_t a, b, c, d;
         xunpack(v.x, a, b);
         xunpack(v.y, c, d);
@@ -1049,7 +985,7 @@ __global__ void __launch_bounds__(256) generate_tiles_kernel(uint4 *__restrict__
         v.y = xpack(em0 >> 16, ep0 >> 16);
         v.z = xpack(em1 & 0xFFFFu, ep1 & 0xFFFFu);
         v.w = xpack(em1 >> 16, ep1 >> 16);
-        db[(t / kTileRecs) * (uint64_t)kTileUint4 + (uint64_t)g * 64 + (t % kTileRecs) + 32 * h] = v;
+        db[(t / kTile) * (uint64_t)kTileUint4 + (uint64_t)g * 64 + (t % kTile) + 32 * h] = v;
     }
 }
 
@@ -1072,9 +1008,8 @@ constexpr uint64_t kSplitTiles = 1024;
 // measured slower), 4 tiles on small ranges, kSplitT under the K-split.
 static TileRange tile_range(const Hooks &h, LaunchRange r) {
     TileRange t;
-    t.tile0 = r.first / kTileRecs;
-    const uint64_t tile1 = (r.first + r.n + kTileRecs - 1) / kTileRecs;
-    t.ntiles = tile1 - t.tile0;
+    t.tile0 = tile_span(r).tile0;
+    t.ntiles = tile_span(r).ntiles;
     t.tiles_per_wave = t.ntiles < kSmallTiles ? 1 : kMfmaTiles;
     t.ksplit = t.ntiles <= kSplitTiles ? 4 : 1;
     // test hook: IRIS_TILES_PER_WAVE=1|4 pins the variant (tests run all three on small ranges:
@@ -1202,8 +1137,7 @@ int launch_share_delay(void *stream, uint64_t ticks) {
 }
 
 uint32_t multi_search_partials(LaunchRange r, int nq) {
-    const uint64_t tile0 = r.first / kTileRecs, tile1 = (r.first + r.n + kTileRecs - 1) / kTileRecs;
-    const uint64_t waves = (tile1 - tile0 + (4 / nq) - 1) / (4 / nq);
+    const uint64_t waves = (tile_span(r).ntiles + (4 / nq) - 1) / (4 / nq);
     return (uint32_t)((waves + kWaveSlots - 1) / kWaveSlots);
 }
 
@@ -1212,11 +1146,11 @@ int launch_template_multi_search(void *stream, const void *db, const void *const
     *n_partials = multi_search_partials(r, nq);
     if (r.n == 0) return 0;
     if (nq != 2) return -1;
-    const uint64_t tile0 = r.first / kTileRecs, tile1 = (r.first + r.n + kTileRecs - 1) / kTileRecs;
+    const TileSpan t = tile_span(r);
     QueryFrags qf{};
     for (int i = 0; i < nq; ++i) qf.q[i] = (const uint4 *)qfrags[i];
     hipLaunchKernelGGL(template_multi_kernel<2>, dim3(*n_partials), dim3(256), 0, (hipStream_t)stream,
-                       (const uint4 *)db, qf, tile0, tile1 - tile0, r.first, r.first + r.n, partials);
+                       (const uint4 *)db, qf, t.tile0, t.ntiles, r.first, r.first + r.n, partials);
     return check_launch();
 }
 

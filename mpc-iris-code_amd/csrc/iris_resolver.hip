@@ -25,8 +25,6 @@ struct ResolverArgs {
     uint32_t parts;
 };
 
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 // One wave's 64 rows of a [n][31] u16 array as 16-B words: 64 rows = 3968 B =
 // 248 words, 16-B aligned when the array is (row0 is a multiple of 64).  Word
 // i of the wave's block -> lane i % 64, slot i / 64 (4 slots).  Words past the
@@ -65,12 +63,7 @@ __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uin
     const uint64_t e0 = row0 * kRot, ne = rows * kRot;
     bool aligned = ((uintptr_t)denoms & 15) == 0;
     for (uint32_t p = 0; p < a.parts; ++p) aligned &= ((uintptr_t)a.shares[p] & 15) == 0;
-    Partial c;
-    c.num = 0;
-    c.den = 0;
-    c.rot = 0;
-    c.pad = 0;
-    c.idx = row0 + lane;
+    Partial c = partial_of(0, 0, 0, row0 + lane);
     // wrapping sum of the shares (src/main.rs:603-607) in packed u16 lanes, all loads issued up front
     u16x8 num[kSlots], den[kSlots];
 #pragma unroll
@@ -124,19 +117,7 @@ __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uin
         topk_store(ms, (uint64_t)blockIdx.x * kWaveSlots + ws, lane, entry);
         return;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const Partial o = partial_shfl_xor(c, off);
-        if (partial_better_dev(o, c)) c = o;
-    }
-    if (lane == 0) sh_best[ws] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Partial b = sh_best[0];
-        for (int w = 1; w < kWaveSlots; ++w)
-            if (partial_better_dev(sh_best[w], b)) b = sh_best[w];
-        partials[blockIdx.x] = b;
-    }
+    if (block_argmin(c, sh_best, kWaveSlots)) partials[blockIdx.x] = c;
 }
 
 uint32_t resolver_partials(uint64_t n) {

@@ -16,39 +16,15 @@
 // each wave then reads its A-fragments with ds_read_b128 (2 per 3 T MFMAs).
 #include <hip/hip_runtime.h>
 
-#include "iris_device.hpp"
+#include "iris_engines_device.hpp"
 
 namespace iris {
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kTile = 32;
 constexpr int kStepChunks = 2;                                  // K-chunks per pipeline step
 constexpr int kSteps = kShareChunks / kStepChunks;              // 200
 constexpr int kStepUint4 = kStepChunks * 2 * 64;                // one query's fragments of a step (4 KB)
-
-__device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4 *)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// 16-B copies through a vector type (a uint4 struct copy between address spaces is a memcpy that
-// keeps its register copy in scratch memory)
-__device__ __forceinline__ uint4 load16(const uint4 *p) {
-    const u32x4 v = *(const u32x4 *)p;
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void store16(uint4 *p, const uint4 &v) { *(u32x4 *)p = u32x4{v.x, v.y, v.z, v.w}; }
-
-__device__ __forceinline__ v16i mfma_i8(const uint4 &a, const uint4 &b, const v16i &c) {
-    const v4i av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w};
-    const v4i bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w};
-    return __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, c, 0, 0, 0);
-}
 
 // The G queries of one launch: fragments (kShareFragUint4 uint4, then the 32 int2 row sums) and
 // the query's output slab ([n][31] u16).  Slots valid .. G-1 repeat slot 0's fragments and are
@@ -59,27 +35,6 @@ struct BatchQueries {
     uint16_t *out[G];
     int valid;
 };
-
-// One tile's epilogue for one query: today's single-query epilogue (shares_mfma_kernel).
-__device__ __forceinline__ void store_query_tile(uint16_t *out, uint16_t *lds, const int2 *qsum, const v16i &s1,
-                                                 const v16i &s2, uint64_t tile_t0, uint64_t first, uint64_t end,
-                                                 bool tile_valid, int lane) {
-    // row 31 (lane t + 32, register 15) holds sum e'_lo in S1 and sum e'_hi + sum e'_lo in S2
-    const int h = lane >> 5;
-    const int src = (lane & 31) + 32;
-    const int elo = __shfl(s1[15], src);
-    const int ehi = __shfl(s2[15], src) - elo;
-    store_tile_rows(out, lds, tile_t0, first, end, tile_valid, lane, [&](int r) {
-        const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int2 qs = qsum[k < kRot ? k : 0];  // (sum q'_lo, sum q'_hi) of row k
-        // the 16384 * K terms vanish mod 2^16 (K = 12800)
-        const uint32_t lo = (uint32_t)s1[r] + 128u * (uint32_t)elo + 128u * (uint32_t)qs.x;
-        const uint32_t cross = (uint32_t)s2[r] + 128u * (uint32_t)ehi + 128u * (uint32_t)qs.x +
-                               128u * (uint32_t)elo + 128u * (uint32_t)qs.y;
-        return (uint16_t)(lo + 256u * cross);
-    });
-    __builtin_amdgcn_wave_barrier();  // the LDS rows are read before the next query overwrites them
-}
 
 }  // namespace
 
@@ -214,9 +169,11 @@ __global__ void __launch_bounds__(256, 2)
         if (g >= qs.valid) break;  // wave-uniform
         const int2 *qsum = (const int2 *)(qs.frag[g] + kShareFragUint4);
 #pragma unroll
-        for (int t = 0; t < T; ++t)
+        for (int t = 0; t < T; ++t) {
             store_query_tile(qs.out[g], lds, qsum, s1[g][t], s2[g][t], (tile0 + tw + t) * kTile, first, end,
                              tw + t < ntiles, lane);
+            __builtin_amdgcn_wave_barrier();  // the LDS rows are read before the next query overwrites them
+        }
     }
 }
 
@@ -290,31 +247,18 @@ __global__ void __launch_bounds__(64 * KS, 2)
     for (int u = 0; u < kSt - 1; ++u)
         if (s + u < kSliceSteps) compute(st[u], s + u);
 
-    __shared__ int red[KS - 1][G][2][16][64];
+    __shared__ SliceSums<KS, G> red;
     __shared__ __attribute__((aligned(16))) uint16_t sh_out[1024];
-    if (slice != 0) {
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                red[slice - 1][g][0][i][lane] = s1[g][i];
-                red[slice - 1][g][1][i][lane] = s2[g][i];
-            }
-    }
+    if (slice != 0) slice_put<KS, G>(red, slice, lane, s1, s2);
     __syncthreads();
     if (slice != 0) return;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         if (g >= qs.valid) break;  // wave-uniform
-#pragma unroll
-        for (int k = 0; k < KS - 1; ++k)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                s1[g][i] += red[k][g][0][i][lane];
-                s2[g][i] += red[k][g][1][i][lane];
-            }
+        slice_add<KS, G>(red, g, lane, s1[g], s2[g]);
         store_query_tile(qs.out[g], sh_out, (const int2 *)(qs.frag[g] + kShareFragUint4), s1[g], s2[g], tile * kTile,
                          first, end, true, lane);
+        __builtin_amdgcn_wave_barrier();  // the LDS rows are read before the next query overwrites them
     }
 }
 
@@ -322,13 +266,12 @@ __global__ void __launch_bounds__(64 * KS, 2)
 constexpr int kBatchG = 4;
 constexpr int kBatchT = 1;
 constexpr int kBatchSplitKS = 2;
-// Up to this many tiles (131 072 shares) a range runs in the K-split form -- the single-query kernels'
-// threshold (kSharesSplitTiles): the large form starts one workgroup per 4 T = 4 tiles, at most two
+// Up to kSharesSplitTiles tiles (131 072 shares) a range runs in the K-split form, as a single query's
+// does: the large form starts one workgroup per 4 T = 4 tiles, at most two
 // rounds of its 2 workgroups per CU below it.  (T = 2 at one wave per SIMD, 256 accumulators in
 // AGPRs: the register allocator spilled ~315 VGPRs with 150 unused, so T = 1.)
 // IRIS_TILES_PER_WAVE (a test hook) pins the large form on ranges of any size, as it pins the
 // single-query and masks kernels' variants: T is 1, so both of its values select the same kernel.
-constexpr uint64_t kSharesBatchSplitTiles = 4096;
 
 // nq queries (qfrags[q]: a DistanceEngine's fragments) over [r.first, r.first + r.n) of a TILES share
 // database; query q's rows go to out + q * r.n * 31.  Large ranges: groups of kBatchG queries per
@@ -344,10 +287,9 @@ int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void
     if (sig) sig->armed = false;
     if (forms) *forms = SharesBatchForms{};
     if (r.n == 0 || nq == 0) return 0;
-    const uint64_t t0 = r.first / kTile;
-    const uint64_t ntiles = (r.first + r.n + kTile - 1) / kTile - t0;
+    const uint64_t t0 = tile_span(r).tile0, ntiles = tile_span(r).ntiles;
     const uint64_t slab = r.n * (uint64_t)kRot;
-    const bool split = ntiles <= kSharesBatchSplitTiles && !h.tiles_per_wave;  // the hook pins the large form for tests
+    const bool split = ntiles <= kSharesSplitTiles && !h.tiles_per_wave;  // the hook pins the large form for tests
     for (uint32_t q0 = 0; q0 < nq;) {
         const uint32_t m = nq - q0 < (uint32_t)kBatchG ? nq - q0 : (uint32_t)kBatchG;
         if (m == 1 || (split && m < (uint32_t)kBatchG)) {

@@ -4,7 +4,9 @@
 // escaped rows, every alignment of the caller's array) against a scalar restatement, and the
 // helper pool's parallel_copy under concurrent callers (parts claimed by whoever is free), and
 // copy_nt (non-temporal stores from dst's first 64-B boundary) at every source / destination offset,
-// and sum_u16 / parallel_sum_u16 (the resolver's wrapping share sums) against a scalar sum.
+// and sum_u16 / parallel_sum_u16 (the resolver's wrapping share sums) against a scalar sum, and
+// tile_span (the tiles of a TILES database that a record range touches: every launcher's grid and
+// first tile) against the formula written out.
 // These are library internals, declared here as the library defines them (iris_internal.hpp).
 #include <atomic>
 #include <cstdio>
@@ -20,6 +22,13 @@ void expand_packed_rows(uint16_t *out, const uint8_t *pk, const uint16_t *esc, s
 void copy_nt(char *dst, const char *src, size_t n);
 void sum_u16(uint16_t *dst, const uint16_t *const *src, int k, size_t n);
 void parallel_sum_u16(uint16_t *dst, const uint16_t *const *src, int k, size_t n, int lane);
+struct LaunchRange {
+    uint64_t first, n;
+};
+struct TileSpan {
+    uint64_t tile0, ntiles;
+};
+TileSpan tile_span(LaunchRange r);
 }  // namespace iris
 
 static int failures = 0;
@@ -149,6 +158,22 @@ int main() {
             });
         for (auto &t : ts) t.join();
         CHECK(bad.load() == 0);
+    }
+    // tile_span: first tile and tile count of [first, first + n), at tile boundaries, inside a tile and
+    // for a range that starts and ends past 2^32 records
+    for (uint64_t base : {0ull, 1ull << 32, (1ull << 40) + 32})
+        for (uint64_t first : {0, 5, 31, 32})
+            for (uint64_t n : {1, 27, 32, 33}) {
+                const uint64_t f = base + first;
+                const iris::TileSpan t = iris::tile_span(iris::LaunchRange{f, n});
+                CHECK(t.tile0 == f / 32);
+                CHECK(t.ntiles == (f + n + 31) / 32 - f / 32);
+                CHECK(t.tile0 * 32 <= f && f < t.tile0 * 32 + 32);                      // the first record's tile
+                CHECK((t.tile0 + t.ntiles) * 32 >= f + n && (t.tile0 + t.ntiles - 1) * 32 < f + n);  // the last record's
+            }
+    {
+        const iris::TileSpan t = iris::tile_span(iris::LaunchRange{(1ull << 32) - 7, 40});  // ends past 2^32
+        CHECK(t.tile0 == (1ull << 27) - 1 && t.ntiles == 3);
     }
     std::printf("host paths: %d failures\n", failures);
     return failures ? 1 : 0;

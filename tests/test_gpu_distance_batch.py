@@ -24,7 +24,7 @@ from test_distance_batch_abi import build_cpp_program
 pytestmark = pytest.mark.gpu
 ROT = 31
 E_ARG, E_RANGE = -1, -5
-SPLIT_TILES = 4096  # kSharesBatchSplitTiles
+SPLIT_TILES = 4096  # kSharesSplitTiles
 BIG_N = SPLIT_TILES * 32 + 27
 FILL = 0x5A5A
 
@@ -220,6 +220,23 @@ def test_device_form_writes_its_rows_only(ctx, queries, want257, first, n):
     assert (rows == want257[:nq, first:first + n]).all()
     assert (before == FILL).all(), "words before the output"
     assert (after == FILL).all(), "words after the output"
+
+
+# The single-query kernels share their K-loop and epilogue with each other and the epilogue with the
+# batch kernels: each of their forms on the tile span, the clamp of the last tile and both store paths.
+@pytest.mark.parametrize("tpw", [None, 1, 4], ids=["split", "one-tile", "two-tiles"])
+def test_single_query_forms_at_the_range_edges(device, hooked_device, queries, want257, tpw):
+    """shares_split_kernel (no hook on a small range), shares_mfma_kernel<1> (IRIS_TILES_PER_WAVE=1) and
+    shares_mfma_kernel<2> (=4: the big variant is two tiles per wave) over one record inside a tile, a
+    range across two tile boundaries, whole aligned tiles and an aligned start with a ragged end (9
+    tiles: the last wave's second tile is past the range)."""
+    dev = device if tpw is None else hooked_device(IRIS_TILES_PER_WAVE=tpw)
+    with _db257(dev, ih.LAYOUT_TILES) as db, ih.DistanceEngine(dev, queries[0]) as eng:
+        for first, n in [(5, 1), (31, 34), (64, 64), (8, 240), (0, 257)]:
+            out = np.full((n, ROT), 0xABCD, np.uint16)
+            eng.batch_process(out, db, first=first, n=n)
+            assert (out == want257[0, first:first + n]).all(), (first, n)
+            assert (_device_rows(dev, eng, db, first, n) == want257[0, first:first + n]).all(), (first, n)
 
 
 # ---------------------------------------------------------------- 3. byte-bias extremes

@@ -22,7 +22,7 @@ from test_masks_batch_abi import build_cpp_program
 pytestmark = pytest.mark.gpu
 ROT = 31
 E_ARG, E_RANGE = -1, -5
-SPLIT_TILES = 1024  # kMasksBatchSplitTiles
+SPLIT_TILES = 1024  # kMasksSplitTiles
 NONE = 2**64 - 1
 # Persistent grid of the batch kernel: min(ceil(ceil(ntiles / T) / 4), 2 x CUs) workgroups of 4 waves, T = 2
 # tiles per wave for passes of 3 or 4 queries (nq = 5 and 7 run no pass of 2).  On 256 CUs that
