@@ -76,6 +76,34 @@ pub fn resolver_topk(
     })
 }
 
+/// The distance distribution of the resolver's aggregation over device arrays of n * 31 u16
+/// (iris_resolver_histogram; no reference counterpart) -> (bins, invalid): a row is counted in bin
+/// min(nbins - 1, floor(distance * nbins)), one without a valid rotation in `invalid` alone.
+/// `nbins` is a power of two up to `ffi::IRIS_HIST_MAX_BINS`; histograms of chunks add.
+pub fn resolver_histogram(
+    dev: &Device,
+    shares_device: &[*const u16],
+    denoms_device: *const u16,
+    n: u64,
+    nbins: u32,
+) -> Result<(Vec<u64>, u64)> {
+    let mut bins = vec![0u64; nbins.clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize];
+    let mut invalid = 0u64;
+    check(unsafe {
+        ffi::iris_resolver_histogram(
+            dev.raw(),
+            shares_device.as_ptr(),
+            shares_device.len() as u32,
+            denoms_device,
+            n,
+            nbins,
+            bins.as_mut_ptr(),
+            &mut invalid,
+        )
+    })?;
+    Ok((bins, invalid))
+}
+
 /// An engine handle plus the device it lives on (kept alive by the clone).
 struct Handle {
     raw: *mut ffi::IrisEngine,
@@ -283,6 +311,27 @@ impl MasksEngine {
         })
     }
 
+    /// The distance distribution of that step (iris_resolver_histogram_masks; no reference
+    /// counterpart) -> (bins, invalid); `nbins` is a power of two up to `ffi::IRIS_HIST_MAX_BINS`.
+    pub fn histogram(&self, masks: &Database, first: u64, n: u64, shares_device: &[*const u16], nbins: u32) -> Result<(Vec<u64>, u64)> {
+        let mut bins = vec![0u64; nbins.clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize];
+        let mut invalid = 0u64;
+        check(unsafe {
+            ffi::iris_resolver_histogram_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                nbins,
+                bins.as_mut_ptr(),
+                &mut invalid,
+            )
+        })?;
+        Ok((bins, invalid))
+    }
+
     /// The same step with the participants' replies still in host memory (`shares[p]` holds the
     /// n = `shares[p].len()` rows of records [first, first + n)): the library sums the parts on
     /// the host and uploads only the sum (iris_resolver_search_masks_host).
@@ -457,6 +506,36 @@ impl MasksBatchEngine {
             .enumerate()
             .map(|(q, &c)| buf[q * room..q * room + c as usize].iter().map(match_to_pair).collect())
             .collect())
+    }
+
+    /// Every query's distance histogram of that step in one pass over the masks
+    /// (iris_resolver_batch_histogram_masks): entry q is what `MasksEngine::histogram` gives for
+    /// query q on slab q of every part.
+    pub fn batch_histogram(
+        &self,
+        masks: &Database,
+        first: u64,
+        n: u64,
+        shares_device: &[*const u16],
+        nbins: u32,
+    ) -> Result<Vec<(Vec<u64>, u64)>> {
+        let room = nbins.clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize;
+        let mut flat = vec![0u64; self.nq * room];
+        let mut invalid = vec![0u64; self.nq];
+        check(unsafe {
+            ffi::iris_resolver_batch_histogram_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                nbins,
+                flat.as_mut_ptr(),
+                invalid.as_mut_ptr(),
+            )
+        })?;
+        Ok((0..self.nq).map(|q| (flat[q * room..(q + 1) * room].to_vec(), invalid[q])).collect())
     }
 }
 

@@ -422,6 +422,40 @@ extern "C" {
         bins: *mut u64,
         invalid: *mut u64,
     ) -> c_int;
+    // resolver histograms: the same distribution from the participants' share rows (a distance can
+    // exceed 1 on garbage shares: the last bin takes it)
+    pub fn iris_resolver_histogram(
+        dev: *mut IrisDevice,
+        shares_device: *const *const u16,
+        parts: u32,
+        denoms_device: *const u16,
+        n: u64,
+        nbins: u32,
+        bins: *mut u64,
+        invalid: *mut u64,
+    ) -> c_int;
+    pub fn iris_resolver_histogram_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        nbins: u32,
+        bins: *mut u64,
+        invalid: *mut u64,
+    ) -> c_int;
+    pub fn iris_resolver_batch_histogram_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        nbins: u32,
+        bins: *mut u64,
+        invalid: *mut u64,
+    ) -> c_int;
     // threshold matching: every record below a distance (no reference counterpart for the threshold)
     pub fn iris_template_matches(
         engine: *mut IrisEngine,

@@ -726,8 +726,7 @@ int iris_pending_topk_wait(iris_pending_t *pending /* an iris_pending_topk_t */,
  * queries need a TILES database).  The bytes copied back per call are 8 (nbins + 1) per query,
  * whatever n is.
  *
- * Out of scope: the resolver forms and the masks batch form (the natural follow-up, from the
- * resolver's decode); the pipelined and device-group forms (histograms add: a caller sums its
+ * Out of scope: the pipelined and device-group forms (histograms add: a caller sums its
  * shards); host-array forms; bin counts that are not a power of two and caller-given edges;
  * weighted counts; more than 1024 bins (the batched kernel keeps four queries' histograms in LDS
  * beside its 128-KiB fragment ring: 16 KiB at 1024 bins fit the CU's 160 KiB, 64 KiB at 4096 do
@@ -744,6 +743,49 @@ int iris_template_histogram(iris_engine_t *engine, const iris_db_t *db, uint64_t
  * pass each.  The call waits once. */
 int iris_template_batch_histogram(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                                   uint32_t nbins, uint64_t *bins /* [nq][nbins] */, uint64_t *invalid /* [nq] */);
+
+/* ----------------------------------------------------- resolver histograms
+ * The same distribution where the MPC deployment first has distances: at the resolver, after the
+ * participants' [u16; 31] share rows are summed and decoded against the masks denominators
+ * (src/main.rs:597-621, src/lib.rs:97-107).  Three calls, siblings of the three resolver search
+ * calls with exactly their inputs; there is no index_base, no dist_out and no threshold, because a
+ * histogram has no indices.  The contract is the histograms' above, restated for the resolver's
+ * value range:
+ *
+ * A record is counted in bin min(nbins - 1, floor(distance * nbins)) of the f64 distance the
+ * sibling search / matches call reports for it: the best rotation of uneq / den, in exact fraction
+ * order, lowest rotation on ties.  A record whose 31 denominators are all zero is counted in
+ * *invalid alone: sum(bins) + *invalid == n, always.  Garbage shares are not an error: uneq can be
+ * up to 32767 and, in iris_resolver_histogram, den up to 65535, so a distance can exceed 1; such a
+ * record falls in the last bin, by the same min.  The device bins in integers,
+ * min(nbins - 1, num * nbins / den) with num * nbins <= 32767 * 1024 < 2^25 in u32, which equals
+ * the f64 rule for every den in 1..65535.
+ *
+ * nbins: a power of two in 1..IRIS_HIST_MAX_BINS.  The prefix sum of j < nbins bins equals the
+ * total the sibling *_matches* call reports for threshold = (double)j / nbins, cap = 0; the sum of
+ * all bins is its total at +inf.  bins and invalid are OVERWRITTEN, never accumulated; n == 0
+ * writes zeros; a refused call leaves both untouched; identical calls return identical bytes.
+ * The value arguments (nbins, NULL outputs, parts 1..8) are checked before the handles; the other
+ * checks and the locking are the sibling search's.
+ *
+ * Out of scope: host-array forms (*_host); pipelined and device-group forms; the distance batch
+ * engine; other bin counts or caller-given edges; more than 1024 bins. */
+/* iris_resolver_search's sibling: denominators given */
+int iris_resolver_histogram(iris_device_t *dev, const uint16_t *const *shares_device, uint32_t parts,
+                            const uint16_t *denoms_device, uint64_t n,
+                            uint32_t nbins, uint64_t *bins /* [nbins] */, uint64_t *invalid);
+/* iris_resolver_search_masks' sibling: the denominators computed on the fly from the masks
+ * database (TILES: one fused pass; LANES: the masks kernel into a workspace, then the resolver's) */
+int iris_resolver_histogram_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                  const uint16_t *const *shares_device, uint32_t parts,
+                                  uint32_t nbins, uint64_t *bins /* [nbins] */, uint64_t *invalid);
+/* iris_resolver_batch_search_masks' sibling, for a masks batch engine (nq = 1..64) and query-major
+ * share arrays: one histogram per query, up to 4 queries a masks pass.  Row q and invalid[q] are
+ * byte for byte what iris_resolver_histogram_masks returns for MasksEngine(qmasks[q]) on slab q.
+ * The call waits once. */
+int iris_resolver_batch_histogram_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                        const uint16_t *const *shares_device, uint32_t parts,
+                                        uint32_t nbins, uint64_t *bins /* [nq][nbins] */, uint64_t *invalid /* [nq] */);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

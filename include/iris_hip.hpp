@@ -575,6 +575,17 @@ public:
                                             index_base, k, out, count);
         });
     }
+    // The distance distribution of that resolver step in one masks pass (iris_resolver_histogram_masks;
+    // no reference counterpart): nbins is a power of two up to IRIS_HIST_MAX_BINS; a distance above 1
+    // (garbage shares) joins the last bin.  Histograms of chunks add.
+    Histogram histogram(const Database &db, const std::vector<const uint16_t *> &shares_device, uint32_t nbins,
+                        uint64_t first, uint64_t n) const {
+        Histogram res;
+        res.bins.assign(nbins && nbins <= IRIS_HIST_MAX_BINS ? nbins : 1, 0);
+        check(iris_resolver_histogram_masks(h_, db.handle(), first, n, shares_device.data(), (uint32_t)shares_device.size(),
+                                            nbins, res.bins.data(), &res.invalid));
+        return res;
+    }
     // The same with the participants' outputs in host memory (the rows as they arrive): summed on
     // the host, the sum uploaded (iris_resolver_search_masks_host).
     Match resolve_host(const Database &db, const std::vector<const std::vector<Rotations> *> &shares, uint64_t first,
@@ -660,6 +671,22 @@ public:
                                              (uint32_t)shares_device.size(), index_base, k, flat.data(), counts.data()));
         std::vector<std::vector<Match>> res(nq_);
         for (uint32_t q = 0; q < nq_; ++q) res[q].assign(flat.begin() + (size_t)q * room, flat.begin() + (size_t)q * room + counts[q]);
+        return res;
+    }
+    // Every query's distance histogram of that step, up to 4 queries a masks pass
+    // (iris_resolver_batch_histogram_masks): result[q] is what MasksEngine(queries[q]).histogram gives
+    // on slab q of every part.
+    std::vector<Histogram> histogram(const Database &db, const std::vector<const uint16_t *> &shares_device,
+                                     uint32_t nbins, uint64_t first, uint64_t n) const {
+        const uint32_t room = nbins && nbins <= IRIS_HIST_MAX_BINS ? nbins : 1;
+        std::vector<uint64_t> flat((size_t)nq_ * room), invalid(nq_);
+        check(iris_resolver_batch_histogram_masks(h_, db.handle(), first, n, shares_device.data(),
+                                                  (uint32_t)shares_device.size(), nbins, flat.data(), invalid.data()));
+        std::vector<Histogram> res(nq_);
+        for (uint32_t q = 0; q < nq_; ++q) {
+            res[q].bins.assign(flat.begin() + (size_t)q * room, flat.begin() + (size_t)(q + 1) * room);
+            res[q].invalid = invalid[q];
+        }
         return res;
     }
 
@@ -960,6 +987,16 @@ inline std::vector<Match> resolver_topk(Device &dev, const std::vector<const uin
         return iris_resolver_topk(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
                                   index_base, k, out, count);
     });
+}
+// Device-array form of the resolver's histogram (iris_resolver_histogram): the distance distribution
+// of the n rows; nbins is a power of two up to IRIS_HIST_MAX_BINS.
+inline Histogram resolver_histogram(Device &dev, const std::vector<const uint16_t *> &shares_device,
+                                    const uint16_t *denoms_device, uint64_t n, uint32_t nbins) {
+    Histogram res;
+    res.bins.assign(nbins && nbins <= IRIS_HIST_MAX_BINS ? nbins : 1, 0);
+    check(iris_resolver_histogram(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
+                                  nbins, res.bins.data(), &res.invalid));
+    return res;
 }
 // Merges top-k lists that carry global indices (shards, chunks, GPUs) into the k best, best first
 // (iris_topk_merge; host only).

@@ -1,7 +1,8 @@
 // iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
 // and batched, with the runners that turn launch units into match lists, the pipelined forms of
 // the single-query template match and top-k (their handles live by iris_pending.hpp; here is only
-// what a match or a top-k handle adds), and the distance histograms of the template engines.
+// what a match or a top-k handle adds), and the distance histograms of the template engines and of
+// the resolver forms.
 // Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
@@ -36,7 +37,7 @@ static int launch_template_select(iris_device *d, const iris_db *db, const void 
     });
 }
 
-// The single-query masks form of a match or a top-k pass, on masks engine c and the shares of its
+// The single-query masks form of a match, a top-k or a histogram pass, on masks engine c and the shares of its
 // query: a TILES database runs the fused masks_mfma_kernel; LANES the masks kernel into the
 // workspace (the denominators) and then the resolver kernel.  *den: the denominators once they are
 // enqueued -- a caller that launches again (the rerun of an overflowing list) while the workspace
@@ -45,7 +46,8 @@ static int masks_single_launch(iris_device *d, const iris_engine *c, const iris_
                                const uint16_t *const *shares, uint32_t parts, Pass p, const MatchSink &sink,
                                const uint16_t **den) {
     const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
-    const char *name = pass_name(p, tiles ? "masks_match" : "resolver_match", tiles ? "masks_topk" : "resolver_topk");
+    const char *name = pass_name(p, tiles ? "masks_match" : "resolver_match", tiles ? "masks_topk" : "resolver_topk",
+                                 tiles ? "masks_resolve_hist" : "resolver_hist");
     if (!name) return fail(IRIS_E_ARG, "no masks pass of that mode");
     if (tiles)
         return timed(d, name, r.n, [&] {
@@ -815,16 +817,16 @@ static int hist_empty(uint32_t nq, uint32_t nbins, uint64_t *bins, uint64_t *inv
     return 0;
 }
 
-// One histogram call of nq single-query passes over n records (iris_template_histogram: nq = 1; a
-// batch engine of up to kBatchStreamMax queries).  Query q has `copies` copies of its nbins + 1
-// counters in the device's counter buffer, all zeroed on the stream first; its pass -- launch(q,
-// sink), "template_hist" -- adds every workgroup's LDS histogram to copy
-// blockIdx.x % copies, "hist_reduce" sums the copies straight into the pinned host result, and the
-// call waits once.  copies = 1 (the IRIS_HIST_COPIES=1 test hook): the passes add into the result
-// itself and a copy brings it back (DESIGN.md 4.17 has both measured).  A histogram always fits, so
-// there is no second pass.
-static int hist_run(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, uint64_t *invalid, uint32_t nq,
-                    const std::function<int(uint32_t, const MatchSink &)> &launch) {
+// One histogram call of nq queries over n records each (iris_template_histogram: nq = 1; a batch
+// engine of up to kBatchStreamMax queries; the resolver forms).  Query q has `copies` copies of its
+// nbins + 1 counters in the device's counter buffer, all zeroed on the stream first; enqueue(sinks)
+// launches every pass of the call, sinks[q] being query q's -- a pass ("template_hist", ...) adds every
+// workgroup's LDS histogram to copy blockIdx.x % copies -- "hist_reduce" sums the copies of all
+// queries straight into the pinned host result, and the call waits once.  copies = 1 (the
+// IRIS_HIST_COPIES=1 test hook): the passes add into the result itself and a copy brings it back
+// (DESIGN.md 4.17 and 4.18 have both measured).  A histogram always fits, so there is no second pass.
+static int hist_run_all(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, uint64_t *invalid, uint32_t nq,
+                        const std::function<int(const MatchSink *)> &enqueue) {
     if (n == 0) return hist_empty(nq, nbins, bins, invalid);
     const uint32_t words = nbins + 1, copies = d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
     const size_t row = (size_t)copies * words;
@@ -832,7 +834,9 @@ static int hist_run(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, 
     CHK(ensure_host_result(d, (size_t)nq * words * sizeof(uint64_t)));
     uint64_t *cnt = (uint64_t *)d->match_count.p;
     HIPCHK(hipMemsetAsync(cnt, 0, nq * row * sizeof(uint64_t), d->stream));
-    for (uint32_t q = 0; q < nq; ++q) CHK(launch(q, hist_sink(cnt + q * row, nbins, copies)));
+    std::vector<MatchSink> sinks(nq);
+    for (uint32_t q = 0; q < nq; ++q) sinks[q] = hist_sink(cnt + q * row, nbins, copies);
+    CHK(enqueue(sinks.data()));
     if (copies > 1)
         CHK(timed(d, "hist_reduce", nq * row, [&] {
             return launch_hist_reduce(d->stream, cnt, words, copies, nq, (uint64_t *)d->host_result);
@@ -841,6 +845,15 @@ static int hist_run(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, 
         HIPCHK(hipMemcpyAsync(d->host_result, cnt, (size_t)nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
     CHK(sync(d));
     return hist_finish(d, n, nbins, nq, bins, invalid);
+}
+
+// hist_run_all of one single-query pass per query: launch(q, sink) enqueues query q's
+static int hist_run(iris_device *d, uint64_t n, uint32_t nbins, uint64_t *bins, uint64_t *invalid, uint32_t nq,
+                    const std::function<int(uint32_t, const MatchSink &)> &launch) {
+    return hist_run_all(d, n, nbins, bins, invalid, nq, [&](const MatchSink *sinks) {
+        for (uint32_t q = 0; q < nq; ++q) CHK(launch(q, sinks[q]));
+        return 0;
+    });
 }
 
 // iris_template_search's histogram sibling (header: "histograms")
@@ -893,6 +906,81 @@ int iris_template_batch_histogram(iris_engine_t *e, const iris_db_t *db, uint64_
     HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
     CHK(sync(d));
     return hist_finish(d, n, nbins, nq, bins, invalid);
+}
+
+// iris_resolver_search's histogram sibling (header: "resolver histograms"): resolver_kernel's
+// histogram mode ("resolver_hist"), one workgroup per 256 rows, through hist_run's counter copies.
+int iris_resolver_histogram(iris_device_t *d, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms,
+                            uint64_t n, uint32_t nbins, uint64_t *bins, uint64_t *invalid) {
+    IRIS_KEEP_DEVICE();
+    CHK(hist_args(nbins, bins, invalid));  // the value arguments first: refused whatever the handles
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(d, "NULL argument");
+    CHK(share_args(shares, parts, n, denoms != nullptr));
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    return hist_run(d, n, nbins, bins, invalid, 1, [&](uint32_t, const MatchSink &hs) {
+        return timed(d, "resolver_hist", n, [&] { return launch_resolver(Pass::Hist, d->stream, shares, parts, denoms, n, hs); });
+    });
+}
+
+// iris_resolver_search_masks' histogram sibling: TILES runs the fused masks_mfma_kernel<MASKS_HIST>
+// ("masks_resolve_hist"); LANES the masks kernel into the workspace and then the resolver kernel's
+// histogram mode ("resolver_hist").
+int iris_resolver_histogram_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                  const uint16_t *const *shares_device, uint32_t parts, uint32_t nbins, uint64_t *bins,
+                                  uint64_t *invalid) {
+    IRIS_KEEP_DEVICE();
+    CHK(hist_args(nbins, bins, invalid));  // the value arguments first: refused whatever the handles
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(single_masks_args(e, db, "iris_resolver_batch_histogram_masks"));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    return hist_run(d, n, nbins, bins, invalid, 1, [&](uint32_t, const MatchSink &hs) {
+        const uint16_t *den = nullptr;
+        return masks_single_launch(d, e, db, r, shares_device, parts, Pass::Hist, hs, &den);
+    });
+}
+
+// iris_resolver_batch_search_masks' histogram sibling, with iris_resolver_batch_matches_masks'
+// dispatch: TILES ranges the batch kernel runs walk the queries in groups of kMasksBatchG, each group
+// one pass of masks_batch_kernel<BATCH_HIST> ("masks_batch_hist") into the group's sinks, a single
+// left-over query one fused single-query pass; other TILES ranges one such pass per query; LANES the
+// masks kernel into the workspace and the resolver kernel per query.  Every pass is enqueued before
+// the one hist_reduce over all nq rows and the one wait.
+int iris_resolver_batch_histogram_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                        const uint16_t *const *shares_device, uint32_t parts, uint32_t nbins,
+                                        uint64_t *bins, uint64_t *invalid) {
+    IRIS_KEEP_DEVICE();
+    CHK(hist_args(nbins, bins, invalid));  // the value arguments first: refused whatever the handles
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(masks_batch_args(e, db));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const MasksWalk w(e, db, first, n);
+    return hist_run_all(d, n, nbins, bins, invalid, e->nq, [&](const MatchSink *hs) {
+        for (MasksUnit u = w.unit(0); u.m; u = w.unit(u.q0 + u.m)) {
+            if (u.m > 1) {
+                CHK(timed(d, "masks_batch_hist", n * u.m, [&] {
+                    return launch_masks_batch(Pass::Hist, d->hooks, d->stream, db->data, u.frags, u.m, w.r,
+                                              {shares_device, parts, u.q0, hs + u.q0, MasksBatchOut::HistTag{}});
+                }));
+                continue;
+            }
+            // one query through the single-query forms, on its slab of every part
+            const uint16_t *sl[8], *den = nullptr;
+            w.slabs(u.q0, shares_device, parts, sl);
+            CHK(masks_single_launch(d, u.one, db, w.r, sl, parts, Pass::Hist, hs[u.q0], &den));
+        }
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -382,9 +382,13 @@ __device__ __forceinline__ void hist_zero(uint32_t *lds, uint32_t nbins) {
     for (uint32_t i = threadIdx.x; i <= nbins; i += blockDim.x) lds[i] = 0;
 }
 // One record per lane (`counted` lanes only; every lane of the wave calls this).  The bin is the
-// integer floor(num * nbins / den), num <= den <= 12800 and nbins <= 1024 a power of two, so the
-// product is below 2^24 and equals floor of the f64 distance times nbins (the header's rule);
-// distance 1.0 joins the last bin.  den = 0: a ballot counts the wave's invalid records, one add.
+// integer min(nbins - 1, floor(num * nbins / den)) with nbins <= 1024 a power of two.  Template
+// passes: num <= den <= 12800, the product below 2^24.  Resolver passes: num <= 32767 (a u16 >> 1)
+// and den <= 65535, the product at most 32767 * 1024 < 2^25 in u32; num > den (garbage shares, a
+// distance above 1) joins the last bin by the same min.  Either way the quotient equals floor of
+// the f64 distance times nbins (the header's rule; checked for every den in 1..65535 beside every
+// bin edge, tests/test_resolver_histogram_abi.py); distance 1.0 joins the last bin.  den = 0: a
+// ballot counts the wave's invalid records, one add.
 __device__ __forceinline__ void hist_count(uint32_t *lds, uint32_t nbins, int lane, bool counted, uint32_t num,
                                            uint32_t den) {
     if (counted && den != 0) {

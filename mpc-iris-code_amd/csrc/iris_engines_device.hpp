@@ -16,17 +16,20 @@ struct ResolveView {
     uint32_t parts;
     uint64_t base;
     bool aligned;           // every share array is 16-B aligned at `base`
-    const MatchSink &sink;  // MATCH: the query's records, room, counter and threshold; TOPK: topk_sink
+    const MatchSink &sink;  // MATCH: the query's records, room, counter and threshold; TOPK: topk_sink; HIST: hist_sink
     double *dist;           // null, or the query's n distances
     Partial &best;          // the lane's running best; TOPK: this lane's entry of the wave's list
+    uint32_t *hist = nullptr;  // HIST: the query's LDS histogram of the workgroup (hist_sink_bins(sink) + 1 words)
 };
 
 // Resolver epilogue of one tile (records t0 .. t0+31 of the database), `den` its denominators in the
 // MFMA C layout and lds the wave's 2 KB: the tile's summed shares are staged in LDS, each lane decodes
 // its 16 (record, rotation) cells (decode_distance, src/lib.rs:97-107) and half 0 of the wave
 // takes the record's best to the running best, or (MATCH) appends it to the sink if it lies below
-// the threshold, or (TOPK) inserts it into the wave's list.
-template <bool MATCH, bool TOPK>
+// the threshold, or (TOPK) inserts it into the wave's list, or (HIST) counts it in v.hist
+// (hist_count: no running best, no dist, no append; the caller zeroes and flushes v.hist around
+// its walk, behind workgroup barriers).
+template <bool MATCH, bool TOPK, bool HIST = false>
 __device__ __forceinline__ void resolve_tile(const ResolveView &v, uint16_t *lds, int lane, uint64_t t0, bool tv,
                                              const v16f &den, uint64_t first, uint64_t end) {
     const bool full = tv && t0 >= first && t0 + 32 <= end && ((t0 - first) & 7) == 0 && v.aligned;
@@ -61,6 +64,11 @@ __device__ __forceinline__ void resolve_tile(const ResolveView &v, uint16_t *lds
     }, bn, bd, br);
     const uint64_t tg = t0 + (lane & 31);
     const bool valid = tv && tg >= first && tg < end;
+    if constexpr (HIST) {  // half 0 counts: both halves hold the record's best
+        hist_count(v.hist, hist_sink_bins(v.sink), lane, valid && h == 0, bn, bd);
+        __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+        return;
+    }
     if constexpr (MATCH) {
         const bool hit[1] = {match_hit(v.sink, valid && h == 0, bn, bd)};
         const uint32_t hn[1] = {bn}, hd[1] = {bd};

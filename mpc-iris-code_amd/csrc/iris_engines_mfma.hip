@@ -28,8 +28,8 @@ namespace iris {
 // costs registers: 5.1 vs 2.7 ms)
 constexpr int kMasksTiles = 7;
 constexpr int kResolveTiles = 4;
-// MASKS_RESOLVE (1), MASKS_MATCH (3) and MASKS_TOPK (4) share the resolver step's shape
-constexpr bool masks_resolving(int mode) { return mode == 1 || mode == 3 || mode == 4; }
+// MASKS_RESOLVE (1), MASKS_MATCH (3), MASKS_TOPK (4) and MASKS_HIST (5) share the resolver step's shape
+constexpr bool masks_resolving(int mode) { return mode == 1 || mode == 3 || mode == 4 || mode == 5; }
 template <int MODE>
 constexpr int masks_tiles() { return !masks_resolving(MODE) ? kMasksTiles : kResolveTiles; }
 constexpr int kMasksBlocksPerCu = 2;  // persistent grid: workgroups per CU
@@ -71,7 +71,12 @@ struct MaskResolve {
 // rs.match.threshold are appended to rs.match (iris_resolver_matches_masks)
 // MASKS_TOPK: MASKS_RESOLVE's staging and decode; the running best becomes the wave's top-k list
 // (topk_insert), stored at rs.match.buf[wave] (rs.match = topk_sink; iris_resolver_topk_masks)
-enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3, MASKS_TOPK = 4 };
+// MASKS_HIST: MASKS_RESOLVE's staging and decode; in place of the running best, every record of the
+// range is counted in the workgroup's LDS histogram (rs.match = hist_sink; hist_count), zeroed ahead
+// of a barrier before the walk and added once, behind a barrier after it, to the workgroup's copy of
+// the counters (iris_resolver_histogram_masks).  Both barriers stand outside `if (total)`: waves
+// without a tile group reach them too, as they reach block_argmin's in the search.
+enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3, MASKS_TOPK = 4, MASKS_HIST = 5 };
 
 // Persistent: each wave walks the tile groups wave, wave + nwaves, ... as one
 // flat stream of (group, step) K-steps, so the loads of the next group are in
@@ -115,7 +120,13 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
     };
-    const ResolveView view{rs.shares, rs.parts, 0, rs.aligned, rs.match, rs.dist_out, best};
+    uint32_t *hist = nullptr;
+    if constexpr (MODE == MASKS_HIST) {
+        hist = hist_lds<1>();
+        hist_zero(hist, hist_sink_bins(rs.match));
+        __syncthreads();
+    }
+    const ResolveView view{rs.shares, rs.parts, 0, rs.aligned, rs.match, rs.dist_out, best, hist};
     if (total) {
         zero();
         struct Stage {
@@ -156,8 +167,8 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
                         store_tile_packed((uint8_t *)out, out + (end - first) * 16, (tile0 + tw + t) * kTile, first, end,
                                           tw + t < ntiles, lane, [&](int r) { return (uint32_t)acc[t][r]; });
                     else
-                        resolve_tile<MODE == MASKS_MATCH, MODE == MASKS_TOPK>(view, lds, lane, (tile0 + tw + t) * kTile,
-                                                                             tw + t < ntiles, acc[t], first, end);
+                        resolve_tile<MODE == MASKS_MATCH, MODE == MASKS_TOPK, MODE == MASKS_HIST>(
+                            view, lds, lane, (tile0 + tw + t) * kTile, tw + t < ntiles, acc[t], first, end);
                 }
                 zero();
             }
@@ -176,6 +187,10 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
         }
     }
     if constexpr (MODE == MASKS_TOPK) topk_store(rs.match, wave, lane, best);  // every wave of the grid: one list
+    if constexpr (MODE == MASKS_HIST) {  // every wave of the workgroup: the counts are in before the flush reads them
+        __syncthreads();
+        hist_flush(hist, hist_sink_bins(rs.match), hist_sink_copy(rs.match));
+    }
     if constexpr (MODE == MASKS_RESOLVE) {
         __shared__ Partial sh_best[kWaveSlots];
         if (block_argmin(best, sh_best, kWaveSlots)) rs.partials[blockIdx.x] = best;
@@ -312,6 +327,9 @@ int launch_masks_resolve(Pass p, const Hooks &h, void *stream, const void *db, c
     case Pass::Search: return masks_resolve_pass<MASKS_RESOLVE>(h, stream, db, qfrag, r, shares, parts, o);
     case Pass::Match: return masks_resolve_pass<MASKS_MATCH>(h, stream, db, qfrag, r, shares, parts, o);
     case Pass::Topk: return masks_resolve_pass<MASKS_TOPK>(h, stream, db, qfrag, r, shares, parts, o);
+    case Pass::Hist:
+        if (r.n != 0 && !hist_sink_ok(o.sink)) return -1;
+        return masks_resolve_pass<MASKS_HIST>(h, stream, db, qfrag, r, shares, parts, o);
     default: return -1;
     }
 }

@@ -168,13 +168,18 @@ inline MatchSink topk_sink(Partial *lists, uint32_t k) { return MatchSink{lists,
 // A histogram pass (iris_*_histogram) takes it as well: count = counters[copies][nbins + 1], u64,
 // zeroed on the stream before the launch, and cap = nbins | (copies - 1) << 32 (both powers of two);
 // buf and threshold are unused.  A workgroup bins its records in LDS (bin = min(nbins - 1,
-// num * nbins / den) of the best rotation, integers: num * nbins < 2^24) and adds its non-zero
+// num * nbins / den) of the best rotation, integers: num * nbins < 2^25, hist_count) and adds its non-zero
 // words to copy blockIdx.x % copies: words 0 .. nbins - 1 the bins, word nbins the records without
 // a valid rotation.  copies = 1 is the result itself; launch_hist_reduce sums more.
 constexpr uint32_t kHistMaxBins = IRIS_HIST_MAX_BINS;
 constexpr uint32_t kHistCopies = 64;  // the flush and its measurement
 inline MatchSink hist_sink(uint64_t *counters, uint32_t nbins, uint32_t copies) {
     return MatchSink{nullptr, (uint64_t)nbins | (uint64_t)(copies - 1) << 32, counters, 0.0};
+}
+// whether s is a hist_sink the kernels' LDS histograms hold: counters, nbins a power of two up to kHistMaxBins
+inline bool hist_sink_ok(const MatchSink &s) {
+    const uint32_t nbins = (uint32_t)s.cap;
+    return s.count && nbins >= 1 && nbins <= kHistMaxBins && (nbins & (nbins - 1)) == 0;
 }
 
 // ---------------------------------------------------------------- generator
@@ -436,7 +441,7 @@ int launch_shares_batch(const Hooks &h, void *stream, const void *db, const void
 
 // -- the fused resolver step, TILES (masks_mfma_kernel's resolving modes, iris_engines_mfma.hip): the
 // masks pass whose rows are the denominators of shares[0..parts) (1..8 device arrays of r.n rows,
-// summed), decoded in place of being stored.  Search, Match or Topk; every mode runs the same grid,
+// summed), decoded in place of being stored.  Search, Match, Topk or Hist; every mode runs the same grid,
 // masks_resolve_partials(h, r) workgroups at one or four tiles per wave; an empty range launches nothing.
 uint32_t masks_resolve_partials(const Hooks &h, LaunchRange r);  // partials a search writes
 uint64_t masks_topk_units(const Hooks &h, LaunchRange r);        // lists a top-k pass writes
@@ -444,7 +449,7 @@ int launch_masks_resolve(Pass p, const Hooks &h, void *stream, const void *db, c
                          const uint16_t *const *shares, uint32_t parts, const PassOut &o);
 
 // -- the resolver, denominators given (resolver_kernel, iris_resolver.hip): rows i < n of shares[0..parts)
-// (1..8) summed and decoded against denoms.  Search, Match or Topk; one workgroup per 256 rows in
+// (1..8) summed and decoded against denoms.  Search, Match, Topk or Hist; one workgroup per 256 rows in
 // every mode; n == 0 launches nothing.
 uint32_t resolver_partials(uint64_t n);    // partials a search writes
 uint64_t resolver_topk_units(uint64_t n);  // lists a top-k pass writes
@@ -508,12 +513,17 @@ struct MasksBatchOut {
     Partial *lists = nullptr;         // Topk: every wave stores its k best of query s at lists + s * stride
     uint64_t stride = 0;              //   + wave * k (masks_batch_topk_units lists per query); k 1..kTopkMax
     uint32_t k = 0;
+    const MatchSink *hists = nullptr; // Hist: hists[s] is query s's hist_sink (counters zeroed on the stream by the caller),
+                                      //   every query's the same nbins and copies
+    struct HistTag {};
     MasksBatchOut(uint16_t *out) : rows(out) {}
     MasksBatchOut(const MasksBatchResolve &r, uint32_t *n_partials) : resolve(true), rs(r), np(n_partials) {}
     MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, const MatchSink *match_sinks)
         : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, sinks(match_sinks) {}
     MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, Partial *l, uint64_t s, uint32_t kk)
         : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, lists(l), stride(s), k(kk) {}
+    MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, const MatchSink *hist_sinks, HistTag)
+        : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, hists(hist_sinks) {}
 };
 int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
                        LaunchRange r, const MasksBatchOut &o);

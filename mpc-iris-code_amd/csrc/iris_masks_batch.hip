@@ -32,7 +32,7 @@ namespace {
 
 constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
 
-enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2, BATCH_TOPK = 3 };
+enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2, BATCH_TOPK = 3, BATCH_HIST = 4 };
 
 __device__ __forceinline__ uint32_t dword_of(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
@@ -54,6 +54,7 @@ struct MaskBatchArgs {
     uint32_t aligned;       // bit g: slab g of every part starts 16-B aligned
     MatchSink match[G];     // BATCH_MATCH: the slot's own records, room, counter and threshold
                             // BATCH_TOPK: topk_sink -- buf = the slot's lists [gridDim.x * 4][k], cap = k
+                            // BATCH_HIST: hist_sink -- the slot's counter copies; every slot the same nbins and copies
 };
 
 }  // namespace
@@ -69,6 +70,11 @@ struct MaskBatchArgs {
 // walks its tile groups.  After the loop every wave of the grid -- one with no tile group stores
 // an empty list, launch_topk_merge reads them all -- stores each valid slot's list at
 // a.match[g].buf[wave]: no shuffle reduction, no sh_best, no partials.
+// BATCH_HIST: BATCH_RESOLVE's staging and decode; each record of a valid slot is counted in the slot's
+// LDS histogram (hist_lds<G>(), slot g at g * (kHistMaxBins + 1): 16.4 KB beside sh_out's 8 KB for
+// four slots), resident while the wave walks its tile groups.  The histograms are zeroed ahead of a
+// barrier before the walk and, behind a barrier after it, each valid slot's non-zero words are added
+// once to the workgroup's copy of a.match[g]'s counters (hist_flush).
 template <int G, int T, int MODE>
 __global__ void __launch_bounds__(256, 2)
     masks_batch_kernel(const uint4 *__restrict__ db, MaskBatchArgs<G> a, uint64_t tile0, uint64_t ntiles, uint64_t first,
@@ -78,12 +84,22 @@ __global__ void __launch_bounds__(256, 2)
     const uint64_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaveSlots + (threadIdx.x >> 6));
     const uint64_t nwaves = (uint64_t)gridDim.x * kWaveSlots;
     const uint64_t ngroups = (ntiles + T - 1) / T;
-    if (MODE != BATCH_RESOLVE && MODE != BATCH_TOPK && wave >= ngroups) return;
+    // BATCH_RESOLVE and BATCH_TOPK: every wave of the grid writes after the walk; BATCH_HIST: every
+    // wave of the workgroup reaches the two histogram barriers
+    if (MODE != BATCH_RESOLVE && MODE != BATCH_TOPK && MODE != BATCH_HIST && wave >= ngroups) return;
     const uint32_t total = wave < ngroups ? (uint32_t)((ngroups - wave + nwaves - 1) / nwaves) * kSteps : 0;
     uint16_t *lds = sh_out[threadIdx.x >> 6];
     Partial best[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) best[g] = partial_none();
+
+    uint32_t *hist = nullptr;
+    if constexpr (MODE == BATCH_HIST) {
+        hist = hist_lds<G>();
+#pragma unroll
+        for (int g = 0; g < G; ++g) hist_zero(hist + g * (kHistMaxBins + 1), hist_sink_bins(a.match[0]));
+        __syncthreads();
+    }
 
     v16f acc[G][T];
     auto zero = [&] {
@@ -152,9 +168,10 @@ __global__ void __launch_bounds__(256, 2)
                             } else {
                                 // slot g's slab of every share array; alignment is the slab's own
                                 const ResolveView view{a.shares, a.parts, a.slab[g], ((a.aligned >> g) & 1u) != 0, a.match[g],
-                                                       MODE == BATCH_RESOLVE ? a.dist[g] : nullptr, best[g]};
-                                resolve_tile<MODE == BATCH_MATCH, MODE == BATCH_TOPK>(view, lds, lane, (tile0 + tw + t) * kTile,
-                                                                                     tw + t < ntiles, acc[g][t], first, end);
+                                                       MODE == BATCH_RESOLVE ? a.dist[g] : nullptr, best[g],
+                                                       MODE == BATCH_HIST ? hist + g * (kHistMaxBins + 1) : nullptr};
+                                resolve_tile<MODE == BATCH_MATCH, MODE == BATCH_TOPK, MODE == BATCH_HIST>(
+                                    view, lds, lane, (tile0 + tw + t) * kTile, tw + t < ntiles, acc[g][t], first, end);
                             }
                         }
                     }
@@ -188,6 +205,13 @@ __global__ void __launch_bounds__(256, 2)
 #pragma unroll
         for (int g = 0; g < G; ++g)
             if (g < a.valid) topk_store(a.match[g], wave, lane, best[g]);  // every wave of the grid: one list per slot
+    }
+    if constexpr (MODE == BATCH_HIST) {  // every wave of the workgroup: the counts are in before the flush reads them
+        __syncthreads();
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (g < a.valid)
+                hist_flush(hist + g * (kHistMaxBins + 1), hist_sink_bins(a.match[g]), hist_sink_copy(a.match[g]));
     }
     if constexpr (MODE == BATCH_RESOLVE) {
         __shared__ Partial sh_best[G][kWaveSlots];
@@ -251,7 +275,7 @@ int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const 
     return check_launch();
 }
 
-template <int G>  // mode = BATCH_*: BATCH_OUT writes `out`, the others read rs, BATCH_MATCH and BATCH_TOPK fill sinks
+template <int G>  // mode = BATCH_*: BATCH_OUT writes `out`, the others read rs, BATCH_MATCH, BATCH_TOPK and BATCH_HIST fill sinks
 int launch_slots(int mode, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
                  LaunchRange r, uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks) {
     const BatchTiles t = batch_tiles(h, r, batch_big_tiles<G>());
@@ -281,6 +305,7 @@ int launch_slots(int mode, const Hooks &h, void *stream, const void *db, const v
     a.parts = rs->parts;
     for (uint32_t p = 0; p < rs->parts; ++p) a.shares[p] = rs->shares[p];
     if (mode == BATCH_TOPK) return launch_group<G, BATCH_TOPK>(stream, db, a, t, r);
+    if (mode == BATCH_HIST) return launch_group<G, BATCH_HIST>(stream, db, a, t, r);
     if (mode == BATCH_MATCH) return launch_group<G, BATCH_MATCH>(stream, db, a, t, r);
     return launch_group<G, BATCH_RESOLVE>(stream, db, a, t, r);
 }
@@ -322,15 +347,20 @@ int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, con
     MatchSink ts[kMasksBatchG];
     switch (p) {
     case Pass::Search:
-        if (o.sinks || o.lists || (!rs && !o.rows)) return -1;
+        if (o.sinks || o.lists || o.hists || (!rs && !o.rows)) return -1;
         return launch_mode(rs ? BATCH_RESOLVE : BATCH_OUT, h, stream, db, qfrags, m, r, o.rows, rs, o.np, nullptr);
     case Pass::Match:
-        if (!rs || !o.sinks) return -1;
+        if (!rs || !o.sinks || o.hists) return -1;
         return launch_mode(BATCH_MATCH, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, o.sinks);
     case Pass::Topk:
-        if (!rs || !o.lists || o.k == 0 || o.k > kTopkMax) return -1;
+        if (!rs || !o.lists || o.hists || o.k == 0 || o.k > kTopkMax) return -1;
         for (uint32_t s = 0; s < m; ++s) ts[s] = topk_sink(o.lists + s * o.stride, o.k);
         return launch_mode(BATCH_TOPK, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, ts);
+    case Pass::Hist:  // one nbins and one number of copies for all slots: the kernel zeroes by slot 0's
+        if (!rs || !o.hists || o.sinks || o.lists || o.rows) return -1;
+        for (uint32_t s = 0; s < m; ++s)
+            if (!hist_sink_ok(o.hists[s]) || o.hists[s].cap != o.hists[0].cap) return -1;
+        return launch_mode(BATCH_HIST, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, o.hists);
     default: return -1;
     }
 }

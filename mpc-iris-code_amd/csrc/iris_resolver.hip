@@ -50,7 +50,11 @@ constexpr int kSlots = (kWords + 63) / 64;         // 4
 // MATCH (iris_resolver_matches): the load and sum path is the search's; after the per-row decode
 // the rows below ms.threshold are appended to ms (idx = row) instead of the argmin.
 // TOPK (iris_resolver_topk): the wave's k best rows go to its list ms.buf[wave] (ms = topk_sink).
-template <bool MATCH = false, bool TOPK = false>
+// HIST (iris_resolver_histogram): every row is counted in the workgroup's LDS histogram (ms =
+// hist_sink), one hist_count per lane between two barriers that every wave reaches -- the kernel
+// has no exit before its epilogue -- and the workgroup adds its non-zero words to its copy once.
+// The histogram reuses the staged denominators' LDS behind one more barrier.
+template <bool MATCH = false, bool TOPK = false, bool HIST = false>
 __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uint16_t *__restrict__ denoms,
                                                        uint64_t n, double *__restrict__ dist_out,
                                                        Partial *__restrict__ partials, MatchSink ms) {
@@ -103,6 +107,19 @@ __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uin
         }
         if (dist_out) dist_out[row0 + lane] = c.den ? (double)c.num / (double)c.den : __builtin_inf();
     }
+    if constexpr (HIST) {
+        // the histogram (kHistMaxBins + 1 words) takes sh_den's place once every wave has decoded its
+        // rows: a buffer of its own would cost a workgroup per CU (36 KB against 31.9 KB of LDS)
+        static_assert(sizeof(sh_den) >= (kHistMaxBins + 1) * sizeof(uint32_t), "the histogram fits sh_den");
+        uint32_t *hist = (uint32_t *)&sh_den[0][0];
+        __syncthreads();
+        hist_zero(hist, hist_sink_bins(ms));
+        __syncthreads();
+        hist_count(hist, hist_sink_bins(ms), lane, (uint64_t)lane < rows, c.num, c.den);
+        __syncthreads();
+        hist_flush(hist, hist_sink_bins(ms), hist_sink_copy(ms));
+        return;
+    }
     if constexpr (MATCH) {
         const bool hit[1] = {match_hit(ms, (uint64_t)lane < rows, c.num, c.den)};
         const uint32_t hn[1] = {c.num}, hd[1] = {c.den};
@@ -126,7 +143,7 @@ uint32_t resolver_partials(uint64_t n) {
 
 uint64_t resolver_topk_units(uint64_t n) { return (uint64_t)resolver_partials(n) * kWaveSlots; }
 
-template <bool MATCH, bool TOPK>
+template <bool MATCH, bool TOPK, bool HIST = false>
 static int resolver_pass(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
                          const PassOut &o) {
     if (n == 0) return 0;
@@ -134,7 +151,7 @@ static int resolver_pass(void *stream, const uint16_t *const *shares, uint32_t p
     ResolverArgs a{};
     for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
     a.parts = parts;
-    hipLaunchKernelGGL((resolver_kernel<MATCH, TOPK>), dim3(resolver_partials(n)), dim3(64 * kWaveSlots), 0,
+    hipLaunchKernelGGL((resolver_kernel<MATCH, TOPK, HIST>), dim3(resolver_partials(n)), dim3(64 * kWaveSlots), 0,
                        (hipStream_t)stream, a, denoms, n, o.dist_out, o.partials, o.sink);
     return check_launch();
 }
@@ -146,6 +163,9 @@ int launch_resolver(Pass p, void *stream, const uint16_t *const *shares, uint32_
     case Pass::Search: return resolver_pass<false, false>(stream, shares, parts, denoms, n, o);
     case Pass::Match: return resolver_pass<true, false>(stream, shares, parts, denoms, n, o);
     case Pass::Topk: return resolver_pass<false, true>(stream, shares, parts, denoms, n, o);
+    case Pass::Hist:
+        if (n != 0 && !hist_sink_ok(o.sink)) return -1;
+        return resolver_pass<false, false, true>(stream, shares, parts, denoms, n, o);
     default: return -1;
     }
 }

@@ -210,6 +210,10 @@ def load_library(path=None):
                                  ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_template_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
+            "iris_resolver_histogram": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, ctypes.c_uint32, P, P],
+                                        ctypes.c_int),
+            "iris_resolver_histogram_masks": ([P, P, u64, u64, P, ctypes.c_uint32, ctypes.c_uint32, P, P], ctypes.c_int),
+            "iris_resolver_batch_histogram_masks": ([P, P, u64, u64, P, ctypes.c_uint32, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_query_table_sizes": ([ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_size_t),
                                         ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
             "iris_engine_query_tables": ([P, P, ctypes.c_size_t, P, ctypes.c_size_t], ctypes.c_int),
@@ -286,6 +290,7 @@ def exported_symbols():
         "iris_template_topk", "iris_resolver_topk", "iris_resolver_topk_masks", "iris_topk_merge",
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
         "iris_template_histogram", "iris_template_batch_histogram",
+        "iris_resolver_histogram", "iris_resolver_histogram_masks", "iris_resolver_batch_histogram_masks",
     ]
 
 
@@ -1054,6 +1059,23 @@ class MasksEngine(_Engine):
             for p in tmp:
                 dev.free(p)
 
+    def histogram(self, db, share_ptrs, nbins, first=0, n=None):
+        """The distance distribution of the resolver step in one masks pass
+        (iris_resolver_histogram_masks; no reference counterpart): share_ptrs are the participants'
+        device arrays of n*31 u16.  -> (bins: np.ndarray[nbins] of uint64, invalid: int).  A row is
+        counted in bin min(nbins - 1, floor(distance * nbins)) -- a distance above 1 (garbage shares)
+        in the last -- one without a valid rotation in `invalid` alone; nbins is a power of two up
+        to HIST_MAX_BINS.  The prefix sum of j bins is matches(j / nbins, cap=0)'s total."""
+        n = (len(db) - int(first)) if n is None else n
+        nb = int(nbins)
+        ptrs = [int(p) for p in share_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        bins = np.zeros(nb if 0 < nb <= HIST_MAX_BINS else 1, np.uint64)
+        invalid = ctypes.c_uint64(0)
+        _check(load_library().iris_resolver_histogram_masks(self.handle, db.handle, int(first), int(n), arr, len(ptrs), nb,
+                                                            _ptr(bins), ctypes.addressof(invalid)))
+        return bins, int(invalid.value)
+
 
 class DistanceEngine(_Engine):
     """DistanceEngine (src/lib.rs:28-53): out[k] = dot_u16(rot(query, k-15), entry)."""
@@ -1482,6 +1504,21 @@ class MasksBatchEngine(_Engine):
                                                              int(index_base), int(k), out, counts))
         return [[_copy_match(out[q * room + j]) for j in range(counts[q])] for q in range(self.nq)]
 
+    def histogram(self, db, shares_device_ptrs, nbins, first=0, n=None):
+        """Every query's distance histogram of that resolver step, up to 4 queries a masks pass
+        (iris_resolver_batch_histogram_masks): shares_device_ptrs as in resolve().
+        -> (np.ndarray[nq, nbins] of uint64, np.ndarray[nq] of uint64): row q and entry q are what
+        MasksEngine(masks[q]).histogram gives on slab q of every part."""
+        n = (len(db) - first) if n is None else n
+        nb = int(nbins)
+        ptrs = [int(p) for p in shares_device_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        bins = np.zeros((self.nq, nb if 0 < nb <= HIST_MAX_BINS else 1), np.uint64)
+        invalid = np.zeros(self.nq, np.uint64)
+        _check(load_library().iris_resolver_batch_histogram_masks(self.handle, db.handle, int(first), int(n), arr, len(ptrs),
+                                                                  nb, _ptr(bins), _ptr(invalid)))
+        return bins, invalid
+
 
 # ====================================================================== device groups
 
@@ -1752,6 +1789,19 @@ def resolver_topk(device, share_ptrs, denoms_ptr, n, k, index_base=0):
                                           int(index_base), int(k), o, cnt), k)
 
 
+def resolver_histogram(device, share_ptrs, denoms_ptr, n, nbins):
+    """The distance distribution of the resolver's aggregation (iris_resolver_histogram; device
+    arrays of n*31 u16) -> (bins: np.ndarray[nbins] of uint64, invalid: int); nbins is a power of
+    two up to HIST_MAX_BINS, a distance above 1 joins the last bin."""
+    ptrs = (ctypes.c_void_p * max(len(share_ptrs), 1))(*share_ptrs)
+    nb = int(nbins)
+    bins = np.zeros(nb if 0 < nb <= HIST_MAX_BINS else 1, np.uint64)
+    invalid = ctypes.c_uint64(0)
+    _check(load_library().iris_resolver_histogram(device.handle, ptrs, len(share_ptrs), ctypes.c_void_p(denoms_ptr), int(n),
+                                                  nb, _ptr(bins), ctypes.addressof(invalid)))
+    return bins, int(invalid.value)
+
+
 # ====================================================================== arch plugin
 
 
@@ -1789,7 +1839,7 @@ def f64_bits(x):
 
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
-    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "TOPK_MAX", "HIST_MAX_BINS", "dot_bool", "dot_u16",
+    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "TOPK_MAX", "HIST_MAX_BINS", "dot_bool", "dot_u16",
     "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",

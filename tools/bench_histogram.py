@@ -102,7 +102,7 @@ def table(rows, reps, note):
     out = {}
     for h, (label, dev, fn, names) in zip(host, rows):
         dms = device_ms(dev, fn, names, min(reps, 10))
-        out[label] = (float(np.median(h)) * 1e3, sum(dms.values()))
+        out[label] = (float(np.median(h)) * 1e3, sum(dms.values()), spread(h))  # host ms, device ms, host spread
         parts = ", ".join(f"{k} {v:.4f}" for k, v in dms.items())
         print(f"   {label:<10}    {out[label][0]:10.4f}      {spread(h):6.1%}   {out[label][1]:10.4f}   ({parts})")
     return out
