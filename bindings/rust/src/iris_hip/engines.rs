@@ -21,6 +21,15 @@ use std::ptr;
 use super::{check, default_device, ffi, match_to_pair, Database, Device, Record, Result, ShardedDatabase};
 use crate::{Bits, EncodedBits, Template};
 
+/// The result of `TemplateEngine::report`: the parts that were asked for, each as its sibling method
+/// returns it.
+#[derive(Clone, Debug, Default)]
+pub struct Report {
+    pub matches: Option<(Vec<(f64, usize)>, u64)>,
+    pub topk: Option<Vec<(f64, usize)>>,
+    pub histogram: Option<(Vec<u64>, u64)>,
+}
+
 /// Runs one `iris_*_matches` call: `call(out, cap, count)`.  `cap = None` returns every match (room
 /// for 1024 first, then once more with room for the reported count); `Some(0)` only counts.
 /// -> (the matches of lowest index as `(distance, index)`, ascending; the total count).
@@ -729,6 +738,58 @@ impl TemplateEngine {
             ffi::iris_template_histogram(self.h.raw, db.raw(), first, n, nbins, bins.as_mut_ptr(), &mut invalid)
         })?;
         Ok((bins, invalid))
+    }
+
+    /// Several of `matches`, `topk` and `histogram` from ONE read of [first, first + n)
+    /// (iris_template_report; no reference counterpart).  A part is selected by its argument:
+    /// `matches = Some((threshold, cap))` (the `cap` lowest indices and the exact total; 0 only
+    /// counts), `k = Some(k)`, `nbins = Some(nbins)`; at least one.  Each selected part of the result
+    /// is exactly what the sibling method returns, the others are `None`.
+    pub fn report(
+        &self,
+        db: &Database,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        matches: Option<(f64, u64)>,
+        k: Option<u32>,
+        nbins: Option<u32>,
+    ) -> Result<Report> {
+        let mut list = vec![ffi::IrisMatch::default(); matches.map_or(0, |m| m.1) as usize];
+        let mut best = vec![ffi::IrisMatch::default(); k.map_or(0, |k| k.max(1)) as usize];
+        let mut bins = vec![0u64; nbins.map_or(0, |b| b.clamp(1, ffi::IRIS_HIST_MAX_BINS)) as usize];
+        let mut r = ffi::IrisReport {
+            parts: 0,
+            k: k.unwrap_or(0),
+            nbins: nbins.unwrap_or(0),
+            topk_count: 0,
+            threshold: matches.map_or(0.0, |m| m.0),
+            matches: if list.is_empty() { ptr::null_mut() } else { list.as_mut_ptr() },
+            matches_cap: list.len() as u64,
+            matches_count: 0,
+            topk: best.as_mut_ptr(),
+            bins: bins.as_mut_ptr(),
+            invalid: 0,
+        };
+        if matches.is_some() {
+            r.parts |= ffi::IRIS_REPORT_MATCHES;
+        }
+        if k.is_some() {
+            r.parts |= ffi::IRIS_REPORT_TOPK;
+        }
+        if nbins.is_some() {
+            r.parts |= ffi::IRIS_REPORT_HIST;
+        }
+        check(unsafe {
+            ffi::iris_template_report(self.h.raw, db.raw(), first, n, index_base, &mut r as *mut ffi::IrisReport as *mut _)
+        })?;
+        list.truncate(r.matches_count.min(r.matches_cap) as usize);
+        best.truncate(r.topk_count as usize);
+        Ok(Report {
+            matches: matches.map(|_| (list.iter().map(match_to_pair).collect(), r.matches_count)),
+            topk: k.map(|_| best.iter().map(match_to_pair).collect()),
+            histogram: nbins.map(|_| (bins, r.invalid)),
+        })
     }
 
     /// Enqueues `topk` and returns at once (iris_template_topk_async): a pass still running may

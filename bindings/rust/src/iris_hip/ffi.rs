@@ -18,6 +18,10 @@ pub const IRIS_ROTATIONS: usize = 31;
 pub const IRIS_MAX_ROTATION: i32 = 15;
 pub const IRIS_TOPK_MAX: u32 = 64;
 pub const IRIS_HIST_MAX_BINS: u32 = 1024;
+/// The parts of a report call (`iris_report_t::parts`).
+pub const IRIS_REPORT_MATCHES: u32 = 1;
+pub const IRIS_REPORT_TOPK: u32 = 2;
+pub const IRIS_REPORT_HIST: u32 = 4;
 
 /// Status codes.
 pub const IRIS_OK: c_int = 0;
@@ -100,6 +104,23 @@ pub struct IrisMatch {
     pub den: u32,
     pub rotation: i32,
     pub reserved: u32,
+}
+
+/// `iris_report_t`: the arguments and results of `iris_template_report` (no implicit padding).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct IrisReport {
+    pub parts: u32,
+    pub k: u32,
+    pub nbins: u32,
+    pub topk_count: u32,
+    pub threshold: f64,
+    pub matches: *mut IrisMatch,
+    pub matches_cap: u64,
+    pub matches_count: u64,
+    pub topk: *mut IrisMatch,
+    pub bins: *mut u64,
+    pub invalid: u64,
 }
 
 extern "C" {
@@ -421,6 +442,16 @@ extern "C" {
         nbins: u32,
         bins: *mut u64,
         invalid: *mut u64,
+    ) -> c_int;
+    // combined passes: several of matches / topk / histogram of one probe from one read of the range;
+    // `report` points at an IrisReport (the header declares it void *)
+    pub fn iris_template_report(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        report: *mut c_void,
     ) -> c_int;
     // resolver histograms: the same distribution from the participants' share rows (a distance can
     // exceed 1 on garbage shares: the last bin takes it)

@@ -744,6 +744,67 @@ int iris_template_histogram(iris_engine_t *engine, const iris_db_t *db, uint64_t
 int iris_template_batch_histogram(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                                   uint32_t nbins, uint64_t *bins /* [nq][nbins] */, uint64_t *invalid /* [nq] */);
 
+/* --------------------------------------------------------- combined passes
+ * The match list, the k closest records and the distance histogram of ONE probe from ONE read of
+ * the range.  An identification service asks all three for the same probe -- the list is the
+ * decision, the neighbours go to the operator and the audit log, the histogram shows whether the
+ * scores still sit where the threshold was calibrated -- and each sibling call is a full pass over
+ * the database that is bound by reading it.  All three are functions of the one value the search's
+ * loops produce per record, its best rotation (src/template.rs:43-47 per record,
+ * src/main.rs:616-621 over records): a report pass computes it once and feeds every selected sink.
+ *
+ * report->parts selects the parts, IRIS_REPORT_* bits: at least one, no others (IRIS_E_ARG).  EACH
+ * SELECTED PART IS BYTE FOR BYTE WHAT ITS SIBLING CALL WRITES for the same engine, database,
+ * range, index_base and arguments:
+ *   MATCHES  matches[0 .. min(matches_count, matches_cap)) and matches_count are
+ *            iris_template_matches' out and *count for (threshold, cap);
+ *   TOPK     topk[0 .. topk_count) and topk_count are iris_template_topk's out and *count for k;
+ *   HIST     bins[0 .. nbins) and invalid are iris_template_histogram's for nbins.
+ * That sentence is the whole semantics: thresholds are decided on the f64 the search would report,
+ * order is the exact fraction and then the lowest index, the bin is the integer num * nbins / den,
+ * and a record without a valid rotation is in no list and counts in `invalid`.  The fields and
+ * arrays of a part that is not selected are neither read nor written.
+ *
+ * Refusals: the value arguments are checked before the handles -- parts, then each selected part's
+ * own arguments under its sibling's rules (a NaN threshold, matches NULL with a cap, k outside
+ * 1..IRIS_TOPK_MAX, topk NULL, nbins not a power of two in 1..IRIS_HIST_MAX_BINS, bins NULL) -- then
+ * the engine, the database and the range as in the siblings: a single-query template engine and a
+ * templates database of either layout; a batch engine is IRIS_E_ARG.  A refused or failed call
+ * writes nothing, the out fields of the struct included: nothing is written before every selected
+ * part has succeeded.  n == 0: the counts and the bins are zero, and nothing is launched.
+ *
+ * One part selected runs that sibling's own pass.  Two or three run one pass, followed on the
+ * stream by the top-k merge and the histogram's reduce, and the call waits once; a match list that
+ * overflows the room of the first pass runs the matches part alone once more, as
+ * iris_template_matches does (never with matches_cap == 0).
+ *
+ * Out of scope: the pipelined forms (a report pass neither hosts nor is hosted in the sharing ring);
+ * template batch and masks batch engines; the resolver forms (iris_resolver_report_masks would be
+ * the natural next: the fused masks kernel ends in the same three sinks); host-array forms and
+ * device groups; more than one threshold, k or histogram per call; a search part -- topk[0] at
+ * k = 1 is the search's result. */
+#define IRIS_REPORT_MATCHES 1
+#define IRIS_REPORT_TOPK 2
+#define IRIS_REPORT_HIST 4
+typedef struct iris_report {
+    uint32_t parts;         /* in: IRIS_REPORT_* bits, at least one, no others */
+    uint32_t k;             /* in, TOPK: 1..IRIS_TOPK_MAX */
+    uint32_t nbins;         /* in, HIST: a power of two, 1..IRIS_HIST_MAX_BINS */
+    uint32_t topk_count;    /* out, TOPK */
+    double threshold;       /* in, MATCHES: not NaN */
+    iris_match_t *matches;  /* in, MATCHES: room for matches_cap records (may be NULL when the cap is 0) */
+    uint64_t matches_cap;   /* in, MATCHES */
+    uint64_t matches_count; /* out, MATCHES: the exact total, also when it exceeds the cap */
+    iris_match_t *topk;     /* in, TOPK: room for k records */
+    uint64_t *bins;         /* in, HIST: nbins words */
+    uint64_t invalid;       /* out, HIST */
+} iris_report_t;
+/* report: the caller's iris_report_t.  It crosses as void *: the functions of this header take
+ * scalars, opaque handles and the two value structs iris_match_t and iris_template_t, the closed set
+ * every binding mirrors, and a struct of arguments is memory the caller lays out as above. */
+int iris_template_report(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                         uint64_t index_base, void *report /* iris_report_t * */);
+
 /* ----------------------------------------------------- resolver histograms
  * The same distribution where the MPC deployment first has distances: at the resolver, after the
  * participants' [u16; 31] share rows are summed and decoded against the masks denominators

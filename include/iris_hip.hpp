@@ -33,6 +33,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -63,6 +64,20 @@ constexpr uint64_t kAllMatches = UINT64_MAX;  // cap: return every match
 struct Histogram {
     std::vector<uint64_t> bins;
     uint64_t invalid = 0;
+};
+
+// What a report call asks for (iris_template_report): a part is selected by giving its argument.
+struct ReportRequest {
+    std::optional<double> threshold;  // the matches part, with cap (kAllMatches: every match)
+    uint64_t cap = kAllMatches;
+    std::optional<uint32_t> k;        // the top-k part
+    std::optional<uint32_t> nbins;    // the histogram part
+};
+// Its result: each selected part is what matches() / topk() / histogram() returns, the others are empty.
+struct Report {
+    std::optional<Matches> matches;
+    std::optional<std::vector<Match>> topk;
+    std::optional<Histogram> histogram;
 };
 
 class Error : public std::runtime_error {
@@ -812,6 +827,50 @@ public:
         Histogram res;
         res.bins.assign(nbins && nbins <= IRIS_HIST_MAX_BINS ? nbins : 1, 0);
         check(iris_template_histogram(h_, db.handle(), first, n, nbins, res.bins.data(), &res.invalid));
+        return res;
+    }
+    // Several of matches(), topk() and histogram() from ONE read of the range (iris_template_report; no
+    // reference counterpart): each part the request selects is exactly what the sibling method returns.
+    // cap = kAllMatches: room for 1024 matches in the combined pass, a longer list through matches().
+    Report report(const Database &db, const ReportRequest &req, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        iris_report_t r{};
+        Report res;
+        std::vector<Match> list, best;
+        const bool all = req.cap == kAllMatches;
+        if (req.threshold) {
+            r.parts |= IRIS_REPORT_MATCHES;
+            r.threshold = *req.threshold;
+            r.matches_cap = all ? 1024 : req.cap;
+            list.resize(r.matches_cap);
+            r.matches = r.matches_cap ? list.data() : nullptr;
+        }
+        if (req.k) {
+            r.parts |= IRIS_REPORT_TOPK;
+            r.k = *req.k;
+            best.resize(std::max<uint32_t>(*req.k, 1));
+            r.topk = best.data();
+        }
+        if (req.nbins) {
+            r.parts |= IRIS_REPORT_HIST;
+            r.nbins = *req.nbins;
+            res.histogram.emplace();
+            res.histogram->bins.assign(r.nbins && r.nbins <= IRIS_HIST_MAX_BINS ? r.nbins : 1, 0);
+            r.bins = res.histogram->bins.data();
+        }
+        check(iris_template_report(h_, db.handle(), first, n, index_base, &r));
+        if (req.threshold) {
+            if (all && r.matches_count > r.matches_cap) {
+                res.matches = matches(db, *req.threshold, first, n, index_base, r.matches_count);
+            } else {
+                list.resize(std::min<uint64_t>(r.matches_cap, r.matches_count));
+                res.matches = Matches{std::move(list), r.matches_count};
+            }
+        }
+        if (req.k) {
+            best.resize(r.topk_count);
+            res.topk = std::move(best);
+        }
+        if (req.nbins) res.histogram->invalid = r.invalid;
         return res;
     }
     // pipelined form: returns once the search is enqueued (the engine may be destroyed before the wait)

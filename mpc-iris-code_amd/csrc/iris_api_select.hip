@@ -1,8 +1,9 @@
 // iris_api_select.hip — the C ABI (include/iris_hip.h): threshold matching and top-k, single-query
 // and batched, with the runners that turn launch units into match lists, the pipelined forms of
 // the single-query template match and top-k (their handles live by iris_pending.hpp; here is only
-// what a match or a top-k handle adds), and the distance histograms of the template engines and of
-// the resolver forms.
+// what a match or a top-k handle adds), the distance histograms of the template engines and of
+// the resolver forms, and the combined pass that answers a match, a top-k and a histogram call of
+// one probe from one read (iris_template_report).
 // Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
@@ -981,6 +982,177 @@ int iris_resolver_batch_histogram_masks(iris_engine_t *e, const iris_db_t *db, u
         }
         return 0;
     });
+}
+
+// ------------------------------------------------------------------ combined passes
+
+// The pinned host result of a report call: the staged ReportSinks, the match counter, the merged
+// top-k list, the histogram row -- disjoint, each at a 64-byte boundary.
+constexpr size_t kReportCountOff = 128, kReportTopkOff = 192;
+constexpr size_t kReportHistOff = kReportTopkOff + kTopkMax * sizeof(Partial);
+static_assert(sizeof(ReportSinks) <= kReportCountOff && kReportHistOff % 64 == 0, "report result layout");
+// The device's counter buffer of a report call: the match counter, then (a line on) the histogram's copies
+constexpr size_t kReportHistWord = 8;
+
+// Two or three parts of iris_template_report over r (not empty) from ONE pass ("template_report").
+// The device's buffers are shared by region: d->matches holds the top-k lists (and the merge's spare
+// lists) and behind them the match records; d->match_count the match counter and behind it the
+// histogram's copies; the pinned result as laid out above.  The pass is followed on the stream by
+// the top-k merge, the histogram's reduce (copies = 1: a copy) and the copy of the match counter,
+// and the call waits once.  A match list that overflows its room (matches_run_units' rule: the
+// caller's cap or kMatchFirstRoom, a grown buffer in full, cap = 0 never) runs again alone, as a
+// plain match pass ("template_match") whose room is the reported count; its ensure() may replace
+// d->matches, so the top-k list and the histogram are taken off the pinned result first.  Nothing
+// reaches *rep or its arrays before every part has succeeded.
+static int report_run(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r, uint64_t index_base,
+                      iris_report_t *rep) {
+    const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
+               want_hist = rep->parts & IRIS_REPORT_HIST;
+    const uint64_t n = r.n, base = index_base + r.first, cap = want_match ? rep->matches_cap : 0;
+    const uint32_t k = want_topk ? rep->k : 0, nbins = want_hist ? rep->nbins : 0;
+    const uint64_t units = want_topk ? template_topk_lists(d, db, r) : 0;
+    const size_t lists_bytes = (units + topk_spare_lists(units)) * k * sizeof(Partial);
+    const uint32_t words = nbins + 1, copies = !want_hist ? 0 : d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
+    uint64_t room = 0;
+    if (cap) {
+        room = std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom));
+        if (d->matches.cap > lists_bytes)  // reuse_grown: what an earlier call grew, behind the lists
+            room = std::max<uint64_t>(room, std::min<uint64_t>(n, (d->matches.cap - lists_bytes) / sizeof(Partial)));
+    }
+    CHK(ensure(d, d->matches, lists_bytes + room * sizeof(Partial)));
+    CHK(ensure(d, d->match_count, (kReportHistWord + (size_t)copies * words) * sizeof(uint64_t)));
+    CHK(ensure(d, d->match_sinks, sizeof(ReportSinks)));
+    CHK(ensure_host_result(d, kReportHistOff + (size_t)kHistMaxBins * sizeof(uint64_t) + sizeof(uint64_t)));
+    Partial *lists = (Partial *)d->matches.p, *spare = lists + units * k;
+    Partial *records = (Partial *)((char *)d->matches.p + lists_bytes);
+    uint64_t *cnt = (uint64_t *)d->match_count.p, *hist = cnt + kReportHistWord;
+    char *res = (char *)d->host_result;
+    HIPCHK(hipMemsetAsync(cnt, 0, (kReportHistWord + (size_t)copies * words) * sizeof(uint64_t), d->stream));
+    // the sinks cross to the device from pinned memory, as a template batch match pass's do
+    ReportSinks *stage = (ReportSinks *)res;
+    *stage = ReportSinks{};
+    if (want_match) stage->match = MatchSink{records, room, cnt, rep->threshold};
+    if (want_topk) stage->topk = topk_sink(lists, k);
+    if (want_hist) stage->hist = hist_sink(hist, nbins, copies);
+    const ReportSinks *dsinks = (const ReportSinks *)d->match_sinks.p;
+    HIPCHK(hipMemcpyAsync((void *)dsinks, stage, sizeof(ReportSinks), hipMemcpyHostToDevice, d->stream));
+    CHK(timed(d, "template_report", n, [&] {
+        return db->k.layout == IRIS_LAYOUT_TILES
+                   ? launch_template_mfma(Pass::Report, d->hooks, d->stream, db->data, e->qfrag, r, dsinks)
+                   : launch_template(Pass::Report, d->stream, db->data, e->qtab, r, dsinks);
+    }));
+    if (want_topk)
+        CHK(timed(d, "topk_merge", units, [&] {
+            return launch_topk_merge(d->stream, lists, spare, units, k, (Partial *)(res + kReportTopkOff));
+        }));
+    if (want_hist) {
+        if (copies > 1)
+            CHK(timed(d, "hist_reduce", (uint64_t)copies * words, [&] {
+                return launch_hist_reduce(d->stream, hist, words, copies, 1, (uint64_t *)(res + kReportHistOff));
+            }));
+        else
+            HIPCHK(hipMemcpyAsync(res + kReportHistOff, hist, words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (want_match)
+        HIPCHK(hipMemcpyAsync(res + kReportCountOff, cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+    CHK(sync(d));
+    // every part's result off the pinned words: a rerun below reuses them
+    uint64_t total = 0;
+    Partial best[kTopkMax];
+    std::vector<uint64_t> row;
+    std::vector<Partial> recs;
+    if (want_match) {
+        memcpy(&total, res + kReportCountOff, sizeof(total));
+        if (total > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+    }
+    if (want_topk) memcpy(best, res + kReportTopkOff, k * sizeof(Partial));
+    const uint64_t take = std::min(total, cap);
+    try {
+        if (want_hist) row.assign((const uint64_t *)(res + kReportHistOff), (const uint64_t *)(res + kReportHistOff) + words);
+        if (take) recs.resize(total);
+    } catch (const std::bad_alloc &) {
+        return fail(IRIS_E_NOMEM, "out of host memory");
+    }
+    if (want_hist) {
+        uint64_t sum = 0;
+        for (uint32_t i = 0; i < words; ++i) sum += row[i];
+        if (sum != n) return fail(IRIS_E_HIP, "histogram pass did not count every record of the range once");
+    }
+    if (take) {
+        if (total > room) {  // the matches part alone once more, its room the reported count
+            CHK(ensure(d, d->matches, total * sizeof(Partial)));
+            records = (Partial *)d->matches.p;
+            HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint64_t), d->stream));
+            CHK(launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Match, MatchSink{records, total, cnt, rep->threshold}));
+            HIPCHK(hipMemcpyAsync(res + kReportCountOff, cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+            CHK(sync(d));
+            if (memcmp(res + kReportCountOff, &total, sizeof(total)) != 0)
+                return fail(IRIS_E_HIP, "match pass counts differ between two runs");
+        }
+        HIPCHK(hipMemcpyAsync(recs.data(), records, total * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
+        CHK(sync(d));
+    }
+    if (want_match) {
+        if (take) match_list(recs.data(), total, take, base, rep->matches);
+        rep->matches_count = total;
+    }
+    if (want_topk) rep->topk_count = topk_list(best, k, base, rep->topk);
+    if (want_hist) {
+        memcpy(rep->bins, row.data(), nbins * sizeof(uint64_t));
+        rep->invalid = row[nbins];
+    }
+    return 0;
+}
+
+// Several of iris_template_matches, iris_template_topk and iris_template_histogram for one probe from
+// one read of the range (header: "combined passes").  One part: that sibling's own pass through its
+// own runner.
+int iris_template_report(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                         void *report) {
+    IRIS_KEEP_DEVICE();
+    iris_report_t *const rep = (iris_report_t *)report;
+    ARG(rep, "report is NULL");  // the value arguments first: refused whatever the handles
+    const uint32_t all = IRIS_REPORT_MATCHES | IRIS_REPORT_TOPK | IRIS_REPORT_HIST;
+    ARG(rep->parts != 0 && (rep->parts & ~all) == 0, "parts must be one or more of IRIS_REPORT_MATCHES, _TOPK, _HIST");
+    const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
+               want_hist = rep->parts & IRIS_REPORT_HIST;
+    if (want_match) CHK(matches_args(rep->threshold, rep->matches, rep->matches_cap, &rep->matches_count));
+    if (want_topk) CHK(topk_args(rep->k, rep->topk, &rep->topk_count));
+    if (want_hist) CHK(hist_args(rep->nbins, rep->bins, &rep->invalid));
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    // one part: the sibling's pass, its count through a local -- a failed call leaves the struct as it was
+    if (rep->parts == IRIS_REPORT_MATCHES) {
+        uint64_t count = 0;
+        CHK(matches_run(d, n, index_base + first, rep->threshold, rep->matches, rep->matches_cap, &count,
+                        [&](const MatchSink &ms) { return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Match, ms); }));
+        rep->matches_count = count;
+        return 0;
+    }
+    if (rep->parts == IRIS_REPORT_TOPK) {
+        uint32_t count = 0;
+        const uint64_t units = n ? template_topk_lists(d, db, r) : 0;
+        CHK(topk_run(d, n, index_base + first, rep->k, rep->topk, &count, units, [&](const MatchSink &ts) {
+            return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Topk, ts);
+        }));
+        rep->topk_count = count;
+        return 0;
+    }
+    if (rep->parts == IRIS_REPORT_HIST)
+        return hist_run(d, n, rep->nbins, rep->bins, &rep->invalid, 1, [&](uint32_t, const MatchSink &hs) {
+            return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Hist, hs);
+        });
+    if (n == 0) {  // nothing is launched
+        if (want_match) rep->matches_count = 0;
+        if (want_topk) rep->topk_count = 0;
+        if (want_hist) CHK(hist_empty(1, rep->nbins, rep->bins, &rep->invalid));
+        return 0;
+    }
+    return report_run(d, e, db, r, index_base, rep);
 }
 
 }  // extern "C"

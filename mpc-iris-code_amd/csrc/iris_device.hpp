@@ -474,6 +474,23 @@ __device__ __forceinline__ void topk_store_lists(const Lists &m, uint64_t unit, 
     }
 }
 
+// Report passes (iris_template_report; ReportSinks, iris_internal.hpp).  The pass's MatchSink points
+// at the device struct of the three sinks: the fields the sinks' helpers read, through a pointer that
+// is global by type -- a wave-uniform address, so they are scalar loads and every "is this part
+// present" test is a scalar branch, the same for all waves of the workgroup.  Read after the K loop:
+// nothing of it is carried across.
+__device__ __forceinline__ ReportSinks report_sinks_load(const MatchSink &ms) {
+    const __attribute__((address_space(1))) ReportSinks *const p = (const __attribute__((address_space(1))) ReportSinks *)ms.buf;
+    ReportSinks r;
+    r.match = MatchSink{p->match.buf, p->match.cap, p->match.count, p->match.threshold};
+    r.topk = MatchSink{p->topk.buf, p->topk.cap, nullptr, 0.0};
+    r.hist = MatchSink{nullptr, p->hist.cap, p->hist.count, 0.0};
+    return r;
+}
+__device__ __forceinline__ bool report_has_match(const ReportSinks &r) { return r.match.count != nullptr; }
+__device__ __forceinline__ bool report_has_topk(const ReportSinks &r) { return r.topk.cap != 0; }
+__device__ __forceinline__ bool report_has_hist(const ReportSinks &r) { return r.hist.count != nullptr; }
+
 // Last-workgroup reduction (a search's partials reduce without a second launch).  Thread 0
 // publishes this workgroup's partial with agent-scope atomic stores (sc1: written through
 // past the XCD's L2, coherent across the XCDs without an L2 writeback / invalidate -- a full

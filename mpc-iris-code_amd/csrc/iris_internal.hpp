@@ -181,6 +181,14 @@ inline bool hist_sink_ok(const MatchSink &s) {
     const uint32_t nbins = (uint32_t)s.cap;
     return s.count && nbins >= 1 && nbins <= kHistMaxBins && (nbins & (nbins - 1)) == 0;
 }
+// A report pass (iris_template_report) feeds all three from one read of the database: a small DEVICE
+// struct holds the three sinks and the pass's MatchSink points at it (report_sink: buf; the other
+// fields are unused), so the kernels keep their signature and read the sinks once, after their K
+// loop.  A part the call did not select is absent: match.count null, topk.cap 0, hist.count null.
+struct ReportSinks {
+    MatchSink match, topk, hist;
+};
+inline MatchSink report_sink(const ReportSinks *device_sinks) { return MatchSink{(Partial *)device_sinks, 0, nullptr, 0.0}; }
 
 // ---------------------------------------------------------------- generator
 // Counter-based synthetic data: limb = splitmix64 output number
@@ -266,7 +274,9 @@ constexpr uint64_t kSharesSplitTiles = 4096;
 //   Match:  every record under a threshold, appended to a MatchSink
 //   Topk:   the k closest records of every unit (a wave that holds candidates), into topk_sink lists
 //   Hist:   the distribution of the distances, into hist_sink counters
-enum class Pass { Counts, Search, Match, Topk, Hist };
+//   Report: Match, Topk and Hist together -- those of them its ReportSinks hold -- from one read
+//           (the single-query template kernels only)
+enum class Pass { Counts, Search, Match, Topk, Hist, Report };
 
 // The operands of a single-query pass; what its mode does not write stays null.
 struct PassOut {
@@ -274,9 +284,11 @@ struct PassOut {
     double *dist_out = nullptr;                       // Search: null, or n distances
     Partial *partials = nullptr;                      // Search: the family's *_partials() records
     MatchSink sink{};                                 // Match, Topk, Hist: counters zeroed on the stream by the caller
+                                                      // Report: report_sink of the device struct of the three
     PassOut(uint16_t *num, uint16_t *den) : num_out(num), den_out(den) {}
     PassOut(double *dist, Partial *parts) : dist_out(dist), partials(parts) {}
     PassOut(const MatchSink &s) : sink(s) {}
+    PassOut(const ReportSinks *device_sinks) : sink(report_sink(device_sinks)) {}
     // whether the operands are the ones mode p writes (the launchers refuse a pass whose are not)
     bool fits(Pass p) const {
         const bool counts = num_out || den_out, search = partials || dist_out;

@@ -103,7 +103,9 @@ struct LanesOrder {
 // iris_template_topk)
 // MODE_HIST: every record of the range is counted in the bin of its best rotation (ms = hist_sink,
 // iris_template_histogram), in the workgroup's LDS histogram, flushed once
-enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2, MODE_TOPK = 3, MODE_HIST = 4 };
+// MODE_REPORT: those three from one read (ms = report_sink: the device's ReportSinks,
+// iris_template_report), each part the struct holds as its own mode does it
+enum { MODE_COUNTS = 0, MODE_SEARCH = 1, MODE_MATCH = 2, MODE_TOPK = 3, MODE_HIST = 4, MODE_REPORT = 5 };
 
 // Each wave: one 64-record block.  Workgroup: 4 waves.
 template <int MODE>
@@ -179,6 +181,32 @@ __global__ void __launch_bounds__(256, 5)
             hist_count(hist, hist_sink_bins(ms), lane, valid, c.num, c.den);
             __syncthreads();
             hist_flush(hist, hist_sink_bins(ms), hist_sink_copy(ms));
+            return;
+        }
+        if constexpr (MODE == MODE_REPORT) {
+            // a part's presence is workgroup-uniform, and nothing above returns: the histogram's two
+            // barriers are reached by every wave or by none
+            const ReportSinks rs = report_sinks_load(ms);
+            if (report_has_hist(rs)) {
+                uint32_t *hist = hist_lds<1>();
+                hist_zero(hist, hist_sink_bins(rs.hist));
+                __syncthreads();
+                hist_count(hist, hist_sink_bins(rs.hist), lane, valid, c.num, c.den);
+                __syncthreads();
+                hist_flush(hist, hist_sink_bins(rs.hist), hist_sink_copy(rs.hist));
+            }
+            if (report_has_match(rs)) {
+                const bool hit[1] = {match_hit(rs.match, valid, c.num, c.den)};
+                const uint32_t hn[1] = {c.num}, hd[1] = {c.den};
+                const int hr[1] = {c.rot};
+                const uint64_t hi[1] = {o};
+                append_matches<1>(rs.match, lane, hit, hn, hd, hr, hi);
+            }
+            if (report_has_topk(rs)) {
+                Partial entry = partial_none();
+                topk_insert(entry, (uint32_t)rs.topk.cap, lane, c, valid);
+                topk_store(rs.topk, wave, lane, entry);
+            }
             return;
         }
         if constexpr (MODE == MODE_MATCH) {
@@ -522,6 +550,7 @@ int launch_template(Pass p, void *stream, const void *db, const void *qtab, Laun
     case Pass::Match: return lanes_pass<MODE_MATCH>(stream, db, qtab, r, o, n_partials);
     case Pass::Topk: return lanes_pass<MODE_TOPK>(stream, db, qtab, r, o, n_partials);
     case Pass::Hist: return lanes_pass<MODE_HIST>(stream, db, qtab, r, o, n_partials);
+    case Pass::Report: return lanes_pass<MODE_REPORT>(stream, db, qtab, r, o, n_partials);
     }
     return -1;
 }

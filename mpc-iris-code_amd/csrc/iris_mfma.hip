@@ -67,7 +67,10 @@ __device__ __forceinline__ void chunk_step(uint32_t x0, uint32_t x1, const QFrag
 // MF_HIST: every record of the range is counted in the bin of its best rotation's distance (ms =
 // hist_sink: iris_template_histogram) -- LDS atomics into the workgroup's histogram, whose non-zero
 // words are added to the workgroup's copy of the counters once; no partials, no reduce
-enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2, MF_TOPK = 3, MF_HIST = 4 };
+// MF_REPORT: MF_MATCH, MF_TOPK and MF_HIST from one read (iris_template_report): ms = report_sink
+// points at the device's ReportSinks, read after the K loop, and each tile's best rotation, computed
+// once, goes to every sink the struct holds -- a part's presence is workgroup-uniform
+enum { MF_COUNTS = 0, MF_SEARCH = 1, MF_MATCH = 2, MF_TOPK = 3, MF_HIST = 4, MF_REPORT = 5 };
 
 // KS > 1 (small ranges, T = kSplitT): the KS waves of a tile group split K -- wave w computes
 // chunk groups [w' * 100 / KS, +100 / KS) of tiles T * (blockIdx.x * (4 / KS) + w / KS) + t (w' = w % KS)
@@ -173,6 +176,15 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
         hist_zero(hist_lds<1>(), hist_sink_bins(ms));
         if constexpr (KS == 1) __syncthreads();
     }
+    // MF_REPORT: the three sinks; with a histogram part (workgroup-uniform) the same zeroing and barrier
+    ReportSinks rs{};
+    if constexpr (MODE == MF_REPORT) {
+        rs = report_sinks_load(ms);
+        if (report_has_hist(rs)) {
+            hist_zero(hist_lds<1>(), hist_sink_bins(rs.hist));
+            if constexpr (KS == 1) __syncthreads();
+        }
+    }
     if constexpr (KS > 1) {  // the K-slices' partial sums -> slice 0's accumulators (exact)
         __shared__ float red[W][T][32][64];
         if (slice != 0) {
@@ -209,9 +221,9 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     uint64_t hi[T];
     // MF_TOPK recomputes the wave's first tile here from an opaque copy of threadIdx.x: at T = 4 the
     // main loop has no register to spare, and the 64-bit tile numbers this epilogue needs would
-    // otherwise be spilled across it
+    // otherwise be spilled across it (MF_REPORT: its top-k part's)
     uint64_t twe = tw, wave_e = wave;
-    if constexpr (MODE == MF_TOPK) {
+    if constexpr (MODE == MF_TOPK || MODE == MF_REPORT) {
         uint32_t tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
         wave_e = (uint64_t)blockIdx.x * (W / KS) + (tx >> 6) / KS;
@@ -258,6 +270,17 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                 hr[t] = br;
                 continue;
             }
+            if constexpr (MODE == MF_REPORT) {
+                // the histogram's count as MF_HIST; the candidate as MF_TOPK keeps it, which is also
+                // MF_MATCH's record wherever it hits (a hit is a valid lane of half 0)
+                if (report_has_hist(rs)) hist_count(hist_lds<1>(), hist_sink_bins(rs.hist), lane, valid && h == 0, bn, bd);
+                hit[t] = report_has_match(rs) && match_hit(rs.match, valid && h == 0, bn, bd);
+                hn[t] = bn;
+                hd[t] = valid && h == 0 ? bd : 0;
+                hr[t] = br;
+                hi[t] = o;
+                continue;
+            }
             if (valid && dist_out && h == 0) dist_out[o] = bd ? (double)bn / (double)bd : __builtin_inf();
             const Partial c = partial_of(bn, valid ? bd : 0, br, o);
             if (partial_better_dev(c, best)) best = c;
@@ -278,6 +301,23 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                         partial_of(hn[t], hd[t], hr[t], (tile0 + twe + t) * kTile + (lane & 31) - first), true);
         }
         if (slice == 0) topk_store(ms, wave_e, lane, best);
+    }
+    // MF_REPORT: the parts the sinks hold, each as its own mode above -- the histogram's second
+    // barrier under the same workgroup-uniform test as its first
+    if constexpr (MODE == MF_REPORT) {
+        if (report_has_hist(rs)) {
+            __syncthreads();
+            hist_flush(hist_lds<1>(), hist_sink_bins(rs.hist), hist_sink_copy(rs.hist));
+        }
+        if (report_has_match(rs)) append_matches<T>(rs.match, lane, hit, hn, hd, hr, hi);
+        if (report_has_topk(rs)) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                topk_insert(best, (uint32_t)rs.topk.cap, lane,
+                            partial_of(hn[t], hd[t], hr[t], (tile0 + twe + t) * kTile + (lane & 31) - first), true);
+            }
+            if (slice == 0) topk_store(rs.topk, wave_e, lane, best);
+        }
     }
     if constexpr (MODE == MF_SEARCH) {
         __shared__ Partial sh[W];
@@ -1079,6 +1119,7 @@ int launch_template_mfma(Pass p, const Hooks &h, void *stream, const void *db, c
     case Pass::Match: return mfma_pass<MF_MATCH>(h, stream, db, qfrag, r, o, n_partials, fin);
     case Pass::Topk: return mfma_pass<MF_TOPK>(h, stream, db, qfrag, r, o, n_partials, fin);
     case Pass::Hist: return mfma_pass<MF_HIST>(h, stream, db, qfrag, r, o, n_partials, fin);
+    case Pass::Report: return mfma_pass<MF_REPORT>(h, stream, db, qfrag, r, o, n_partials, fin);
     }
     return -1;
 }

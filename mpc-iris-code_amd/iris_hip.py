@@ -86,6 +86,32 @@ class Match(ctypes.Structure):
                 f"rotation={self.rotation})")
 
 
+REPORT_MATCHES, REPORT_TOPK, REPORT_HIST = 1, 2, 4  # IRIS_REPORT_*
+
+
+class Report(ctypes.Structure):
+    """iris_report_t: the arguments and results of iris_template_report."""
+
+    _fields_ = [("parts", ctypes.c_uint32), ("k", ctypes.c_uint32), ("nbins", ctypes.c_uint32),
+                ("topk_count", ctypes.c_uint32), ("threshold", ctypes.c_double),
+                ("matches", ctypes.POINTER(Match)), ("matches_cap", ctypes.c_uint64),
+                ("matches_count", ctypes.c_uint64), ("topk", ctypes.POINTER(Match)),
+                ("bins", ctypes.POINTER(ctypes.c_uint64)), ("invalid", ctypes.c_uint64)]
+
+
+class ReportResult:
+    """What TemplateEngine.report() returns; the fields of a part that was not asked for are None."""
+
+    __slots__ = ("matches", "matches_count", "topk", "bins", "invalid")
+
+    def __init__(self):
+        self.matches = self.matches_count = self.topk = self.bins = self.invalid = None
+
+    def __repr__(self):
+        return (f"ReportResult(matches_count={self.matches_count}, topk={None if self.topk is None else len(self.topk)}, "
+                f"bins={None if self.bins is None else len(self.bins)}, invalid={self.invalid})")
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -210,6 +236,7 @@ def load_library(path=None):
                                  ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
             "iris_template_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
+            "iris_template_report": ([P, P, u64, u64, u64, ctypes.POINTER(Report)], ctypes.c_int),
             "iris_resolver_histogram": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, ctypes.c_uint32, P, P],
                                         ctypes.c_int),
             "iris_resolver_histogram_masks": ([P, P, u64, u64, P, ctypes.c_uint32, ctypes.c_uint32, P, P], ctypes.c_int),
@@ -291,6 +318,7 @@ def exported_symbols():
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
         "iris_template_histogram", "iris_template_batch_histogram",
         "iris_resolver_histogram", "iris_resolver_histogram_masks", "iris_resolver_batch_histogram_masks",
+        "iris_template_report",
     ]
 
 
@@ -1199,6 +1227,54 @@ class TemplateEngine(_Engine):
                                                       ctypes.byref(invalid)))
         return bins, int(invalid.value)
 
+    def report(self, db, threshold=None, cap=None, k=None, nbins=None, first=0, n=None, index_base=0):
+        """Several of matches(), topk() and histogram() from ONE read of the range
+        (iris_template_report; no reference counterpart) -> ReportResult.  A part is asked for by
+        its argument: `threshold` (with `cap` as in matches(): None returns every match, 0 only
+        counts) fills .matches and .matches_count, `k` fills .topk, `nbins` fills .bins and
+        .invalid; each is exactly what the sibling method returns, the others stay None.  At least
+        one part must be asked for."""
+        n = (len(db) - first) if n is None else n
+        r = Report()
+        res = ReportResult()
+        keep = []  # the arrays the struct points at
+        want_all = False
+        if threshold is not None:
+            r.parts |= REPORT_MATCHES
+            r.threshold = float(threshold)
+            want_all = cap is None
+            room = max(1024, getattr(self, "_match_room", 0)) if want_all else int(cap)
+            r.matches_cap = room
+            if room:
+                keep.append((Match * room)())
+                r.matches = keep[-1]
+        if k is not None:
+            r.parts |= REPORT_TOPK
+            r.k = int(k)
+            keep.append((Match * (max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1))())
+            r.topk = keep[-1]
+        if nbins is not None:
+            nb = int(nbins)
+            r.parts |= REPORT_HIST
+            r.nbins = nb
+            res.bins = np.zeros(nb if 0 < nb <= HIST_MAX_BINS else 1, np.uint64)
+            r.bins = res.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        _check(load_library().iris_template_report(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                   ctypes.byref(r)))
+        if threshold is not None:
+            res.matches_count = int(r.matches_count)
+            if want_all and res.matches_count > r.matches_cap:  # the rest of a longer list: the sibling's pass
+                res.matches, _ = self.matches(db, threshold, first, n, index_base, cap=res.matches_count)
+            else:
+                res.matches = [_copy_match(r.matches[i]) for i in range(min(res.matches_count, r.matches_cap))]
+            if want_all:
+                self._match_room = min(res.matches_count + res.matches_count // 4, 1 << 22)
+        if k is not None:
+            res.topk = [_copy_match(r.topk[i]) for i in range(r.topk_count)]
+        if nbins is not None:
+            res.invalid = int(r.invalid)
+        return res
+
     def topk_async(self, db, k, first=0, n=None, index_base=0):
         """Enqueue topk() and return at once (iris_template_topk_async) -> PendingTopk, whose
         wait() returns what topk() with the same arguments returns.  The engine may be closed
@@ -1839,7 +1915,7 @@ def f64_bits(x):
 
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
-    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "TOPK_MAX", "HIST_MAX_BINS", "dot_bool", "dot_u16",
+    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "TOPK_MAX", "HIST_MAX_BINS", "Report", "ReportResult", "REPORT_MATCHES", "REPORT_TOPK", "REPORT_HIST", "dot_bool", "dot_u16",
     "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
