@@ -21,7 +21,7 @@ use std::ptr;
 use super::{check, default_device, ffi, match_to_pair, Database, Device, Record, Result, ShardedDatabase};
 use crate::{Bits, EncodedBits, Template};
 
-/// The result of `TemplateEngine::report`: the parts that were asked for, each as its sibling method
+/// The result of `TemplateEngine::report`, `MasksEngine::report` and `resolver_report`: the parts that were asked for, each as its sibling method
 /// returns it.
 #[derive(Clone, Debug, Default)]
 pub struct Report {
@@ -111,6 +111,76 @@ pub fn resolver_histogram(
         )
     })?;
     Ok((bins, invalid))
+}
+
+/// Runs one report call (iris_template_report, iris_resolver_report, iris_resolver_report_masks):
+/// `call(report)` on an `IrisReport` filled from the selected parts -- `matches = Some((threshold,
+/// cap))`, `k = Some(k)`, `nbins = Some(nbins)` -- -> the parts that were asked for.
+fn collect_report(
+    matches: Option<(f64, u64)>,
+    k: Option<u32>,
+    nbins: Option<u32>,
+    mut call: impl FnMut(&mut ffi::IrisReport) -> i32,
+) -> Result<Report> {
+    let mut list = vec![ffi::IrisMatch::default(); matches.map_or(0, |m| m.1) as usize];
+    let mut best = vec![ffi::IrisMatch::default(); k.map_or(0, |k| k.max(1)) as usize];
+    let mut bins = vec![0u64; nbins.map_or(0, |b| b.clamp(1, ffi::IRIS_HIST_MAX_BINS)) as usize];
+    let mut r = ffi::IrisReport {
+        parts: 0,
+        k: k.unwrap_or(0),
+        nbins: nbins.unwrap_or(0),
+        topk_count: 0,
+        threshold: matches.map_or(0.0, |m| m.0),
+        matches: if list.is_empty() { ptr::null_mut() } else { list.as_mut_ptr() },
+        matches_cap: list.len() as u64,
+        matches_count: 0,
+        topk: best.as_mut_ptr(),
+        bins: bins.as_mut_ptr(),
+        invalid: 0,
+    };
+    if matches.is_some() {
+        r.parts |= ffi::IRIS_REPORT_MATCHES;
+    }
+    if k.is_some() {
+        r.parts |= ffi::IRIS_REPORT_TOPK;
+    }
+    if nbins.is_some() {
+        r.parts |= ffi::IRIS_REPORT_HIST;
+    }
+    check(call(&mut r))?;
+    list.truncate(r.matches_count.min(r.matches_cap) as usize);
+    best.truncate(r.topk_count as usize);
+    Ok(Report {
+        matches: matches.map(|_| (list.iter().map(match_to_pair).collect(), r.matches_count)),
+        topk: k.map(|_| best.iter().map(match_to_pair).collect()),
+        histogram: nbins.map(|_| (bins, r.invalid)),
+    })
+}
+
+/// Several of the resolver's matches, top-k and histogram over device arrays of n * 31 u16 from
+/// ONE read of the share rows (iris_resolver_report; no reference counterpart).  Parts as in
+/// `TemplateEngine::report`; each selected part is exactly what the sibling call returns.
+pub fn resolver_report(
+    dev: &Device,
+    shares_device: &[*const u16],
+    denoms_device: *const u16,
+    n: u64,
+    index_base: u64,
+    matches: Option<(f64, u64)>,
+    k: Option<u32>,
+    nbins: Option<u32>,
+) -> Result<Report> {
+    collect_report(matches, k, nbins, |r| unsafe {
+        ffi::iris_resolver_report(
+            dev.raw(),
+            shares_device.as_ptr(),
+            shares_device.len() as u32,
+            denoms_device,
+            n,
+            index_base,
+            r as *mut ffi::IrisReport as *mut _,
+        )
+    })
 }
 
 /// An engine handle plus the device it lives on (kept alive by the clone).
@@ -339,6 +409,34 @@ impl MasksEngine {
             )
         })?;
         Ok((bins, invalid))
+    }
+
+    /// Several of `matches`, `topk` and `histogram` of that step from ONE masks pass
+    /// (iris_resolver_report_masks; no reference counterpart).  Parts as in `TemplateEngine::report`;
+    /// each selected part is exactly what the sibling method returns.
+    pub fn report(
+        &self,
+        masks: &Database,
+        first: u64,
+        n: u64,
+        shares_device: &[*const u16],
+        index_base: u64,
+        matches: Option<(f64, u64)>,
+        k: Option<u32>,
+        nbins: Option<u32>,
+    ) -> Result<Report> {
+        collect_report(matches, k, nbins, |r| unsafe {
+            ffi::iris_resolver_report_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                index_base,
+                r as *mut ffi::IrisReport as *mut _,
+            )
+        })
     }
 
     /// The same step with the participants' replies still in host memory (`shares[p]` holds the
@@ -755,40 +853,8 @@ impl TemplateEngine {
         k: Option<u32>,
         nbins: Option<u32>,
     ) -> Result<Report> {
-        let mut list = vec![ffi::IrisMatch::default(); matches.map_or(0, |m| m.1) as usize];
-        let mut best = vec![ffi::IrisMatch::default(); k.map_or(0, |k| k.max(1)) as usize];
-        let mut bins = vec![0u64; nbins.map_or(0, |b| b.clamp(1, ffi::IRIS_HIST_MAX_BINS)) as usize];
-        let mut r = ffi::IrisReport {
-            parts: 0,
-            k: k.unwrap_or(0),
-            nbins: nbins.unwrap_or(0),
-            topk_count: 0,
-            threshold: matches.map_or(0.0, |m| m.0),
-            matches: if list.is_empty() { ptr::null_mut() } else { list.as_mut_ptr() },
-            matches_cap: list.len() as u64,
-            matches_count: 0,
-            topk: best.as_mut_ptr(),
-            bins: bins.as_mut_ptr(),
-            invalid: 0,
-        };
-        if matches.is_some() {
-            r.parts |= ffi::IRIS_REPORT_MATCHES;
-        }
-        if k.is_some() {
-            r.parts |= ffi::IRIS_REPORT_TOPK;
-        }
-        if nbins.is_some() {
-            r.parts |= ffi::IRIS_REPORT_HIST;
-        }
-        check(unsafe {
-            ffi::iris_template_report(self.h.raw, db.raw(), first, n, index_base, &mut r as *mut ffi::IrisReport as *mut _)
-        })?;
-        list.truncate(r.matches_count.min(r.matches_cap) as usize);
-        best.truncate(r.topk_count as usize);
-        Ok(Report {
-            matches: matches.map(|_| (list.iter().map(match_to_pair).collect(), r.matches_count)),
-            topk: k.map(|_| best.iter().map(match_to_pair).collect()),
-            histogram: nbins.map(|_| (bins, r.invalid)),
+        collect_report(matches, k, nbins, |r| unsafe {
+            ffi::iris_template_report(self.h.raw, db.raw(), first, n, index_base, r as *mut ffi::IrisReport as *mut _)
         })
     }
 

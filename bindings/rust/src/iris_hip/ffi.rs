@@ -106,7 +106,8 @@ pub struct IrisMatch {
     pub reserved: u32,
 }
 
-/// `iris_report_t`: the arguments and results of `iris_template_report` (no implicit padding).
+/// `iris_report_t`: the arguments and results of `iris_template_report` and the resolver reports
+/// (no implicit padding).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct IrisReport {
@@ -486,6 +487,27 @@ extern "C" {
         nbins: u32,
         bins: *mut u64,
         invalid: *mut u64,
+    ) -> c_int;
+    // resolver reports: the combined pass over the participants' share rows; `report` points at an
+    // IrisReport (the header declares it void *)
+    pub fn iris_resolver_report(
+        dev: *mut IrisDevice,
+        shares_device: *const *const u16,
+        parts: u32,
+        denoms_device: *const u16,
+        n: u64,
+        index_base: u64,
+        report: *mut c_void,
+    ) -> c_int;
+    pub fn iris_resolver_report_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        report: *mut c_void,
     ) -> c_int;
     // threshold matching: every record below a distance (no reference counterpart for the threshold)
     pub fn iris_template_matches(

@@ -779,10 +779,10 @@ int iris_template_batch_histogram(iris_engine_t *engine, const iris_db_t *db, ui
  * iris_template_matches does (never with matches_cap == 0).
  *
  * Out of scope: the pipelined forms (a report pass neither hosts nor is hosted in the sharing ring);
- * template batch and masks batch engines; the resolver forms (iris_resolver_report_masks would be
- * the natural next: the fused masks kernel ends in the same three sinks); host-array forms and
+ * template batch and masks batch engines; host-array forms and
  * device groups; more than one threshold, k or histogram per call; a search part -- topk[0] at
- * k = 1 is the search's result. */
+ * k = 1 is the search's result.  The resolver forms, iris_resolver_report and
+ * iris_resolver_report_masks, take this struct and these bits: section "resolver reports" below. */
 #define IRIS_REPORT_MATCHES 1
 #define IRIS_REPORT_TOPK 2
 #define IRIS_REPORT_HIST 4
@@ -847,6 +847,51 @@ int iris_resolver_histogram_masks(iris_engine_t *engine, const iris_db_t *masks_
 int iris_resolver_batch_histogram_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
                                         const uint16_t *const *shares_device, uint32_t parts,
                                         uint32_t nbins, uint64_t *bins /* [nq][nbins] */, uint64_t *invalid /* [nq] */);
+
+/* -------------------------------------------------------- resolver reports
+ * The combined pass where the MPC deployment first has distances: at the resolver, after the
+ * participants' [u16; 31] share rows are summed and decoded against the masks denominators
+ * (src/main.rs:597-621, src/lib.rs:97-107).  No party holds templates there, so the resolver
+ * operator who wants the match list, the k closest records and the score histogram of one probe
+ * pays three passes over 1786 B per record (3 parts); a resolver report reads them once.  Both calls
+ * take the iris_report_t and the IRIS_REPORT_* bits of "combined passes" unchanged.
+ *
+ * The whole semantics: EACH SELECTED PART IS BYTE FOR BYTE WHAT ITS SIBLING CALL WRITES for the
+ * same inputs --
+ *             iris_resolver_report         iris_resolver_report_masks
+ *   MATCHES   iris_resolver_matches        iris_resolver_matches_masks      (threshold, cap, index_base)
+ *   TOPK      iris_resolver_topk           iris_resolver_topk_masks         (k, index_base)
+ *   HIST      iris_resolver_histogram      iris_resolver_histogram_masks    (nbins)
+ * so indices are index_base + row, a distance above 1 from garbage shares joins the last bin, and
+ * a record whose 31 denominators are all zero is in no list and counts in `invalid`.  The fields
+ * and arrays of a part that is not selected are neither read nor written.
+ *
+ * Refusals: the value arguments are checked before the handles -- report->parts, then each selected
+ * part's own arguments under its sibling's rules, then the number of share parts (1..8) -- then the
+ * handles and the range as in the siblings: iris_resolver_report_masks needs a single-query masks
+ * engine and a masks database of either layout; a masks batch engine is IRIS_E_ARG.  A refused or
+ * failed call writes nothing, the out fields of the struct included.  n == 0: the counts and the
+ * bins are zero, and nothing is launched.
+ *
+ * One part selected runs that sibling's own pass.  Two or three run one pass -- TILES: the fused
+ * masks kernel; LANES and iris_resolver_report: the resolver kernel, for a masks database behind
+ * the masks kernel into the workspace -- followed on the stream by the top-k merge and the
+ * histogram's reduce, and the call waits once.  A match list that overflows the room of the first
+ * pass runs the matches part alone once more (never with matches_cap == 0); on a LANES database
+ * that pass reuses the denominators already in the workspace.
+ *
+ * Out of scope: the masks batch engine (an iris_resolver_batch_report_masks needs per-slot sinks
+ * and a per-group overflow rerun, at the register ceiling of the batch kernel's resolving form: the
+ * next follow-up); host-array forms (*_host); pipelined forms; device groups; more than one
+ * threshold, k or histogram per call; a search part -- topk[0] at k = 1 is the search's result. */
+/* iris_resolver_search's sibling: denominators given */
+int iris_resolver_report(iris_device_t *dev, const uint16_t *const *shares_device, uint32_t parts,
+                         const uint16_t *denoms_device, uint64_t n, uint64_t index_base,
+                         void *report /* iris_report_t * */);
+/* iris_resolver_search_masks' sibling: the denominators computed on the fly from the masks database */
+int iris_resolver_report_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                               const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                               void *report /* iris_report_t * */);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

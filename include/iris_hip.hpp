@@ -66,7 +66,7 @@ struct Histogram {
     uint64_t invalid = 0;
 };
 
-// What a report call asks for (iris_template_report): a part is selected by giving its argument.
+// What a report call asks for (iris_template_report, iris_resolver_report*): a part is selected by giving its argument.
 struct ReportRequest {
     std::optional<double> threshold;  // the matches part, with cap (kAllMatches: every match)
     uint64_t cap = kAllMatches;
@@ -118,6 +118,51 @@ inline std::vector<Match> collect_topk(uint32_t k, F call) {
     check(call(list.data(), &count));
     list.resize(count);
     return list;
+}
+// One report call (iris_template_report, iris_resolver_report, iris_resolver_report_masks): call(&r) -> rc
+// with r filled from the request; rematch(count) is the sibling matches call with room for `count`
+// records, which a list longer than the 1024 of cap = kAllMatches comes from.
+template <class F, class G>
+inline Report collect_report(const ReportRequest &req, F call, G rematch) {
+    iris_report_t r{};
+    Report res;
+    std::vector<Match> list, best;
+    const bool all = req.cap == kAllMatches;
+    if (req.threshold) {
+        r.parts |= IRIS_REPORT_MATCHES;
+        r.threshold = *req.threshold;
+        r.matches_cap = all ? 1024 : req.cap;
+        list.resize(r.matches_cap);
+        r.matches = r.matches_cap ? list.data() : nullptr;
+    }
+    if (req.k) {
+        r.parts |= IRIS_REPORT_TOPK;
+        r.k = *req.k;
+        best.resize(std::max<uint32_t>(*req.k, 1));
+        r.topk = best.data();
+    }
+    if (req.nbins) {
+        r.parts |= IRIS_REPORT_HIST;
+        r.nbins = *req.nbins;
+        res.histogram.emplace();
+        res.histogram->bins.assign(r.nbins && r.nbins <= IRIS_HIST_MAX_BINS ? r.nbins : 1, 0);
+        r.bins = res.histogram->bins.data();
+    }
+    check(call(&r));
+    if (req.threshold) {
+        if (all && r.matches_count > r.matches_cap) {
+            res.matches = rematch(r.matches_count);
+        } else {
+            list.resize(std::min<uint64_t>(r.matches_cap, r.matches_count));
+            res.matches = Matches{std::move(list), r.matches_count};
+        }
+    }
+    if (req.k) {
+        best.resize(r.topk_count);
+        res.topk = std::move(best);
+    }
+    if (req.nbins) res.histogram->invalid = r.invalid;
+    return res;
 }
 }  // namespace detail
 
@@ -601,6 +646,19 @@ public:
                                             nbins, res.bins.data(), &res.invalid));
         return res;
     }
+    // Several of matches(), topk() and histogram() of that resolver step from ONE masks pass
+    // (iris_resolver_report_masks; no reference counterpart): each part the request selects is exactly
+    // what the sibling method returns.
+    Report report(const Database &db, const std::vector<const uint16_t *> &shares_device, const ReportRequest &req,
+                  uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        return detail::collect_report(
+            req,
+            [&](iris_report_t *r) {
+                return iris_resolver_report_masks(h_, db.handle(), first, n, shares_device.data(),
+                                                  (uint32_t)shares_device.size(), index_base, r);
+            },
+            [&](uint64_t count) { return matches(db, shares_device, *req.threshold, first, n, index_base, count); });
+    }
     // The same with the participants' outputs in host memory (the rows as they arrive): summed on
     // the host, the sum uploaded (iris_resolver_search_masks_host).
     Match resolve_host(const Database &db, const std::vector<const std::vector<Rotations> *> &shares, uint64_t first,
@@ -833,45 +891,9 @@ public:
     // reference counterpart): each part the request selects is exactly what the sibling method returns.
     // cap = kAllMatches: room for 1024 matches in the combined pass, a longer list through matches().
     Report report(const Database &db, const ReportRequest &req, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
-        iris_report_t r{};
-        Report res;
-        std::vector<Match> list, best;
-        const bool all = req.cap == kAllMatches;
-        if (req.threshold) {
-            r.parts |= IRIS_REPORT_MATCHES;
-            r.threshold = *req.threshold;
-            r.matches_cap = all ? 1024 : req.cap;
-            list.resize(r.matches_cap);
-            r.matches = r.matches_cap ? list.data() : nullptr;
-        }
-        if (req.k) {
-            r.parts |= IRIS_REPORT_TOPK;
-            r.k = *req.k;
-            best.resize(std::max<uint32_t>(*req.k, 1));
-            r.topk = best.data();
-        }
-        if (req.nbins) {
-            r.parts |= IRIS_REPORT_HIST;
-            r.nbins = *req.nbins;
-            res.histogram.emplace();
-            res.histogram->bins.assign(r.nbins && r.nbins <= IRIS_HIST_MAX_BINS ? r.nbins : 1, 0);
-            r.bins = res.histogram->bins.data();
-        }
-        check(iris_template_report(h_, db.handle(), first, n, index_base, &r));
-        if (req.threshold) {
-            if (all && r.matches_count > r.matches_cap) {
-                res.matches = matches(db, *req.threshold, first, n, index_base, r.matches_count);
-            } else {
-                list.resize(std::min<uint64_t>(r.matches_cap, r.matches_count));
-                res.matches = Matches{std::move(list), r.matches_count};
-            }
-        }
-        if (req.k) {
-            best.resize(r.topk_count);
-            res.topk = std::move(best);
-        }
-        if (req.nbins) res.histogram->invalid = r.invalid;
-        return res;
+        return detail::collect_report(
+            req, [&](iris_report_t *r) { return iris_template_report(h_, db.handle(), first, n, index_base, r); },
+            [&](uint64_t count) { return matches(db, *req.threshold, first, n, index_base, count); });
     }
     // pipelined form: returns once the search is enqueued (the engine may be destroyed before the wait)
     PendingSearch search_async(const Database &db, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
@@ -1056,6 +1078,18 @@ inline Histogram resolver_histogram(Device &dev, const std::vector<const uint16_
     check(iris_resolver_histogram(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
                                   nbins, res.bins.data(), &res.invalid));
     return res;
+}
+// Device-array form of the resolver's report (iris_resolver_report): several of resolver_matches(),
+// resolver_topk() and resolver_histogram() from one read of the share rows.
+inline Report resolver_report(Device &dev, const std::vector<const uint16_t *> &shares_device, const uint16_t *denoms_device,
+                              uint64_t n, const ReportRequest &req, uint64_t index_base = 0) {
+    return detail::collect_report(
+        req,
+        [&](iris_report_t *r) {
+            return iris_resolver_report(dev.handle(), shares_device.data(), (uint32_t)shares_device.size(), denoms_device, n,
+                                        index_base, r);
+        },
+        [&](uint64_t count) { return resolver_matches(dev, shares_device, denoms_device, n, *req.threshold, index_base, count); });
 }
 // Merges top-k lists that carry global indices (shards, chunks, GPUs) into the k best, best first
 // (iris_topk_merge; host only).

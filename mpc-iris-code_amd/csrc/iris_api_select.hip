@@ -3,7 +3,7 @@
 // the single-query template match and top-k (their handles live by iris_pending.hpp; here is only
 // what a match or a top-k handle adds), the distance histograms of the template engines and of
 // the resolver forms, and the combined pass that answers a match, a top-k and a histogram call of
-// one probe from one read (iris_template_report).
+// one probe from one read (iris_template_report, iris_resolver_report, iris_resolver_report_masks).
 // Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
@@ -17,11 +17,13 @@ extern "C" {
 // ------------------------------------------------------------------ the single-query passes
 
 // The kernel_stats name of a family's select pass; NULL for a mode the family has no pass for.
-static const char *pass_name(Pass p, const char *match, const char *topk, const char *hist = nullptr) {
+static const char *pass_name(Pass p, const char *match, const char *topk, const char *hist = nullptr,
+                             const char *report = nullptr) {
     switch (p) {
     case Pass::Match: return match;
     case Pass::Topk: return topk;
     case Pass::Hist: return hist;
+    case Pass::Report: return report;
     default: return nullptr;
     }
 }
@@ -30,7 +32,7 @@ static const char *pass_name(Pass p, const char *match, const char *topk, const 
 // kernel on a TILES database (the engine's qfrag), the LANES kernel otherwise (its qtab).
 static int launch_template_select(iris_device *d, const iris_db *db, const void *qtab, const void *qfrag, LaunchRange r,
                                   Pass p, const MatchSink &sink) {
-    const char *name = pass_name(p, "template_match", "template_topk", "template_hist");
+    const char *name = pass_name(p, "template_match", "template_topk", "template_hist", "template_report");
     if (!name) return fail(IRIS_E_ARG, "no template pass of that mode");
     return timed(d, name, r.n, [&] {
         return db->k.layout == IRIS_LAYOUT_TILES ? launch_template_mfma(p, d->hooks, d->stream, db->data, qfrag, r, sink)
@@ -38,8 +40,8 @@ static int launch_template_select(iris_device *d, const iris_db *db, const void 
     });
 }
 
-// The single-query masks form of a match, a top-k or a histogram pass, on masks engine c and the shares of its
-// query: a TILES database runs the fused masks_mfma_kernel; LANES the masks kernel into the
+// The single-query masks form of a match, a top-k, a histogram or a report pass (sink: report_sink),
+// on masks engine c and the shares of its query: a TILES database runs the fused masks_mfma_kernel; LANES the masks kernel into the
 // workspace (the denominators) and then the resolver kernel.  *den: the denominators once they are
 // enqueued -- a caller that launches again (the rerun of an overflowing list) while the workspace
 // is still theirs keeps it, and they are not computed twice.
@@ -48,7 +50,7 @@ static int masks_single_launch(iris_device *d, const iris_engine *c, const iris_
                                const uint16_t **den) {
     const bool tiles = db->k.layout == IRIS_LAYOUT_TILES;
     const char *name = pass_name(p, tiles ? "masks_match" : "resolver_match", tiles ? "masks_topk" : "resolver_topk",
-                                 tiles ? "masks_resolve_hist" : "resolver_hist");
+                                 tiles ? "masks_resolve_hist" : "resolver_hist", tiles ? "masks_report" : "resolver_report");
     if (!name) return fail(IRIS_E_ARG, "no masks pass of that mode");
     if (tiles)
         return timed(d, name, r.n, [&] {
@@ -994,23 +996,32 @@ static_assert(sizeof(ReportSinks) <= kReportCountOff && kReportHistOff % 64 == 0
 // The device's counter buffer of a report call: the match counter, then (a line on) the histogram's copies
 constexpr size_t kReportHistWord = 8;
 
-// Two or three parts of iris_template_report over r (not empty) from ONE pass ("template_report").
-// The device's buffers are shared by region: d->matches holds the top-k lists (and the merge's spare
-// lists) and behind them the match records; d->match_count the match counter and behind it the
-// histogram's copies; the pinned result as laid out above.  The pass is followed on the stream by
-// the top-k merge, the histogram's reduce (copies = 1: a copy) and the copy of the match counter,
-// and the call waits once.  A match list that overflows its room (matches_run_units' rule: the
-// caller's cap or kMatchFirstRoom, a grown buffer in full, cap = 0 never) runs again alone, as a
-// plain match pass ("template_match") whose room is the reported count; its ensure() may replace
-// d->matches, so the top-k list and the histogram are taken off the pinned result first.  Nothing
-// reaches *rep or its arrays before every part has succeeded.
-static int report_run(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r, uint64_t index_base,
-                      iris_report_t *rep) {
+// The passes of one report call, whichever family runs them: launch(p, sink) enqueues the family's
+// pass of mode p over the call's range, timed under the family's own names -- Pass::Report with
+// report_sink of the device's ReportSinks, Pass::Match / Topk / Hist with that part's sink, as the
+// sibling call launches it.  units: the lists a top-k (or report) pass writes, 0 for an empty range.
+struct ReportPasses {
+    uint64_t units;
+    std::function<int(Pass, const MatchSink &)> launch;
+};
+
+// Two or three parts of a report call over n records (not none) from ONE pass ("template_report",
+// "masks_report", "resolver_report").  The device's buffers are shared by region: d->matches holds
+// the top-k lists (and the merge's spare lists) and behind them the match records; d->match_count
+// the match counter and behind it the histogram's copies; the pinned result as laid out above.
+// The pass is followed on the stream by the top-k merge, the histogram's reduce (copies = 1: a
+// copy) and the copy of the match counter, and the call waits once.  A match list that overflows
+// its room (matches_run_units' rule: the caller's cap or kMatchFirstRoom, a grown buffer in full,
+// cap = 0 never) runs again alone, as the family's plain match pass whose room is the reported
+// count; its ensure() may replace d->matches, so the top-k list and the histogram are taken off
+// the pinned result first.  That ensure() grows the buffer by the lists' bytes as well, so a caller
+// with a steady list length reruns once, not in every call.  Nothing reaches *rep or its arrays before every part has succeeded.
+static int report_run(iris_device *d, uint64_t n, uint64_t base, iris_report_t *rep, const ReportPasses &ps) {
     const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
                want_hist = rep->parts & IRIS_REPORT_HIST;
-    const uint64_t n = r.n, base = index_base + r.first, cap = want_match ? rep->matches_cap : 0;
+    const uint64_t cap = want_match ? rep->matches_cap : 0;
     const uint32_t k = want_topk ? rep->k : 0, nbins = want_hist ? rep->nbins : 0;
-    const uint64_t units = want_topk ? template_topk_lists(d, db, r) : 0;
+    const uint64_t units = want_topk ? ps.units : 0;
     const size_t lists_bytes = (units + topk_spare_lists(units)) * k * sizeof(Partial);
     const uint32_t words = nbins + 1, copies = !want_hist ? 0 : d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
     uint64_t room = 0;
@@ -1036,11 +1047,7 @@ static int report_run(iris_device *d, const iris_engine *e, const iris_db *db, L
     if (want_hist) stage->hist = hist_sink(hist, nbins, copies);
     const ReportSinks *dsinks = (const ReportSinks *)d->match_sinks.p;
     HIPCHK(hipMemcpyAsync((void *)dsinks, stage, sizeof(ReportSinks), hipMemcpyHostToDevice, d->stream));
-    CHK(timed(d, "template_report", n, [&] {
-        return db->k.layout == IRIS_LAYOUT_TILES
-                   ? launch_template_mfma(Pass::Report, d->hooks, d->stream, db->data, e->qfrag, r, dsinks)
-                   : launch_template(Pass::Report, d->stream, db->data, e->qtab, r, dsinks);
-    }));
+    CHK(ps.launch(Pass::Report, report_sink(dsinks)));
     if (want_topk)
         CHK(timed(d, "topk_merge", units, [&] {
             return launch_topk_merge(d->stream, lists, spare, units, k, (Partial *)(res + kReportTopkOff));
@@ -1080,10 +1087,11 @@ static int report_run(iris_device *d, const iris_engine *e, const iris_db *db, L
     }
     if (take) {
         if (total > room) {  // the matches part alone once more, its room the reported count
-            CHK(ensure(d, d->matches, total * sizeof(Partial)));
+            // grown past the lists too: the next such call finds room for this list behind them (reuse_grown)
+            CHK(ensure(d, d->matches, lists_bytes + total * sizeof(Partial)));
             records = (Partial *)d->matches.p;
             HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint64_t), d->stream));
-            CHK(launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Match, MatchSink{records, total, cnt, rep->threshold}));
+            CHK(ps.launch(Pass::Match, MatchSink{records, total, cnt, rep->threshold}));
             HIPCHK(hipMemcpyAsync(res + kReportCountOff, cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
             CHK(sync(d));
             if (memcmp(res + kReportCountOff, &total, sizeof(total)) != 0)
@@ -1104,55 +1112,108 @@ static int report_run(iris_device *d, const iris_engine *e, const iris_db *db, L
     return 0;
 }
 
+// The value arguments of a report call, refused whatever the handles: the struct, its parts, then
+// each selected part under its sibling's rules.
+static int report_args(iris_report_t *rep) {
+    ARG(rep, "report is NULL");
+    const uint32_t all = IRIS_REPORT_MATCHES | IRIS_REPORT_TOPK | IRIS_REPORT_HIST;
+    ARG(rep->parts != 0 && (rep->parts & ~all) == 0, "parts must be one or more of IRIS_REPORT_MATCHES, _TOPK, _HIST");
+    if (rep->parts & IRIS_REPORT_MATCHES) CHK(matches_args(rep->threshold, rep->matches, rep->matches_cap, &rep->matches_count));
+    if (rep->parts & IRIS_REPORT_TOPK) CHK(topk_args(rep->k, rep->topk, &rep->topk_count));
+    if (rep->parts & IRIS_REPORT_HIST) CHK(hist_args(rep->nbins, rep->bins, &rep->invalid));
+    return 0;
+}
+
+// A report call once its arguments, handles and range stand (the device locked and current), for
+// every family.  One part: that sibling's own pass through its own runner, its count through a
+// local -- a failed call leaves the struct as it was.  An empty range: zeros, nothing launched.
+// Otherwise report_run.
+static int report_dispatch(iris_device *d, uint64_t n, uint64_t base, iris_report_t *rep, const ReportPasses &ps) {
+    if (rep->parts == IRIS_REPORT_MATCHES) {
+        uint64_t count = 0;
+        CHK(matches_run(d, n, base, rep->threshold, rep->matches, rep->matches_cap, &count,
+                        [&](const MatchSink &ms) { return ps.launch(Pass::Match, ms); }));
+        rep->matches_count = count;
+        return 0;
+    }
+    if (rep->parts == IRIS_REPORT_TOPK) {
+        uint32_t count = 0;
+        CHK(topk_run(d, n, base, rep->k, rep->topk, &count, ps.units,
+                     [&](const MatchSink &ts) { return ps.launch(Pass::Topk, ts); }));
+        rep->topk_count = count;
+        return 0;
+    }
+    if (rep->parts == IRIS_REPORT_HIST)
+        return hist_run(d, n, rep->nbins, rep->bins, &rep->invalid, 1,
+                        [&](uint32_t, const MatchSink &hs) { return ps.launch(Pass::Hist, hs); });
+    if (n == 0) {  // nothing is launched
+        if (rep->parts & IRIS_REPORT_MATCHES) rep->matches_count = 0;
+        if (rep->parts & IRIS_REPORT_TOPK) rep->topk_count = 0;
+        if (rep->parts & IRIS_REPORT_HIST) CHK(hist_empty(1, rep->nbins, rep->bins, &rep->invalid));
+        return 0;
+    }
+    return report_run(d, n, base, rep, ps);
+}
+
 // Several of iris_template_matches, iris_template_topk and iris_template_histogram for one probe from
-// one read of the range (header: "combined passes").  One part: that sibling's own pass through its
-// own runner.
+// one read of the range (header: "combined passes").
 int iris_template_report(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
                          void *report) {
     IRIS_KEEP_DEVICE();
     iris_report_t *const rep = (iris_report_t *)report;
-    ARG(rep, "report is NULL");  // the value arguments first: refused whatever the handles
-    const uint32_t all = IRIS_REPORT_MATCHES | IRIS_REPORT_TOPK | IRIS_REPORT_HIST;
-    ARG(rep->parts != 0 && (rep->parts & ~all) == 0, "parts must be one or more of IRIS_REPORT_MATCHES, _TOPK, _HIST");
-    const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
-               want_hist = rep->parts & IRIS_REPORT_HIST;
-    if (want_match) CHK(matches_args(rep->threshold, rep->matches, rep->matches_cap, &rep->matches_count));
-    if (want_topk) CHK(topk_args(rep->k, rep->topk, &rep->topk_count));
-    if (want_hist) CHK(hist_args(rep->nbins, rep->bins, &rep->invalid));
+    CHK(report_args(rep));  // the value arguments first: refused whatever the handles
     CHK(template_args(e, db));
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
     CHK(set_device(d));
     CHK(range_ok(db, first, n));
     const LaunchRange r{first, n};
-    // one part: the sibling's pass, its count through a local -- a failed call leaves the struct as it was
-    if (rep->parts == IRIS_REPORT_MATCHES) {
-        uint64_t count = 0;
-        CHK(matches_run(d, n, index_base + first, rep->threshold, rep->matches, rep->matches_cap, &count,
-                        [&](const MatchSink &ms) { return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Match, ms); }));
-        rep->matches_count = count;
-        return 0;
-    }
-    if (rep->parts == IRIS_REPORT_TOPK) {
-        uint32_t count = 0;
-        const uint64_t units = n ? template_topk_lists(d, db, r) : 0;
-        CHK(topk_run(d, n, index_base + first, rep->k, rep->topk, &count, units, [&](const MatchSink &ts) {
-            return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Topk, ts);
-        }));
-        rep->topk_count = count;
-        return 0;
-    }
-    if (rep->parts == IRIS_REPORT_HIST)
-        return hist_run(d, n, rep->nbins, rep->bins, &rep->invalid, 1, [&](uint32_t, const MatchSink &hs) {
-            return launch_template_select(d, db, e->qtab, e->qfrag, r, Pass::Hist, hs);
-        });
-    if (n == 0) {  // nothing is launched
-        if (want_match) rep->matches_count = 0;
-        if (want_topk) rep->topk_count = 0;
-        if (want_hist) CHK(hist_empty(1, rep->nbins, rep->bins, &rep->invalid));
-        return 0;
-    }
-    return report_run(d, e, db, r, index_base, rep);
+    return report_dispatch(d, n, index_base + first, rep, {n ? template_topk_lists(d, db, r) : 0, [&](Pass p, const MatchSink &s) {
+        return launch_template_select(d, db, e->qtab, e->qfrag, r, p, s);
+    }});
+}
+
+// ------------------------------------------------------------------ resolver reports
+
+// iris_resolver_matches, iris_resolver_topk and iris_resolver_histogram for one probe from one read
+// of the share rows (header: "resolver reports"): resolver_kernel's report mode ("resolver_report").
+int iris_resolver_report(iris_device_t *d, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms,
+                         uint64_t n, uint64_t index_base, void *report) {
+    IRIS_KEEP_DEVICE();
+    iris_report_t *const rep = (iris_report_t *)report;
+    CHK(report_args(rep));  // the value arguments first: refused whatever the handles
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    ARG(d, "NULL argument");
+    CHK(share_args(shares, parts, n, denoms != nullptr));
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    return report_dispatch(d, n, index_base, rep, {resolver_topk_units(n), [&](Pass p, const MatchSink &s) {
+        const char *name = pass_name(p, "resolver_match", "resolver_topk", "resolver_hist", "resolver_report");
+        return timed(d, name, n, [&] { return launch_resolver(p, d->stream, shares, parts, denoms, n, s); });
+    }});
+}
+
+// The masks sibling: TILES runs the fused masks_mfma_kernel<MASKS_REPORT> ("masks_report"); LANES
+// the masks kernel into the workspace, once per call -- the rerun of an overflowing match list
+// reuses the denominators -- and then resolver_kernel's report mode.
+int iris_resolver_report_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                               const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base, void *report) {
+    IRIS_KEEP_DEVICE();
+    iris_report_t *const rep = (iris_report_t *)report;
+    CHK(report_args(rep));  // the value arguments first: refused whatever the handles
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(single_masks_args(e, db, "iris_resolver_batch_matches_masks, _topk_masks and _histogram_masks (there is no batched report)"));
+    CHK(share_args(shares_device, parts, n));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    const LaunchRange r{first, n};
+    const uint64_t units = db->k.layout != IRIS_LAYOUT_TILES ? resolver_topk_units(n) : n ? masks_topk_units(d->hooks, r) : 0;
+    const uint16_t *den = nullptr;
+    return report_dispatch(d, n, index_base, rep, {units, [&](Pass p, const MatchSink &s) {
+        return masks_single_launch(d, e, db, r, shares_device, parts, p, s, &den);
+    }});
 }
 
 }  // extern "C"

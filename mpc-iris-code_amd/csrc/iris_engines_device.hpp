@@ -16,10 +16,12 @@ struct ResolveView {
     uint32_t parts;
     uint64_t base;
     bool aligned;           // every share array is 16-B aligned at `base`
-    const MatchSink &sink;  // MATCH: the query's records, room, counter and threshold; TOPK: topk_sink; HIST: hist_sink
+    const MatchSink &sink;  // MATCH: the query's records, room, counter and threshold; TOPK: topk_sink; HIST: hist_sink;
+                            // REPORT: report_sink of the device's ReportSinks
     double *dist;           // null, or the query's n distances
     Partial &best;          // the lane's running best; TOPK: this lane's entry of the wave's list
     uint32_t *hist = nullptr;  // HIST: the query's LDS histogram of the workgroup (hist_sink_bins(sink) + 1 words)
+    const ReportSinks *report = nullptr;  // REPORT: the three sinks, loaded by the caller ahead of a tile group's tiles
 };
 
 // Resolver epilogue of one tile (records t0 .. t0+31 of the database), `den` its denominators in the
@@ -29,7 +31,11 @@ struct ResolveView {
 // the threshold, or (TOPK) inserts it into the wave's list, or (HIST) counts it in v.hist
 // (hist_count: no running best, no dist, no append; the caller zeroes and flushes v.hist around
 // its walk, behind workgroup barriers).
-template <bool MATCH, bool TOPK, bool HIST = false>
+// REPORT: the staging and the best rotation once, then every sink *v.report holds, each as its own
+// mode above runs it.  The caller reads the sinks where they are used (report_sinks_load: wave-uniform
+// scalar loads, once per tile group), so they live for this epilogue only, not across the K loop,
+// and a part's presence is the same for every wave of the workgroup.
+template <bool MATCH, bool TOPK, bool HIST = false, bool REPORT = false>
 __device__ __forceinline__ void resolve_tile(const ResolveView &v, uint16_t *lds, int lane, uint64_t t0, bool tv,
                                              const v16f &den, uint64_t first, uint64_t end) {
     const bool full = tv && t0 >= first && t0 + 32 <= end && ((t0 - first) & 7) == 0 && v.aligned;
@@ -64,6 +70,21 @@ __device__ __forceinline__ void resolve_tile(const ResolveView &v, uint16_t *lds
     }, bn, bd, br);
     const uint64_t tg = t0 + (lane & 31);
     const bool valid = tv && tg >= first && tg < end;
+    if constexpr (REPORT) {
+        const ReportSinks &rs = *v.report;
+        if (report_has_hist(rs)) hist_count(v.hist, hist_sink_bins(rs.hist), lane, valid && h == 0, bn, bd);
+        if (report_has_match(rs)) {
+            const bool hit[1] = {match_hit(rs.match, valid && h == 0, bn, bd)};
+            const uint32_t hn[1] = {bn}, hd[1] = {bd};
+            const int hr[1] = {br};
+            const uint64_t hi[1] = {tg - first};
+            append_matches<1>(rs.match, lane, hit, hn, hd, hr, hi);
+        }
+        if (report_has_topk(rs))
+            topk_insert(v.best, (uint32_t)rs.topk.cap, lane, partial_of(bn, valid ? bd : 0, br, tg - first), h == 0);
+        __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites
+        return;
+    }
     if constexpr (HIST) {  // half 0 counts: both halves hold the record's best
         hist_count(v.hist, hist_sink_bins(v.sink), lane, valid && h == 0, bn, bd);
         __builtin_amdgcn_wave_barrier();  // LDS reads done before the next tile overwrites

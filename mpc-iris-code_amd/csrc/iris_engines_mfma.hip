@@ -28,8 +28,8 @@ namespace iris {
 // costs registers: 5.1 vs 2.7 ms)
 constexpr int kMasksTiles = 7;
 constexpr int kResolveTiles = 4;
-// MASKS_RESOLVE (1), MASKS_MATCH (3), MASKS_TOPK (4) and MASKS_HIST (5) share the resolver step's shape
-constexpr bool masks_resolving(int mode) { return mode == 1 || mode == 3 || mode == 4 || mode == 5; }
+// MASKS_RESOLVE (1), MASKS_MATCH (3), MASKS_TOPK (4), MASKS_HIST (5) and MASKS_REPORT (6) share the resolver step's shape
+constexpr bool masks_resolving(int mode) { return mode == 1 || (mode >= 3 && mode <= 6); }
 template <int MODE>
 constexpr int masks_tiles() { return !masks_resolving(MODE) ? kMasksTiles : kResolveTiles; }
 constexpr int kMasksBlocksPerCu = 2;  // persistent grid: workgroups per CU
@@ -76,7 +76,14 @@ struct MaskResolve {
 // of a barrier before the walk and added once, behind a barrier after it, to the workgroup's copy of
 // the counters (iris_resolver_histogram_masks).  Both barriers stand outside `if (total)`: waves
 // without a tile group reach them too, as they reach block_argmin's in the search.
-enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3, MASKS_TOPK = 4, MASKS_HIST = 5 };
+// MASKS_REPORT: MASKS_MATCH, MASKS_TOPK and MASKS_HIST from one read (iris_resolver_report_masks):
+// rs.match = report_sink points at the device's ReportSinks, and each tile's best rotation, computed
+// once, goes to every sink the struct holds (resolve_tile's report path).  The sinks are read where
+// they are used -- the bin count ahead of the walk, all three per tile, the lists' and the counters'
+// at the end -- so none of their 24 scalar registers is live across the K loop.  A part's presence
+// is workgroup-uniform; with a histogram part the two barriers stand where MASKS_HIST's do, and with
+// a top-k part every wave of the grid stores its list, as in MASKS_TOPK.
+enum { MASKS_OUT = 0, MASKS_RESOLVE = 1, MASKS_PACKED = 2, MASKS_MATCH = 3, MASKS_TOPK = 4, MASKS_HIST = 5, MASKS_REPORT = 6 };
 
 // Persistent: each wave walks the tile groups wave, wave + nwaves, ... as one
 // flat stream of (group, step) K-steps, so the loads of the next group are in
@@ -126,7 +133,19 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
         hist_zero(hist, hist_sink_bins(rs.match));
         __syncthreads();
     }
-    const ResolveView view{rs.shares, rs.parts, 0, rs.aligned, rs.match, rs.dist_out, best, hist};
+    if constexpr (MODE == MASKS_REPORT) {
+        hist = hist_lds<1>();
+        const ReportSinks up = report_sinks_load(rs.match);
+        if (report_has_hist(up)) {  // workgroup-uniform
+            hist_zero(hist, hist_sink_bins(up.hist));
+            __syncthreads();
+        }
+    }
+    // MASKS_REPORT alone: loaded at the end of each tile group, for its tiles; every other mode neither
+    // writes nor reads it (resolve_tile's report path is the one reader), so it takes no register there
+    ReportSinks group{};
+    const ResolveView view{rs.shares, rs.parts, 0, rs.aligned, rs.match, rs.dist_out, best, hist,
+                           MODE == MASKS_REPORT ? &group : nullptr};
     if (total) {
         zero();
         struct Stage {
@@ -158,6 +177,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
             const uint32_t j = s / kSteps;
             if (s - j * kSteps == kSteps - 1) {  // group j done: write its rows / resolve it
                 const uint64_t tw = (wave + (uint64_t)j * nwaves) * T;
+                if constexpr (MODE == MASKS_REPORT) group = report_sinks_load(rs.match);
 #pragma unroll
                 for (int t = 0; t < T; ++t) {
                     if constexpr (MODE == MASKS_OUT)
@@ -167,7 +187,7 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
                         store_tile_packed((uint8_t *)out, out + (end - first) * 16, (tile0 + tw + t) * kTile, first, end,
                                           tw + t < ntiles, lane, [&](int r) { return (uint32_t)acc[t][r]; });
                     else
-                        resolve_tile<MODE == MASKS_MATCH, MODE == MASKS_TOPK, MODE == MASKS_HIST>(
+                        resolve_tile<MODE == MASKS_MATCH, MODE == MASKS_TOPK, MODE == MASKS_HIST, MODE == MASKS_REPORT>(
                             view, lds, lane, (tile0 + tw + t) * kTile, tw + t < ntiles, acc[t], first, end);
                 }
                 zero();
@@ -190,6 +210,14 @@ __global__ void __launch_bounds__(256, masks_blocks_per_cu<MODE>())
     if constexpr (MODE == MASKS_HIST) {  // every wave of the workgroup: the counts are in before the flush reads them
         __syncthreads();
         hist_flush(hist, hist_sink_bins(rs.match), hist_sink_copy(rs.match));
+    }
+    if constexpr (MODE == MASKS_REPORT) {  // each part as its own mode above, under the same workgroup-uniform tests
+        const ReportSinks done = report_sinks_load(rs.match);
+        if (report_has_topk(done)) topk_store(done.topk, wave, lane, best);
+        if (report_has_hist(done)) {
+            __syncthreads();
+            hist_flush(hist, hist_sink_bins(done.hist), hist_sink_copy(done.hist));
+        }
     }
     if constexpr (MODE == MASKS_RESOLVE) {
         __shared__ Partial sh_best[kWaveSlots];
@@ -330,6 +358,7 @@ int launch_masks_resolve(Pass p, const Hooks &h, void *stream, const void *db, c
     case Pass::Hist:
         if (r.n != 0 && !hist_sink_ok(o.sink)) return -1;
         return masks_resolve_pass<MASKS_HIST>(h, stream, db, qfrag, r, shares, parts, o);
+    case Pass::Report: return masks_resolve_pass<MASKS_REPORT>(h, stream, db, qfrag, r, shares, parts, o);
     default: return -1;
     }
 }

@@ -181,7 +181,7 @@ inline bool hist_sink_ok(const MatchSink &s) {
     const uint32_t nbins = (uint32_t)s.cap;
     return s.count && nbins >= 1 && nbins <= kHistMaxBins && (nbins & (nbins - 1)) == 0;
 }
-// A report pass (iris_template_report) feeds all three from one read of the database: a small DEVICE
+// A report pass (iris_template_report, iris_resolver_report*) feeds all three from one read of the database: a small DEVICE
 // struct holds the three sinks and the pass's MatchSink points at it (report_sink: buf; the other
 // fields are unused), so the kernels keep their signature and read the sinks once, after their K
 // loop.  A part the call did not select is absent: match.count null, topk.cap 0, hist.count null.
@@ -275,7 +275,7 @@ constexpr uint64_t kSharesSplitTiles = 4096;
 //   Topk:   the k closest records of every unit (a wave that holds candidates), into topk_sink lists
 //   Hist:   the distribution of the distances, into hist_sink counters
 //   Report: Match, Topk and Hist together -- those of them its ReportSinks hold -- from one read
-//           (the single-query template kernels only)
+//           (the single-query template kernels, the fused masks kernel and the resolver kernel)
 enum class Pass { Counts, Search, Match, Topk, Hist, Report };
 
 // The operands of a single-query pass; what its mode does not write stays null.

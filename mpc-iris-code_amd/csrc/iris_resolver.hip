@@ -54,7 +54,11 @@ constexpr int kSlots = (kWords + 63) / 64;         // 4
 // hist_sink), one hist_count per lane between two barriers that every wave reaches -- the kernel
 // has no exit before its epilogue -- and the workgroup adds its non-zero words to its copy once.
 // The histogram reuses the staged denominators' LDS behind one more barrier.
-template <bool MATCH = false, bool TOPK = false, bool HIST = false>
+// REPORT (iris_resolver_report): those three from one read of the rows (ms = report_sink: the
+// device's ReportSinks, read once, after the decode).  The match append and the top-k insert and
+// store come first; the histogram follows through sh_den's storage, behind barriers that every wave
+// reaches whether or not the part is present -- no return stands ahead of them.
+template <bool MATCH = false, bool TOPK = false, bool HIST = false, bool REPORT = false>
 __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uint16_t *__restrict__ denoms,
                                                        uint64_t n, double *__restrict__ dist_out,
                                                        Partial *__restrict__ partials, MatchSink ms) {
@@ -107,6 +111,32 @@ __global__ void __launch_bounds__(256) resolver_kernel(ResolverArgs a, const uin
         }
         if (dist_out) dist_out[row0 + lane] = c.den ? (double)c.num / (double)c.den : __builtin_inf();
     }
+    if constexpr (REPORT) {
+        const ReportSinks rs = report_sinks_load(ms);
+        const bool valid = (uint64_t)lane < rows;
+        if (report_has_match(rs)) {
+            const bool hit[1] = {match_hit(rs.match, valid, c.num, c.den)};
+            const uint32_t hn[1] = {c.num}, hd[1] = {c.den};
+            const int hr[1] = {c.rot};
+            const uint64_t hi[1] = {c.idx};
+            append_matches<1>(rs.match, lane, hit, hn, hd, hr, hi);
+        }
+        if (report_has_topk(rs)) {
+            Partial entry = partial_none();
+            topk_insert(entry, (uint32_t)rs.topk.cap, lane, c, valid);
+            topk_store(rs.topk, (uint64_t)blockIdx.x * kWaveSlots + ws, lane, entry);
+        }
+        static_assert(sizeof(sh_den) >= (kHistMaxBins + 1) * sizeof(uint32_t), "the histogram fits sh_den");
+        uint32_t *hist = (uint32_t *)&sh_den[0][0];
+        const bool has_hist = report_has_hist(rs);  // workgroup-uniform
+        __syncthreads();
+        if (has_hist) hist_zero(hist, hist_sink_bins(rs.hist));
+        __syncthreads();
+        if (has_hist) hist_count(hist, hist_sink_bins(rs.hist), lane, valid, c.num, c.den);
+        __syncthreads();
+        if (has_hist) hist_flush(hist, hist_sink_bins(rs.hist), hist_sink_copy(rs.hist));
+        return;
+    }
     if constexpr (HIST) {
         // the histogram (kHistMaxBins + 1 words) takes sh_den's place once every wave has decoded its
         // rows: a buffer of its own would cost a workgroup per CU (36 KB against 31.9 KB of LDS)
@@ -143,7 +173,7 @@ uint32_t resolver_partials(uint64_t n) {
 
 uint64_t resolver_topk_units(uint64_t n) { return (uint64_t)resolver_partials(n) * kWaveSlots; }
 
-template <bool MATCH, bool TOPK, bool HIST = false>
+template <bool MATCH, bool TOPK, bool HIST = false, bool REPORT = false>
 static int resolver_pass(void *stream, const uint16_t *const *shares, uint32_t parts, const uint16_t *denoms, uint64_t n,
                          const PassOut &o) {
     if (n == 0) return 0;
@@ -151,7 +181,7 @@ static int resolver_pass(void *stream, const uint16_t *const *shares, uint32_t p
     ResolverArgs a{};
     for (uint32_t p = 0; p < parts; ++p) a.shares[p] = shares[p];
     a.parts = parts;
-    hipLaunchKernelGGL((resolver_kernel<MATCH, TOPK, HIST>), dim3(resolver_partials(n)), dim3(64 * kWaveSlots), 0,
+    hipLaunchKernelGGL((resolver_kernel<MATCH, TOPK, HIST, REPORT>), dim3(resolver_partials(n)), dim3(64 * kWaveSlots), 0,
                        (hipStream_t)stream, a, denoms, n, o.dist_out, o.partials, o.sink);
     return check_launch();
 }
@@ -166,6 +196,7 @@ int launch_resolver(Pass p, void *stream, const uint16_t *const *shares, uint32_
     case Pass::Hist:
         if (n != 0 && !hist_sink_ok(o.sink)) return -1;
         return resolver_pass<false, false, true>(stream, shares, parts, denoms, n, o);
+    case Pass::Report: return resolver_pass<false, false, false, true>(stream, shares, parts, denoms, n, o);
     default: return -1;
     }
 }

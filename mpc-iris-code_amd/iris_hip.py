@@ -90,7 +90,7 @@ REPORT_MATCHES, REPORT_TOPK, REPORT_HIST = 1, 2, 4  # IRIS_REPORT_*
 
 
 class Report(ctypes.Structure):
-    """iris_report_t: the arguments and results of iris_template_report."""
+    """iris_report_t: the arguments and results of iris_template_report and the resolver reports."""
 
     _fields_ = [("parts", ctypes.c_uint32), ("k", ctypes.c_uint32), ("nbins", ctypes.c_uint32),
                 ("topk_count", ctypes.c_uint32), ("threshold", ctypes.c_double),
@@ -100,7 +100,7 @@ class Report(ctypes.Structure):
 
 
 class ReportResult:
-    """What TemplateEngine.report() returns; the fields of a part that was not asked for are None."""
+    """What TemplateEngine.report(), MasksEngine.report() and resolver_report() return; the fields of a part that was not asked for are None."""
 
     __slots__ = ("matches", "matches_count", "topk", "bins", "invalid")
 
@@ -110,6 +110,52 @@ class ReportResult:
     def __repr__(self):
         return (f"ReportResult(matches_count={self.matches_count}, topk={None if self.topk is None else len(self.topk)}, "
                 f"bins={None if self.bins is None else len(self.bins)}, invalid={self.invalid})")
+
+
+def _report(call, owner, threshold, cap, k, nbins, rematch):
+    """One report call (iris_template_report, iris_resolver_report, iris_resolver_report_masks):
+    fills a Report from the arguments that are not None, runs call(pointer to it) and collects the
+    selected parts -> ReportResult.  cap None returns every match: the first call has room for 1024
+    records (or what `owner` remembers of its last list) and a longer list comes from
+    rematch(count), the sibling call with room for all of them."""
+    r = Report()
+    res = ReportResult()
+    marr = tarr = None  # the arrays the struct points at; the returned records are views into them
+    want_all = False
+    if threshold is not None:
+        r.parts |= REPORT_MATCHES
+        r.threshold = float(threshold)
+        want_all = cap is None
+        room = max(1024, getattr(owner, "_match_room", 0)) if want_all else int(cap)
+        r.matches_cap = room
+        if room:
+            marr = (Match * room)()
+            r.matches = marr
+    if k is not None:
+        r.parts |= REPORT_TOPK
+        r.k = int(k)
+        tarr = (Match * (max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1))()
+        r.topk = tarr
+    if nbins is not None:
+        nb = int(nbins)
+        r.parts |= REPORT_HIST
+        r.nbins = nb
+        res.bins = np.zeros(nb if 0 < nb <= HIST_MAX_BINS else 1, np.uint64)
+        r.bins = res.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    _check(call(ctypes.byref(r)))
+    if threshold is not None:
+        res.matches_count = int(r.matches_count)
+        if want_all and res.matches_count > r.matches_cap:  # the rest of a longer list: the sibling's pass
+            res.matches = rematch(res.matches_count)
+        else:
+            res.matches = [marr[i] for i in range(min(res.matches_count, r.matches_cap))]
+        if want_all:
+            owner._match_room = min(res.matches_count + res.matches_count // 4, 1 << 22)
+    if k is not None:
+        res.topk = [tarr[i] for i in range(r.topk_count)]
+    if nbins is not None:
+        res.invalid = int(r.invalid)
+    return res
 
 
 _lib = None
@@ -237,6 +283,9 @@ def load_library(path=None):
             "iris_template_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_report": ([P, P, u64, u64, u64, ctypes.POINTER(Report)], ctypes.c_int),
+            "iris_resolver_report": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.POINTER(Report)],
+                                     ctypes.c_int),
+            "iris_resolver_report_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.POINTER(Report)], ctypes.c_int),
             "iris_resolver_histogram": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, ctypes.c_uint32, P, P],
                                         ctypes.c_int),
             "iris_resolver_histogram_masks": ([P, P, u64, u64, P, ctypes.c_uint32, ctypes.c_uint32, P, P], ctypes.c_int),
@@ -318,7 +367,7 @@ def exported_symbols():
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
         "iris_template_histogram", "iris_template_batch_histogram",
         "iris_resolver_histogram", "iris_resolver_histogram_masks", "iris_resolver_batch_histogram_masks",
-        "iris_template_report",
+        "iris_template_report", "iris_resolver_report", "iris_resolver_report_masks",
     ]
 
 
@@ -1104,6 +1153,20 @@ class MasksEngine(_Engine):
                                                             _ptr(bins), ctypes.addressof(invalid)))
         return bins, int(invalid.value)
 
+    def report(self, db, share_ptrs, threshold=None, cap=None, k=None, nbins=None, first=0, n=None, index_base=0):
+        """Several of matches(), topk() and histogram() of the resolver step from ONE masks pass
+        (iris_resolver_report_masks; no reference counterpart) -> ReportResult, shaped like
+        TemplateEngine.report: `threshold` (with `cap`) asks for .matches and .matches_count, `k` for
+        .topk, `nbins` for .bins and .invalid; each is exactly what the sibling method returns.
+        share_ptrs are the participants' device arrays of n*31 u16."""
+        n = (len(db) - int(first)) if n is None else n
+        ptrs = [int(p) for p in share_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        f = load_library().iris_resolver_report_masks
+        return _report(lambda r: f(self.handle, db.handle, int(first), int(n), arr, len(ptrs), int(index_base), r), self,
+                       threshold, cap, k, nbins,
+                       lambda count: self.matches(db, ptrs, threshold, first, n, index_base, cap=count)[0])
+
 
 class DistanceEngine(_Engine):
     """DistanceEngine (src/lib.rs:28-53): out[k] = dot_u16(rot(query, k-15), entry)."""
@@ -1235,45 +1298,9 @@ class TemplateEngine(_Engine):
         .invalid; each is exactly what the sibling method returns, the others stay None.  At least
         one part must be asked for."""
         n = (len(db) - first) if n is None else n
-        r = Report()
-        res = ReportResult()
-        keep = []  # the arrays the struct points at
-        want_all = False
-        if threshold is not None:
-            r.parts |= REPORT_MATCHES
-            r.threshold = float(threshold)
-            want_all = cap is None
-            room = max(1024, getattr(self, "_match_room", 0)) if want_all else int(cap)
-            r.matches_cap = room
-            if room:
-                keep.append((Match * room)())
-                r.matches = keep[-1]
-        if k is not None:
-            r.parts |= REPORT_TOPK
-            r.k = int(k)
-            keep.append((Match * (max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1))())
-            r.topk = keep[-1]
-        if nbins is not None:
-            nb = int(nbins)
-            r.parts |= REPORT_HIST
-            r.nbins = nb
-            res.bins = np.zeros(nb if 0 < nb <= HIST_MAX_BINS else 1, np.uint64)
-            r.bins = res.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-        _check(load_library().iris_template_report(self.handle, db.handle, int(first), int(n), int(index_base),
-                                                   ctypes.byref(r)))
-        if threshold is not None:
-            res.matches_count = int(r.matches_count)
-            if want_all and res.matches_count > r.matches_cap:  # the rest of a longer list: the sibling's pass
-                res.matches, _ = self.matches(db, threshold, first, n, index_base, cap=res.matches_count)
-            else:
-                res.matches = [_copy_match(r.matches[i]) for i in range(min(res.matches_count, r.matches_cap))]
-            if want_all:
-                self._match_room = min(res.matches_count + res.matches_count // 4, 1 << 22)
-        if k is not None:
-            res.topk = [_copy_match(r.topk[i]) for i in range(r.topk_count)]
-        if nbins is not None:
-            res.invalid = int(r.invalid)
-        return res
+        f = load_library().iris_template_report
+        return _report(lambda r: f(self.handle, db.handle, int(first), int(n), int(index_base), r), self, threshold, cap, k, nbins,
+                       lambda count: self.matches(db, threshold, first, n, index_base, cap=count)[0])
 
     def topk_async(self, db, k, first=0, n=None, index_base=0):
         """Enqueue topk() and return at once (iris_template_topk_async) -> PendingTopk, whose
@@ -1878,6 +1905,18 @@ def resolver_histogram(device, share_ptrs, denoms_ptr, n, nbins):
     return bins, int(invalid.value)
 
 
+def resolver_report(device, share_ptrs, denoms_ptr, n, threshold=None, cap=None, k=None, nbins=None, index_base=0):
+    """Several of resolver_matches(), resolver_topk() and resolver_histogram() from ONE read of the
+    share rows (iris_resolver_report; device arrays of n*31 u16) -> ReportResult, shaped like
+    TemplateEngine.report: a part is asked for by its argument and is exactly what the sibling
+    function returns."""
+    ptrs = (ctypes.c_void_p * max(len(share_ptrs), 1))(*share_ptrs)
+    f = load_library().iris_resolver_report
+    return _report(lambda r: f(device.handle, ptrs, len(share_ptrs), ctypes.c_void_p(denoms_ptr), int(n), int(index_base), r),
+                   device, threshold, cap, k, nbins,
+                   lambda count: resolver_matches(device, share_ptrs, denoms_ptr, n, threshold, index_base, cap=count)[0])
+
+
 # ====================================================================== arch plugin
 
 
@@ -1915,7 +1954,7 @@ def f64_bits(x):
 
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
-    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "TOPK_MAX", "HIST_MAX_BINS", "Report", "ReportResult", "REPORT_MATCHES", "REPORT_TOPK", "REPORT_HIST", "dot_bool", "dot_u16",
+    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "resolver_report", "TOPK_MAX", "HIST_MAX_BINS", "Report", "ReportResult", "REPORT_MATCHES", "REPORT_TOPK", "REPORT_HIST", "dot_bool", "dot_u16",
     "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
