@@ -124,6 +124,25 @@ pub struct IrisReport {
     pub invalid: u64,
 }
 
+/// `iris_batch_report_t`: the arguments of `iris_template_batch_report`; the results go to its
+/// per-query arrays (no implicit padding).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct IrisBatchReport {
+    pub parts: u32,
+    pub k: u32,
+    pub nbins: u32,
+    pub reserved: u32,
+    pub threshold: f64,
+    pub matches: *mut IrisMatch,
+    pub matches_cap: u64,
+    pub matches_counts: *mut u64,
+    pub topk: *mut IrisMatch,
+    pub topk_counts: *mut u32,
+    pub bins: *mut u64,
+    pub invalid: *mut u64,
+}
+
 extern "C" {
     // errors
     pub fn iris_last_error() -> *const c_char;
@@ -506,6 +525,16 @@ extern "C" {
         n: u64,
         shares_device: *const *const u16,
         parts: u32,
+        index_base: u64,
+        report: *mut c_void,
+    ) -> c_int;
+    // template batch reports: several of batch matches / topk / histogram of every probe from one
+    // GEMM pass; `report` points at an IrisBatchReport (the header declares it void *)
+    pub fn iris_template_batch_report(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
         index_base: u64,
         report: *mut c_void,
     ) -> c_int;

@@ -779,7 +779,8 @@ int iris_template_batch_histogram(iris_engine_t *engine, const iris_db_t *db, ui
  * iris_template_matches does (never with matches_cap == 0).
  *
  * Out of scope: the pipelined forms (a report pass neither hosts nor is hosted in the sharing ring);
- * template batch and masks batch engines; host-array forms and
+ * template batch engines here (iris_template_batch_report, section "template batch reports" below,
+ * is their call) and masks batch engines; host-array forms and
  * device groups; more than one threshold, k or histogram per call; a search part -- topk[0] at
  * k = 1 is the search's result.  The resolver forms, iris_resolver_report and
  * iris_resolver_report_masks, take this struct and these bits: section "resolver reports" below. */
@@ -882,7 +883,8 @@ int iris_resolver_batch_histogram_masks(iris_engine_t *engine, const iris_db_t *
  *
  * Out of scope: the masks batch engine (an iris_resolver_batch_report_masks needs per-slot sinks
  * and a per-group overflow rerun, at the register ceiling of the batch kernel's resolving form: the
- * next follow-up); host-array forms (*_host); pipelined forms; device groups; more than one
+ * next follow-up; the template batch engine has its report, iris_template_batch_report, section
+ * "template batch reports" below); host-array forms (*_host); pipelined forms; device groups; more than one
  * threshold, k or histogram per call; a search part -- topk[0] at k = 1 is the search's result. */
 /* iris_resolver_search's sibling: denominators given */
 int iris_resolver_report(iris_device_t *dev, const uint16_t *const *shares_device, uint32_t parts,
@@ -892,6 +894,61 @@ int iris_resolver_report(iris_device_t *dev, const uint16_t *const *shares_devic
 int iris_resolver_report_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
                                const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
                                void *report /* iris_report_t * */);
+
+/* -------------------------------------------------- template batch reports
+ * The combined pass of a template batch engine: every probe's match list, k closest records and
+ * distance histogram from ONE GEMM pass over the range.  A deduplication run asks all three for
+ * each of its probes, and each sibling batch call is a full GEMM that is bound by MFMA issue and
+ * operand expansion, not by what happens to a record's best rotation at the end; a batch report
+ * computes the best rotation once per (probe, record) and feeds every selected sink.
+ *
+ * report->parts selects the parts, the IRIS_REPORT_* bits of "combined passes": at least one, no
+ * others, and reserved is 0 (IRIS_E_ARG).  One threshold, cap, k and bin count serve all nq queries
+ * of the engine.  The whole semantics: EACH SELECTED PART IS BYTE FOR BYTE WHAT ITS SIBLING CALL
+ * WRITES for the same engine, database, range, index_base and arguments --
+ *   MATCHES  matches [nq][matches_cap] and matches_counts [nq] are iris_template_batch_matches' out
+ *            and counts for (threshold, cap);
+ *   TOPK     topk [nq][k] and topk_counts [nq] are iris_template_batch_topk's out and counts for k;
+ *   HIST     bins [nq][nbins] and invalid [nq] are iris_template_batch_histogram's for nbins
+ * -- and so, by those calls' contracts, what the single-query calls (and iris_template_report)
+ * return per query.  Entries past a count stay untouched.  The fields and arrays of a part that is
+ * not selected are neither read nor written.
+ *
+ * Refusals: the value arguments are checked before the handles -- parts and reserved, then each
+ * selected part's own arguments under its sibling's rules, the per-query count arrays required --
+ * then the engine, the database and the range as in the siblings: a batched template engine; more
+ * than 3 queries need a TILES database.  A refused or failed call writes nothing: nothing is
+ * written before every selected part has succeeded (an engine of up to 3 queries: the counts and
+ * the invalid words not before every query has, a query's lists and bins not before every selected
+ * part of that query has).  n == 0: the counts and the bins are zero, and nothing is launched.
+ *
+ * One part selected runs that sibling batch call.  Engines of up to 3 queries run one single-query
+ * report per query (either layout), waiting once per query.  Otherwise two or three parts run one
+ * GEMM pass for all queries, followed on the stream by the top-k merge levels of all queries, and
+ * the call waits once; a query whose match list overflows the room of the first pass has its
+ * aligned block of 4 queries run once more as iris_template_batch_matches' pass (never with
+ * matches_cap == 0).
+ *
+ * Out of scope: the masks batch engine (the next follow-up); pipelined, host-array and
+ * device-group forms; per-query thresholds, k or bin counts; a search part -- topk[q][0] at k = 1
+ * is query q's search result. */
+typedef struct iris_batch_report {
+    uint32_t parts;            /* in: IRIS_REPORT_* bits, at least one, no others */
+    uint32_t k;                /* in, TOPK: 1..IRIS_TOPK_MAX */
+    uint32_t nbins;            /* in, HIST: a power of two, 1..IRIS_HIST_MAX_BINS */
+    uint32_t reserved;         /* in: 0 */
+    double threshold;          /* in, MATCHES: not NaN */
+    iris_match_t *matches;     /* in, MATCHES: [nq][matches_cap], may be NULL when the cap is 0 */
+    uint64_t matches_cap;      /* in, MATCHES */
+    uint64_t *matches_counts;  /* in, MATCHES: [nq], written: the exact totals */
+    iris_match_t *topk;        /* in, TOPK: [nq][k] */
+    uint32_t *topk_counts;     /* in, TOPK: [nq], written */
+    uint64_t *bins;            /* in, HIST: [nq][nbins] */
+    uint64_t *invalid;         /* in, HIST: [nq] */
+} iris_batch_report_t;
+/* report: the caller's iris_batch_report_t; it crosses as void *, as iris_template_report's does */
+int iris_template_batch_report(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                               uint64_t index_base, void *report /* iris_batch_report_t * */);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

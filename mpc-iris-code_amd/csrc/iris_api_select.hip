@@ -3,7 +3,8 @@
 // the single-query template match and top-k (their handles live by iris_pending.hpp; here is only
 // what a match or a top-k handle adds), the distance histograms of the template engines and of
 // the resolver forms, and the combined pass that answers a match, a top-k and a histogram call of
-// one probe from one read (iris_template_report, iris_resolver_report, iris_resolver_report_masks).
+// one probe from one read (iris_template_report, iris_resolver_report, iris_resolver_report_masks),
+// and of every probe of a template batch engine from one GEMM pass (iris_template_batch_report).
 // Calls, locking and errors: see iris_api.hip.
 #include <string.h>
 
@@ -119,6 +120,16 @@ struct MatchWhole {
     std::function<int(const MatchSink *)> launch;
 };
 
+// What a combined pass adds to a threshold-match call whose first pass it rides on
+// (iris_template_batch_report): the device's buffers are shared by region, and the other parts'
+// work stands around the one wait.
+struct MatchRider {
+    size_t lists_bytes;             // of d->matches ahead of the queries' match regions (the top-k lists)
+    size_t count_bytes;             // of d->match_count behind the counters (the histogram rows), zeroed with them
+    std::function<int()> enqueue;   // on the stream behind the first pass: the merge levels, the rows' copy
+    std::function<int()> taken;     // after the wait, before a rerun: their results off the pinned result, checked
+};
+
 // One threshold-match call of nq queries over n records each.  Every query has a counter of its
 // own (all zeroed on the stream before the first launch) and a region of `room` records of the
 // device's match buffer; the first pass -- `whole`, or else every unit's -- is enqueued before the
@@ -131,14 +142,21 @@ struct MatchWhole {
 // single-query calls): a buffer an earlier call grew is used in full by the first pass.  budget
 // (0: none): the bytes all first-pass regions may take together, while a query keeps room for
 // kMatchFirstRoom records -- a large cap times many queries asks for no more.
+// ride (a combined pass, MatchRider): the match regions stand behind the lists; a buffer an earlier
+// call grew is used in full behind them, nq equal regions; when a list overflows, the buffer grows
+// once -- the lists' bytes and, where the budget allows, nq regions of the longest list -- so the
+// next identical call is one pass; and the lists are held back until every unit has succeeded, so a
+// failed call has written nothing (a second host copy of what the call returns: at most nq x cap records).
 static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double threshold, iris_match_t *out, uint64_t cap,
                              uint64_t *counts, uint32_t nq, bool reuse_grown, const std::vector<MatchUnit> &units,
-                             const MatchWhole *whole = nullptr, uint64_t budget = 0) {
+                             const MatchWhole *whole = nullptr, uint64_t budget = 0, const MatchRider *ride = nullptr) {
+    const size_t lists_bytes = ride ? ride->lists_bytes : 0;
     for (uint32_t q = 0; q < nq; ++q) counts[q] = 0;
     if (n == 0) return 0;
     uint32_t nc = whole ? std::max(nq, whole->nqp) : nq;  // counters and first-pass sinks
     for (const MatchUnit &u : units) nc = std::max(nc, u.q0 + u.m + u.pad);
-    CHK(ensure(d, d->match_count, nc * sizeof(uint64_t)));
+    const size_t count_bytes = nc * sizeof(uint64_t) + (ride ? ride->count_bytes : 0);
+    CHK(ensure(d, d->match_count, count_bytes));
     CHK(ensure_host_result(d, nq * sizeof(uint64_t)));
     uint64_t room = 0;
     if (cap) {
@@ -146,32 +164,39 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
         if (budget) want = std::min<uint64_t>(want, budget / (sizeof(Partial) * nq));
         room = std::min<uint64_t>(n, std::max<uint64_t>(want, kMatchFirstRoom));
         if (reuse_grown) room = std::max<uint64_t>(room, std::min<uint64_t>(n, d->matches.cap / sizeof(Partial)));
+        if (ride && d->matches.cap > lists_bytes)  // never more than fits behind the lists
+            room = std::max<uint64_t>(room, std::min<uint64_t>(n, (d->matches.cap - lists_bytes) / (sizeof(Partial) * nq)));
     }
-    CHK(ensure(d, d->matches, nq * room * sizeof(Partial)));
+    CHK(ensure(d, d->matches, lists_bytes + nq * room * sizeof(Partial)));
     uint64_t *cnt = (uint64_t *)d->match_count.p;
-    HIPCHK(hipMemsetAsync(cnt, 0, nc * sizeof(uint64_t), d->stream));
+    Partial *regions = (Partial *)((char *)d->matches.p + lists_bytes);
+    HIPCHK(hipMemsetAsync(cnt, 0, count_bytes, d->stream));
     std::vector<MatchSink> sinks;  // by query; a unit's own during its rerun
-    std::vector<uint64_t> total, off;
+    std::vector<uint64_t> total, off, held_at;
+    std::vector<iris_match_t> held;  // ride: the lists until every unit has succeeded
     try {
         sinks.resize(nc);
         total.resize(nq);
+        if (ride) held_at.resize(nq);
         off.reserve(kMasksBatchG + 1);
     } catch (const std::bad_alloc &) {
         return fail(IRIS_E_NOMEM, "out of host memory");
     }
     for (uint32_t q = 0; q < nc; ++q)
-        sinks[q] = q < nq ? MatchSink{(Partial *)d->matches.p + q * room, room, cnt + q, threshold}
+        sinks[q] = q < nq ? MatchSink{regions + q * room, room, cnt + q, threshold}
                           : MatchSink{nullptr, 0, cnt + q, threshold};
     if (whole) {
         CHK(whole->launch(sinks.data()));
     } else {
         for (const MatchUnit &u : units) CHK(u.launch(sinks.data() + u.q0));
     }
+    if (ride) CHK(ride->enqueue());
     HIPCHK(hipMemcpyAsync(d->host_result, cnt, nq * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
     CHK(sync(d));
     memcpy(total.data(), d->host_result, nq * sizeof(uint64_t));
     for (uint32_t q = 0; q < nq; ++q)
         if (total[q] > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+    if (ride) CHK(ride->taken());
     // query q's total[q] records at src -> counts[q] and its list
     std::vector<Partial> recs;
     auto finish = [&](uint32_t q, const Partial *src) -> int {
@@ -180,12 +205,16 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
         if (take == 0) return 0;
         try {
             recs.resize(total[q]);
+            if (ride) {
+                held_at[q] = held.size();
+                held.resize(held.size() + take);
+            }
         } catch (const std::bad_alloc &) {
             return fail(IRIS_E_NOMEM, "out of host memory");
         }
         HIPCHK(hipMemcpyAsync(recs.data(), src, total[q] * sizeof(Partial), hipMemcpyDeviceToHost, d->stream));
         CHK(sync(d));
-        match_list(recs.data(), total[q], take, base, out + q * cap);
+        match_list(recs.data(), total[q], take, base, ride ? held.data() + held_at[q] : out + q * cap);
         return 0;
     };
     auto overflows = [&](const MatchUnit &u) {
@@ -196,13 +225,18 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
     // the units whose lists fit first: a rerun below may replace the buffer their records are in
     for (const MatchUnit &u : units) {
         if (overflows(u)) continue;
-        for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + (u.q0 + s) * room));
+        for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, regions + (u.q0 + s) * room));
+    }
+    if (ride && cap) {  // the first-pass room of the next identical call
+        const uint64_t longest = *std::max_element(total.begin(), total.end());
+        const uint64_t all = (uint64_t)nq * longest * sizeof(Partial);
+        if (longest > room && (!budget || all <= budget)) CHK(ensure(d, d->matches, lists_bytes + all));
     }
     for (const MatchUnit &u : units) {
         if (!overflows(u)) continue;
         off.assign(u.m + 1, 0);
         for (uint32_t s = 0; s < u.m; ++s) off[s + 1] = off[s] + total[u.q0 + s];
-        CHK(ensure(d, d->matches, off[u.m] * sizeof(Partial)));
+        CHK(ensure(d, d->matches, lists_bytes + off[u.m] * sizeof(Partial)));
         for (uint32_t s = 0; s < u.m + u.pad; ++s)
             sinks[s] = s < u.m ? MatchSink{(Partial *)d->matches.p + off[s], total[u.q0 + s], cnt + u.q0 + s, threshold}
                                : MatchSink{nullptr, 0, cnt + u.q0 + s, threshold};
@@ -214,6 +248,9 @@ static int matches_run_units(iris_device *d, uint64_t n, uint64_t base, double t
             return fail(IRIS_E_HIP, "match pass counts differ between two runs");
         for (uint32_t s = 0; s < u.m; ++s) CHK(finish(u.q0 + s, (const Partial *)d->matches.p + off[s]));
     }
+    for (uint32_t q = 0; ride && q < nq; ++q)
+        if (const uint64_t take = std::min(total[q], cap))
+            memcpy(out + q * cap, held.data() + held_at[q], take * sizeof(iris_match_t));
     return 0;
 }
 
@@ -553,6 +590,30 @@ struct TopkUnit {
 // A merge launch takes at most this many queries (blockIdx.y, launch_topk_merge_level)
 constexpr uint32_t kTopkMergeSlots = 65535;
 
+// The merge levels of m queries whose `lists` lists of k records each stand `stride` records apart
+// from `region` on (the spare lists behind each query's own), on the stream: one launch per level
+// for the queries together (launch_topk_merge_level; more than kTopkMergeSlots queries: one launch
+// per kTopkMergeSlots of them).  The last level writes query s's k records at res + s * k.
+static int topk_merge_enqueue(iris_device *d, Partial *region, uint64_t lists, uint64_t stride, uint32_t k, uint32_t m,
+                              Partial *res) {
+    Partial *src = region, *dst = region + lists * k;
+    for (uint64_t left = lists;;) {
+        const uint64_t groups = topk_spare_lists(left);
+        const bool last = groups == 1;
+        for (uint32_t s0 = 0; s0 < m; s0 += kTopkMergeSlots) {
+            const uint32_t slots = std::min(kTopkMergeSlots, m - s0);
+            CHK(timed(d, "topk_merge", left * slots, [&] {
+                return launch_topk_merge_level(d->stream, src + s0 * stride, left, k,
+                                               last ? res + (size_t)s0 * k : dst + s0 * stride, slots, stride,
+                                               last ? k : stride);
+            }));
+        }
+        if (last) return 0;
+        left = groups;
+        std::swap(src, dst);
+    }
+}
+
 // topk_run for the nq queries of a batch engine.  One lists region of the device's match buffer
 // -- per query of a unit its lists and then the merge's spare lists, (lists + spare) * k records
 // -- serves every unit in stream order: a unit's merge has consumed the
@@ -573,22 +634,7 @@ static int topk_run_units(iris_device *d, uint64_t n, uint64_t base, uint32_t k,
     for (const TopkUnit &u : units) {
         const uint64_t stride = (u.lists + topk_spare_lists(u.lists)) * k;
         CHK(u.launch(region, stride));
-        Partial *src = region, *dst = region + u.lists * k;
-        for (uint64_t left = u.lists;;) {
-            const uint64_t groups = topk_spare_lists(left);
-            const bool last = groups == 1;
-            for (uint32_t s0 = 0; s0 < u.m; s0 += kTopkMergeSlots) {
-                const uint32_t slots = std::min(kTopkMergeSlots, u.m - s0);
-                CHK(timed(d, "topk_merge", left * slots, [&] {
-                    return launch_topk_merge_level(d->stream, src + s0 * stride, left, k,
-                                                   last ? res + ((size_t)u.q0 + s0) * k : dst + s0 * stride, slots, stride,
-                                                   last ? k : stride);
-                }));
-            }
-            if (last) break;
-            left = groups;
-            std::swap(src, dst);
-        }
+        CHK(topk_merge_enqueue(d, region, u.lists, stride, k, u.m, res + (size_t)u.q0 * k));
     }
     CHK(sync(d));
     for (uint32_t q = 0; q < nq; ++q) counts[q] = topk_list(res + (size_t)q * k, k, base, out + (size_t)q * k);
@@ -682,6 +728,47 @@ int iris_resolver_batch_matches_masks(iris_engine_t *e, const iris_db_t *db, uin
 // cap x 1024 records.
 constexpr uint64_t kBatchMatchBudget = 256ull << 20;
 
+// The GEMM's match passes (iris_template_batch_matches, and the reruns of iris_template_batch_report).
+// The sinks cross to the device from pinned memory, so the copy is a plain asynchronous one on the
+// stream: the device's pinned result words past the nq counts the call reads back.  The caller has
+// ensured d->match_sinks (batch_padded(nq) sinks) and the pinned result up to the staged sinks' end.
+static uint32_t batch_padded(uint32_t nq) {  // the engine's padded queries (zero tiles)
+    const uint32_t bq = batch_query_group();
+    return (nq + bq - 1) / bq * bq;
+}
+static size_t batch_stage_off(uint32_t nq) { return (nq * sizeof(uint64_t) + 63) / 64 * 64; }
+// the sinks of queries q0 .. q0 + m - 1 and of the padding queries that fill their last block
+// (host) -> their places in the device array; every pass but the first follows a wait, so the
+// staged sinks are never overwritten in flight
+static int batch_sinks_stage(iris_device *d, uint32_t nq, uint32_t q0, uint32_t m, const MatchSink *ms) {
+    const uint32_t mp = batch_padded(m);
+    MatchSink *stage = (MatchSink *)((char *)d->host_result + batch_stage_off(nq)) + q0;
+    memcpy(stage, ms, mp * sizeof(MatchSink));
+    HIPCHK(hipMemcpyAsync((MatchSink *)d->match_sinks.p + q0, stage, mp * sizeof(MatchSink), hipMemcpyHostToDevice, d->stream));
+    return 0;
+}
+// those sinks staged, then the match pass over those queries' tiles
+static int batch_match_pass(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r, uint32_t q0, uint32_t m,
+                            const MatchSink *ms) {
+    const size_t tile_bytes = (size_t)16 * kPlaneGroups * 64;
+    CHK(batch_sinks_stage(d, e->nq, q0, m, ms));
+    const BatchGeometry geo = batch_geometry(d->hooks, r, m);
+    return timed(d, "template_batch_match", r.n * m, [&] {
+        return launch_batch(Pass::Match, d->hooks, d->stream, db->data, (const char *)e->qfrag + q0 * tile_bytes, r, geo,
+                            (const MatchSink *)d->match_sinks.p + q0);
+    });
+}
+// what runs again when a list overflows: the aligned blocks of batch_query_group() queries
+static std::vector<MatchUnit> batch_match_units(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r) {
+    const uint32_t bq = batch_query_group(), nq = e->nq;
+    std::vector<MatchUnit> units;
+    for (uint32_t q0 = 0; q0 < nq; q0 += bq) {
+        const uint32_t m = std::min(bq, nq - q0);
+        units.push_back(MatchUnit{q0, m, [=](const MatchSink *ms) { return batch_match_pass(d, e, db, r, q0, m, ms); }, bq - m});
+    }
+    return units;
+}
+
 // iris_template_batch_search's threshold sibling, and that call's checks and dispatch.  Engines of
 // up to kBatchStreamMax queries: one single-query match pass per query ("template_match"), all
 // enqueued before the one wait.  The GEMM: one launch of batch_lds_kernel<..., BL_MATCH>
@@ -710,36 +797,13 @@ int iris_template_batch_matches(iris_engine_t *e, const iris_db_t *db, uint64_t 
         }
         return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, nullptr, kBatchMatchBudget);
     }
-    const uint32_t bq = batch_query_group();
-    const uint32_t nqp = (nq + bq - 1) / bq * bq;  // the engine's padded queries (zero tiles)
-    const size_t tile_bytes = (size_t)16 * kPlaneGroups * 64;
-    // the sinks cross to the device from pinned memory, so the copy is a plain asynchronous one on
-    // the stream: the device's pinned result words past the nq counts the call reads back
-    const size_t stage_off = (nq * sizeof(uint64_t) + 63) / 64 * 64;
+    const uint32_t nqp = batch_padded(nq);
     if (n) {
         CHK(ensure(d, d->match_sinks, nqp * sizeof(MatchSink)));
-        CHK(ensure_host_result(d, stage_off + nqp * sizeof(MatchSink)));
+        CHK(ensure_host_result(d, batch_stage_off(nq) + nqp * sizeof(MatchSink)));
+        units = batch_match_units(d, e, db, r);
     }
-    const MatchSink *dsinks = (const MatchSink *)d->match_sinks.p;
-    // the sinks of queries q0 .. q0 + m - 1 and of the padding queries that fill their last block
-    // (host) -> their places in the device array, then the pass over those queries' tiles; every
-    // pass but the first follows a wait, so the staged sinks are never overwritten in flight
-    auto pass = [=](uint32_t q0, uint32_t m, const MatchSink *ms) -> int {
-        const uint32_t mp = (m + bq - 1) / bq * bq;
-        MatchSink *stage = (MatchSink *)((char *)d->host_result + stage_off) + q0;
-        memcpy(stage, ms, mp * sizeof(MatchSink));
-        HIPCHK(hipMemcpyAsync((void *)(dsinks + q0), stage, mp * sizeof(MatchSink), hipMemcpyHostToDevice, d->stream));
-        const BatchGeometry geo = batch_geometry(d->hooks, r, m);
-        return timed(d, "template_batch_match", n * m, [&] {
-            return launch_batch(Pass::Match, d->hooks, d->stream, db->data, (const char *)e->qfrag + q0 * tile_bytes, r, geo,
-                                dsinks + q0);
-        });
-    };
-    for (uint32_t q0 = 0; n && q0 < nq; q0 += bq) {
-        const uint32_t m = std::min(bq, nq - q0);
-        units.push_back(MatchUnit{q0, m, [=](const MatchSink *ms) { return pass(q0, m, ms); }, bq - m});
-    }
-    const MatchWhole whole{nqp, [=](const MatchSink *ms) { return pass(0, nq, ms); }};
+    const MatchWhole whole{nqp, [=](const MatchSink *ms) { return batch_match_pass(d, e, db, r, 0, nq, ms); }};
     return matches_run_units(d, n, base, threshold, out, cap, counts, nq, false, units, &whole, kBatchMatchBudget);
 }
 
@@ -796,20 +860,33 @@ static int hist_args(uint32_t nbins, const uint64_t *bins, const uint64_t *inval
     return 0;
 }
 
-// The nq rows of nbins + 1 counters in the pinned host result (bins, then the invalid count) ->
-// the caller's arrays, once every row adds up to the range: nothing is written before that.
-static int hist_finish(iris_device *d, uint64_t n, uint32_t nbins, uint32_t nq, uint64_t *bins, uint64_t *invalid) {
-    const uint64_t *res = (const uint64_t *)d->host_result;
+// Whether each of the nq rows of nbins + 1 counters at res adds up to the range.
+static int hist_rows_check(const uint64_t *res, uint64_t n, uint32_t nbins, uint32_t nq) {
     const size_t words = (size_t)nbins + 1;
     for (uint32_t q = 0; q < nq; ++q) {
         uint64_t sum = 0;
         for (size_t i = 0; i < words; ++i) sum += res[q * words + i];
         if (sum != n) return fail(IRIS_E_HIP, "histogram pass did not count every record of the range once");
     }
+    return 0;
+}
+
+// checked rows -> the caller's arrays
+static void hist_rows_write(const uint64_t *res, uint32_t nbins, uint32_t nq, uint64_t *bins, uint64_t *invalid) {
+    const size_t words = (size_t)nbins + 1;
     for (uint32_t q = 0; q < nq; ++q) {
         memcpy(bins + (size_t)q * nbins, res + q * words, nbins * sizeof(uint64_t));
         invalid[q] = res[q * words + nbins];
     }
+}
+
+// The nq rows of nbins + 1 counters at res (bins, then the invalid count; null: the pinned host
+// result) -> the caller's arrays, once every row adds up to the range: nothing is written before that.
+static int hist_finish(iris_device *d, uint64_t n, uint32_t nbins, uint32_t nq, uint64_t *bins, uint64_t *invalid,
+                       const uint64_t *res = nullptr) {
+    if (!res) res = (const uint64_t *)d->host_result;
+    CHK(hist_rows_check(res, n, nbins, nq));
+    hist_rows_write(res, nbins, nq, bins, invalid);
     return 0;
 }
 
@@ -1214,6 +1291,165 @@ int iris_resolver_report_masks(iris_engine_t *e, const iris_db_t *db, uint64_t f
     return report_dispatch(d, n, index_base, rep, {units, [&](Pass p, const MatchSink &s) {
         return masks_single_launch(d, e, db, r, shares_device, parts, p, s, &den);
     }});
+}
+
+// ------------------------------------------------------------------ template batch reports
+
+static int batch_report_args(const iris_batch_report_t *rep) {
+    ARG(rep, "report is NULL");
+    const uint32_t all = IRIS_REPORT_MATCHES | IRIS_REPORT_TOPK | IRIS_REPORT_HIST;
+    ARG(rep->parts != 0 && (rep->parts & ~all) == 0, "parts must be one or more of IRIS_REPORT_MATCHES, _TOPK, _HIST");
+    ARG(rep->reserved == 0, "reserved must be 0");
+    if (rep->parts & IRIS_REPORT_MATCHES) CHK(matches_args(rep->threshold, rep->matches, rep->matches_cap, rep->matches_counts));
+    if (rep->parts & IRIS_REPORT_TOPK) CHK(topk_args(rep->k, rep->topk, rep->topk_counts));
+    if (rep->parts & IRIS_REPORT_HIST) CHK(hist_args(rep->nbins, rep->bins, rep->invalid));
+    return 0;
+}
+
+// Two or three parts for the queries of a GEMM engine over r (not empty) from ONE pass of
+// batch_lds_kernel<..., BL_REPORT> ("template_batch_report").  The device's buffers are shared by
+// region: d->matches holds the lists region of iris_template_batch_topk -- nqp (8 G + ceil(8 G / 64)) k
+// records -- and behind it the queries' match regions; d->match_count nqp counters and behind them
+// the histogram rows [nqp][nbins + 1], which the workgroups add into as in BL_HIST; the pinned
+// result the nq counts, the staged sinks, the merged lists [nq][k] and the nq rows, each at a
+// 64-byte boundary.  The merge levels of all queries and the rows' copy follow the pass on the
+// stream, and the call waits once.  With a matches part the call is a threshold-match call
+// (matches_run_units) whose first pass is the report pass: its room, overflow and rerun rules are
+// iris_template_batch_matches', the rerun that call's plain match pass over the block.  The merged
+// lists and the rows are taken off the pinned result before a rerun; nothing reaches the caller's
+// arrays before every part has succeeded.
+static int batch_report_run(iris_device *d, const iris_engine *e, const iris_db *db, LaunchRange r, uint64_t base,
+                            const iris_batch_report_t *rep) {
+    const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
+               want_hist = rep->parts & IRIS_REPORT_HIST;
+    const uint32_t nq = e->nq, nqp = batch_padded(nq);
+    const uint32_t k = want_topk ? rep->k : 0, nbins = want_hist ? rep->nbins : 0;
+    const BatchGeometry geo = batch_geometry(d->hooks, r, nq);
+    const uint64_t lists = want_topk ? batch_topk_units(geo) : 0, stride = (lists + topk_spare_lists(lists)) * k;
+    const size_t lists_bytes = (size_t)nqp * stride * sizeof(Partial);
+    const size_t words = (size_t)nbins + 1, rows_bytes = want_hist ? nqp * words * sizeof(uint64_t) : 0;
+    const auto line = [](size_t b) { return (b + 63) / 64 * 64; };
+    const size_t topk_off = line(batch_stage_off(nq) + nqp * sizeof(MatchSink));
+    const size_t hist_off = line(topk_off + (size_t)nq * k * sizeof(Partial));
+    CHK(ensure_host_result(d, hist_off + (want_hist ? nq * words * sizeof(uint64_t) : 0)));
+    if (want_match) CHK(ensure(d, d->match_sinks, nqp * sizeof(MatchSink)));
+    // the buffers' addresses are read when a step is enqueued: matches_run_units ensures them first
+    const auto rows_dev = [=] { return (uint64_t *)d->match_count.p + nqp; };
+    const auto report_pass = [=](const MatchSink *ms) -> int {  // ms: the nqp sinks; null without a matches part
+        if (ms) CHK(batch_sinks_stage(d, nq, 0, nq, ms));
+        return timed(d, "template_batch_report", r.n * nq, [&] {
+            return launch_batch(Pass::Report, d->hooks, d->stream, db->data, e->qfrag, r, geo,
+                                {ms ? (const MatchSink *)d->match_sinks.p : nullptr, want_topk ? (Partial *)d->matches.p : nullptr,
+                                 stride, k, want_hist ? rows_dev() : nullptr, nbins});
+        });
+    };
+    const auto enqueue = [=]() -> int {
+        char *res = (char *)d->host_result;
+        if (want_topk) CHK(topk_merge_enqueue(d, (Partial *)d->matches.p, lists, stride, k, nq, (Partial *)(res + topk_off)));
+        if (want_hist)
+            HIPCHK(hipMemcpyAsync(res + hist_off, rows_dev(), nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+        return 0;
+    };
+    std::vector<Partial> best;
+    std::vector<uint64_t> rows, mcounts;
+    const auto taken = [&]() -> int {
+        const char *res = (const char *)d->host_result;
+        try {
+            if (want_topk) best.assign((const Partial *)(res + topk_off), (const Partial *)(res + topk_off) + (size_t)nq * k);
+            if (want_hist) rows.assign((const uint64_t *)(res + hist_off), (const uint64_t *)(res + hist_off) + nq * words);
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        return want_hist ? hist_rows_check(rows.data(), r.n, nbins, nq) : 0;
+    };
+    if (want_match) {
+        try {
+            mcounts.resize(nq);
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        const MatchWhole whole{nqp, report_pass};
+        const MatchRider ride{lists_bytes, rows_bytes, enqueue, taken};
+        CHK(matches_run_units(d, r.n, base, rep->threshold, rep->matches, rep->matches_cap, mcounts.data(), nq, false,
+                              batch_match_units(d, e, db, r), &whole, kBatchMatchBudget, &ride));
+        memcpy(rep->matches_counts, mcounts.data(), nq * sizeof(uint64_t));
+    } else {
+        const size_t count_bytes = nqp * sizeof(uint64_t) + rows_bytes;
+        CHK(ensure(d, d->matches, lists_bytes));
+        CHK(ensure(d, d->match_count, count_bytes));
+        HIPCHK(hipMemsetAsync(d->match_count.p, 0, count_bytes, d->stream));
+        CHK(report_pass(nullptr));
+        CHK(enqueue());
+        CHK(sync(d));
+        CHK(taken());
+    }
+    if (want_topk)
+        for (uint32_t q = 0; q < nq; ++q)
+            rep->topk_counts[q] = topk_list(best.data() + (size_t)q * k, k, base, rep->topk + (size_t)q * k);
+    if (want_hist) hist_rows_write(rows.data(), nbins, nq, rep->bins, rep->invalid);  // checked in taken()
+    return 0;
+}
+
+// Several of iris_template_batch_matches, iris_template_batch_topk and iris_template_batch_histogram
+// for every probe of a batch engine from one pass over the range (header: "template batch reports").
+// One part: the sibling call itself.  Engines of up to kBatchStreamMax queries: one single-query
+// report per query (report_dispatch, either layout), each waiting once.  The GEMM: batch_report_run.
+int iris_template_batch_report(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                               void *report) {
+    IRIS_KEEP_DEVICE();
+    const iris_batch_report_t *const rep = (const iris_batch_report_t *)report;
+    CHK(batch_report_args(rep));  // the value arguments first: refused whatever the handles
+    CHK(template_batch_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (rep->parts == IRIS_REPORT_MATCHES)
+        return iris_template_batch_matches(e, db, first, n, index_base, rep->threshold, rep->matches, rep->matches_cap,
+                                           rep->matches_counts);
+    if (rep->parts == IRIS_REPORT_TOPK)
+        return iris_template_batch_topk(e, db, first, n, index_base, rep->k, rep->topk, rep->topk_counts);
+    if (rep->parts == IRIS_REPORT_HIST) return iris_template_batch_histogram(e, db, first, n, rep->nbins, rep->bins, rep->invalid);
+    const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
+               want_hist = rep->parts & IRIS_REPORT_HIST;
+    const uint32_t nq = e->nq;
+    if (n == 0) {  // nothing is launched
+        if (want_match) memset(rep->matches_counts, 0, nq * sizeof(uint64_t));
+        if (want_topk) memset(rep->topk_counts, 0, nq * sizeof(uint32_t));
+        if (want_hist) CHK(hist_empty(nq, rep->nbins, rep->bins, rep->invalid));
+        return 0;
+    }
+    const LaunchRange r{first, n};
+    if (e->sub.empty()) return batch_report_run(d, e, db, r, index_base + first, rep);
+    const uint64_t units = template_topk_lists(d, db, r);
+    iris_report_t ones[kBatchStreamMax] = {};
+    for (uint32_t q = 0; q < nq; ++q) {
+        const iris_engine *c = e->sub[q];
+        iris_report_t &one = ones[q];
+        one.parts = rep->parts;
+        if (want_match) {
+            one.threshold = rep->threshold;
+            one.matches_cap = rep->matches_cap;
+            one.matches = rep->matches_cap ? rep->matches + q * rep->matches_cap : nullptr;
+        }
+        if (want_topk) {
+            one.k = rep->k;
+            one.topk = rep->topk + (size_t)q * rep->k;
+        }
+        if (want_hist) {
+            one.nbins = rep->nbins;
+            one.bins = rep->bins + (size_t)q * rep->nbins;
+        }
+        CHK(report_dispatch(d, n, index_base + first, &one, {units, [&](Pass p, const MatchSink &s) {
+            return launch_template_select(d, db, c->qtab, c->qfrag, r, p, s);
+        }}));
+    }
+    for (uint32_t q = 0; q < nq; ++q) {  // the counts once every query has succeeded
+        if (want_match) rep->matches_counts[q] = ones[q].matches_count;
+        if (want_topk) rep->topk_counts[q] = ones[q].topk_count;
+        if (want_hist) rep->invalid[q] = ones[q].invalid;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -89,7 +89,18 @@ __global__ void __launch_bounds__(256) batch_reduce_kernel(const Partial *__rest
 // walk, where every wave of every workgroup -- staggered or not, with or without an N-group --
 // arrives.  A padding query's zero tile gives den = 0 in every row: its row counts the range as
 // invalid, and the host ignores it.
-enum { BL_SEARCH = 0, BL_MATCH = 1, BL_TOPK = 2, BL_HIST = 3 };
+//
+// BL_REPORT (iris_template_batch_report): two or three of the forms above from ONE walk.  outp is a
+// BatchReport, by value: the device sinks (null: no match part), the lists (lists null: no top-k
+// part) and the rows (counts null: no histogram part), so "is this part present" is a scalar test on
+// kernel arguments, the same for every wave of the grid.  At the end of an N-group best_rotation
+// runs once per (query, tile) under the other forms' `valid`, and each present part takes the
+// candidate exactly as its own form does: hist_count, then topk_insert (the candidate formed as
+// BL_TOPK forms it), as each is produced; only hit / bn / bd / br stay for the one append_matches<WT>
+// per query.  The wave's sinks are scalar-loaded there, not held across the walk.  Before and after
+// the walk: BL_HIST's zeroing, barriers and flush with a histogram part, BL_TOPK's store by every
+// wave of the grid at BL_TOPK's unit number with a top-k part.  No running best, no partials.
+enum { BL_SEARCH = 0, BL_MATCH = 1, BL_TOPK = 2, BL_HIST = 3, BL_REPORT = 4 };
 struct BatchHistRows {
     uint64_t *counts;  // [query of the launch][nbins + 1], zeroed on the stream before the launch
     uint32_t nbins;    // a power of two, 1..kHistMaxBins
@@ -98,6 +109,11 @@ struct BatchTopkLists {
     Partial *lists;   // [query of the launch][units + spare][k]
     uint64_t stride;  // records between two queries' lists
     uint32_t k;       // 1..kTopkMax
+};
+struct BatchReport {
+    const MatchSink *sinks;  // DEVICE array of one sink per padded query, as BL_MATCH's operand; null: absent
+    BatchTopkLists lists;    // lists null: absent
+    BatchHistRows hist;      // counts null: absent
 };
 template <int MODE>
 struct BatchOut {
@@ -114,6 +130,10 @@ struct BatchOut<BL_TOPK> {
 template <>
 struct BatchOut<BL_HIST> {
     typedef BatchHistRows type;
+};
+template <>
+struct BatchOut<BL_REPORT> {
+    typedef BatchReport type;
 };
 template <int NW, int WT, int WQL, int BQL, int MODE = BL_SEARCH, int GPL = 4>
 __global__ void __launch_bounds__(64 * NW, 1)
@@ -213,7 +233,7 @@ __global__ void __launch_bounds__(64 * NW, 1)
     }
     // BL_TOPK: this lane's entry of the wave's list of each of its queries (topk_insert)
     Partial list[WQL];
-    if constexpr (MODE == BL_TOPK) {
+    if constexpr (MODE == BL_TOPK || MODE == BL_REPORT) {
 #pragma unroll
         for (int qi = 0; qi < WQL; ++qi) list[qi] = partial_none();
     }
@@ -222,6 +242,14 @@ __global__ void __launch_bounds__(64 * NW, 1)
 #pragma unroll
         for (int qi = 0; qi < kBQ; ++qi) hist_zero(hist + qi * (kHistMaxBins + 1), outp.nbins);
         __syncthreads();
+    }
+    if constexpr (MODE == BL_REPORT) {
+        if (outp.hist.counts) {  // a kernel argument: every wave of the grid takes the same side
+            uint32_t *hist = hist_lds<kBQ>();
+#pragma unroll
+            for (int qi = 0; qi < kBQ; ++qi) hist_zero(hist + qi * (kHistMaxBins + 1), outp.hist.nbins);
+            __syncthreads();
+        }
     }
     v16f den[WQL][WT], sacc[WQL][WT];
     auto zero = [&] {
@@ -345,6 +373,60 @@ __global__ void __launch_bounds__(64 * NW, 1)
                 }
 #pragma unroll
                 for (int qi = 0; qi < WQL; ++qi) append_matches<WT>(sink[qi], lane, hit[qi], bn[qi], bd[qi], br[qi], idx);
+            } else if constexpr (MODE == BL_REPORT) {
+                // the match form's decision once per (query, tile), for every present part: the
+                // histogram and the list take the candidate as it is produced, the append's operands
+                // wait for the one append per query.  The sinks are scalar loads here (a wave-uniform
+                // address off a kernel argument), so nothing of them is live during the walk.
+                const bool has_match = outp.sinks != nullptr, has_topk = outp.lists.lists != nullptr,
+                           has_hist = outp.hist.counts != nullptr;
+                MatchSink sk[WQL];
+                if (has_match) {
+                    const int qs = __builtin_amdgcn_readfirstlane(w) % QW;
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) sk[qi] = outp.sinks[qg * kBQ + qs * WQL + qi];
+                } else {
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) sk[qi] = MatchSink{nullptr, 0, nullptr, 0.0};
+                }
+                bool hit[WQL][WT];
+                uint32_t bn[WQL][WT], bd[WQL][WT];
+                int br[WQL][WT];
+                uint64_t idx[WT];
+#pragma unroll
+                for (int t = 0; t < WT; ++t) {
+                    const uint64_t trel = (gi + (uint64_t)j * G) * kTilesPerGroup + tset * WT + t;
+                    const uint64_t tg = (tile0 + trel) * 32 + (lane & 31);
+                    const bool valid = live && trel < ntiles && tg >= first && tg < end;
+                    idx[t] = tg - first;
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) {
+                        best_rotation(
+                            lane,
+                            [&](int r, uint32_t &nn, uint32_t &dd) {
+                                dd = (uint32_t)den[qi][t][r];
+                                nn = (uint32_t)(((int)dd - (int)sacc[qi][t][r]) >> 1);
+                            },
+                            bn[qi][t], bd[qi][t], br[qi][t]);
+                        if (has_hist)
+                            hist_count(hist_lds<kBQ>() + (qset * WQL + qi) * (kHistMaxBins + 1), outp.hist.nbins, lane,
+                                       valid && h == 0, bn[qi][t], bd[qi][t]);
+                        if (has_topk) {
+                            Partial c;
+                            c.pad = 0;
+                            c.idx = tg - first;
+                            c.num = bn[qi][t];
+                            c.den = bd[qi][t];
+                            c.rot = br[qi][t];
+                            topk_insert(list[qi], outp.lists.k, lane, c, valid && h == 0);
+                        }
+                        hit[qi][t] = has_match && match_hit(sk[qi], valid && h == 0, bn[qi][t], bd[qi][t]);
+                    }
+                }
+                if (has_match) {
+#pragma unroll
+                    for (int qi = 0; qi < WQL; ++qi) append_matches<WT>(sk[qi], lane, hit[qi], bn[qi], bd[qi], br[qi], idx);
+                }
             } else if constexpr (MODE == BL_HIST) {
                 // the match form's decision (best_rotation, the same `valid`, half 0 counts)
 #pragma unroll
@@ -448,6 +530,24 @@ __global__ void __launch_bounds__(64 * NW, 1)
             topk_store(MatchSink{outp.lists + q * outp.stride, outp.k, nullptr, 0.0}, unit, lane, list[qi]);
         }
     }
+    if constexpr (MODE == BL_REPORT) {
+        if (outp.hist.counts) {
+            __syncthreads();  // outside the walk, behind a test on a kernel argument: every wave arrives
+#pragma unroll
+            for (int qi = 0; qi < kBQ; ++qi)
+                hist_flush(hist_lds<kBQ>() + qi * (kHistMaxBins + 1), outp.hist.nbins,
+                           outp.hist.counts + (uint64_t)(qg * kBQ + qi) * (outp.hist.nbins + 1));
+        }
+        if (outp.lists.lists) {  // every wave of the grid, at BL_TOPK's unit number
+            const uint64_t unit = (uint64_t)gi * (NW / QW) + tset;
+#pragma unroll
+            for (int qi = 0; qi < WQL; ++qi) {
+                const uint64_t q = (uint64_t)qg * kBQ + qset * WQL + qi;
+                topk_store(MatchSink{outp.lists.lists + q * outp.lists.stride, outp.lists.k, nullptr, 0.0}, unit, lane,
+                           list[qi]);
+            }
+        }
+    }
     if constexpr (MODE == BL_SEARCH) {
         // the lanes' running bests -> one Partial per query (lane qi holds query qi's): exact
         // fraction, then the lowest index, then the lowest rotation (the two halves of a
@@ -512,7 +612,7 @@ BatchGeometry batch_geometry(const Hooks &h, LaunchRange r, uint32_t nq) {
 uint64_t batch_topk_units(const BatchGeometry &g) { return (uint64_t)g.G * 8; }
 
 // The one launch of batch_lds_kernel: `out` is the mode's operand (the partials, the device sinks,
-// BatchTopkLists or BatchHistRows), the shape IRIS_BATCH_KERNEL's.
+// BatchTopkLists, BatchHistRows or BatchReport), the shape IRIS_BATCH_KERNEL's.
 template <int MODE>
 static int batch_pass(const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
                       const BatchGeometry &g, typename BatchOut<MODE>::type out) {
@@ -538,6 +638,12 @@ int launch_batch(Pass p, const Hooks &h, void *stream, const void *db, const voi
     case Pass::Hist:
         if (o.nbins == 0 || o.nbins > kHistMaxBins || (o.nbins & (o.nbins - 1))) return -1;
         return batch_pass<BL_HIST>(h, stream, db, qtiles, r, g, BatchHistRows{o.counts, o.nbins});
+    case Pass::Report:
+        if (!o.sinks && !o.lists && !o.counts) return -1;
+        if (o.lists && (o.k == 0 || o.k > kTopkMax || o.stride < batch_topk_units(g) * o.k)) return -1;
+        if (o.counts && (o.nbins == 0 || o.nbins > kHistMaxBins || (o.nbins & (o.nbins - 1)))) return -1;
+        return batch_pass<BL_REPORT>(h, stream, db, qtiles, r, g,
+                                     BatchReport{o.sinks, BatchTopkLists{o.lists, o.stride, o.k}, BatchHistRows{o.counts, o.nbins}});
     default: return -1;
     }
 }

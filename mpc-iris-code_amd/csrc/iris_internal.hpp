@@ -494,6 +494,9 @@ struct BatchPassOut {
     BatchPassOut(const MatchSink *device_sinks) : sinks(device_sinks) {}
     BatchPassOut(Partial *l, uint64_t s, uint32_t kk) : lists(l), stride(s), k(kk) {}
     BatchPassOut(uint64_t *c, uint32_t bins) : counts(c), nbins(bins) {}
+    // Report: the operands of the parts present, as above; an absent part's pointer (sinks, lists, counts) is null
+    BatchPassOut(const MatchSink *device_sinks, Partial *l, uint64_t s, uint32_t kk, uint64_t *c, uint32_t bins)
+        : sinks(device_sinks), lists(l), stride(s), k(kk), counts(c), nbins(bins) {}
 };
 int launch_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *qtiles, LaunchRange r,
                  const BatchGeometry &g, const BatchPassOut &o);

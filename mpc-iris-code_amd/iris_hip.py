@@ -112,6 +112,32 @@ class ReportResult:
                 f"bins={None if self.bins is None else len(self.bins)}, invalid={self.invalid})")
 
 
+class BatchReport(ctypes.Structure):
+    """iris_batch_report_t: the arguments of iris_template_batch_report (the results go to its arrays)."""
+
+    _fields_ = [("parts", ctypes.c_uint32), ("k", ctypes.c_uint32), ("nbins", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("threshold", ctypes.c_double),
+                ("matches", ctypes.POINTER(Match)), ("matches_cap", ctypes.c_uint64),
+                ("matches_counts", ctypes.POINTER(ctypes.c_uint64)), ("topk", ctypes.POINTER(Match)),
+                ("topk_counts", ctypes.POINTER(ctypes.c_uint32)), ("bins", ctypes.POINTER(ctypes.c_uint64)),
+                ("invalid", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class BatchReportResult:
+    """What TemplateBatchEngine.report() returns, per query; the fields of a part that was not asked
+    for are None.  matches[q] and topk[q] are lists of Match that view the arrays the call filled."""
+
+    __slots__ = ("matches", "matches_counts", "topk", "bins", "invalid")
+
+    def __init__(self):
+        self.matches = self.matches_counts = self.topk = self.bins = self.invalid = None
+
+    def __repr__(self):
+        return (f"BatchReportResult(matches_counts={self.matches_counts}, "
+                f"topk={None if self.topk is None else len(self.topk)}, "
+                f"bins={None if self.bins is None else self.bins.shape}, invalid={self.invalid})")
+
+
 def _report(call, owner, threshold, cap, k, nbins, rematch):
     """One report call (iris_template_report, iris_resolver_report, iris_resolver_report_masks):
     fills a Report from the arguments that are not None, runs call(pointer to it) and collects the
@@ -283,6 +309,7 @@ def load_library(path=None):
             "iris_template_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_report": ([P, P, u64, u64, u64, ctypes.POINTER(Report)], ctypes.c_int),
+            "iris_template_batch_report": ([P, P, u64, u64, u64, ctypes.POINTER(BatchReport)], ctypes.c_int),
             "iris_resolver_report": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.POINTER(Report)],
                                      ctypes.c_int),
             "iris_resolver_report_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.POINTER(Report)], ctypes.c_int),
@@ -367,7 +394,7 @@ def exported_symbols():
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
         "iris_template_histogram", "iris_template_batch_histogram",
         "iris_resolver_histogram", "iris_resolver_histogram_masks", "iris_resolver_batch_histogram_masks",
-        "iris_template_report", "iris_resolver_report", "iris_resolver_report_masks",
+        "iris_template_report", "iris_resolver_report", "iris_resolver_report_masks", "iris_template_batch_report",
     ]
 
 
@@ -1465,6 +1492,53 @@ class TemplateBatchEngine(_Engine):
                                                             _ptr(invalid)))
         return bins, invalid
 
+    def report(self, db, parts, threshold=0.0, cap=0, k=0, nbins=0, first=0, n=None, index_base=0):
+        """Several of matches(), topk() and histogram() for every query from ONE pass over the
+        templates (iris_template_batch_report; no reference counterpart) -> BatchReportResult.
+        parts: REPORT_MATCHES | REPORT_TOPK | REPORT_HIST; threshold and cap (records per query; 0
+        only counts) serve the matches part, k the top-k part, nbins the histogram part.  Each part
+        is byte for byte what the sibling method's call writes: matches[q] the min(count, cap)
+        lowest indices, matches_counts[q] the exact total, topk[q] best first, bins[q] and
+        invalid[q] query q's histogram.  The records are views of the arrays the call filled."""
+        n = (len(db) - first) if n is None else n
+        parts = int(parts)
+        r = BatchReport()
+        res = BatchReportResult()
+        r.parts = parts
+        marr = mcounts = tarr = tcounts = None
+        room = 1
+        if parts & REPORT_MATCHES:
+            r.threshold = float(threshold)
+            r.matches_cap = int(cap)
+            if int(cap):
+                marr = (Match * (self.nq * int(cap)))()
+                r.matches = marr
+            mcounts = (ctypes.c_uint64 * self.nq)()
+            r.matches_counts = mcounts
+        if parts & REPORT_TOPK:
+            r.k = int(k)
+            room = max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1
+            tarr = (Match * (self.nq * room))()
+            tcounts = (ctypes.c_uint32 * self.nq)()
+            r.topk = tarr
+            r.topk_counts = tcounts
+        if parts & REPORT_HIST:
+            nb = int(nbins)
+            r.nbins = nb
+            res.bins = np.zeros((self.nq, nb if 0 < nb <= HIST_MAX_BINS else 1), np.uint64)
+            res.invalid = np.zeros(self.nq, np.uint64)
+            r.bins = res.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+            r.invalid = res.invalid.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        _check(load_library().iris_template_batch_report(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                         ctypes.byref(r)))
+        if parts & REPORT_MATCHES:
+            c = int(cap)
+            res.matches_counts = [int(x) for x in mcounts]
+            res.matches = [[marr[q * c + j] for j in range(min(c, res.matches_counts[q]))] for q in range(self.nq)]
+        if parts & REPORT_TOPK:
+            res.topk = [[tarr[q * room + j] for j in range(tcounts[q])] for q in range(self.nq)]
+        return res
+
 
 class DistanceBatchEngine(_Engine):
     """nq DistanceEngines at once (iris_distance_batch_engine_new): one pass over a share database
@@ -1954,7 +2028,7 @@ def f64_bits(x):
 
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
-    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "resolver_report", "TOPK_MAX", "HIST_MAX_BINS", "Report", "ReportResult", "REPORT_MATCHES", "REPORT_TOPK", "REPORT_HIST", "dot_bool", "dot_u16",
+    "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "resolver_report", "TOPK_MAX", "HIST_MAX_BINS", "Report", "ReportResult", "BatchReport", "BatchReportResult", "REPORT_MATCHES", "REPORT_TOPK", "REPORT_HIST", "dot_bool", "dot_u16",
     "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
