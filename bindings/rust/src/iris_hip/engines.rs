@@ -644,6 +644,102 @@ impl MasksBatchEngine {
         })?;
         Ok((0..self.nq).map(|q| (flat[q * room..(q + 1) * room].to_vec(), invalid[q])).collect())
     }
+
+    /// Several of `batch_matches`, `batch_topk` and `batch_histogram` for every query from ONE pass
+    /// over the masks and the share slabs (iris_resolver_batch_report_masks; no reference
+    /// counterpart).  A part is selected by its argument: `matches = Some((threshold, cap))` with
+    /// cap records a query (`0` only counts), `k`, `nbins`; one of each serves all queries.  Entry
+    /// q holds the selected parts as those methods return them for query q; `topk[0]` at k = 1 is
+    /// the batched resolve's entry q.
+    pub fn batch_report(
+        &self,
+        masks: &Database,
+        first: u64,
+        n: u64,
+        shares_device: &[*const u16],
+        index_base: u64,
+        matches: Option<(f64, u64)>,
+        k: Option<u32>,
+        nbins: Option<u32>,
+    ) -> Result<Vec<Report>> {
+        batch_report_call(self.nq, matches, k, nbins, |r| unsafe {
+            ffi::iris_resolver_batch_report_masks(
+                self.h.raw,
+                masks.raw(),
+                first,
+                n,
+                shares_device.as_ptr(),
+                shares_device.len() as u32,
+                index_base,
+                r,
+            )
+        })
+    }
+}
+
+/// One batch report call (iris_template_batch_report, iris_resolver_batch_report_masks) for nq
+/// queries: `call(report)` with the IrisBatchReport filled from the selected parts' arguments, then
+/// entry q's selected parts from its arrays.
+fn batch_report_call(
+    nq: usize,
+    matches: Option<(f64, u64)>,
+    k: Option<u32>,
+    nbins: Option<u32>,
+    call: impl FnOnce(*mut std::ffi::c_void) -> std::os::raw::c_int,
+) -> Result<Vec<Report>> {
+    let mut r = ffi::IrisBatchReport {
+        parts: 0,
+        k: 0,
+        nbins: 0,
+        reserved: 0,
+        threshold: 0.0,
+        matches: ptr::null_mut(),
+        matches_cap: 0,
+        matches_counts: ptr::null_mut(),
+        topk: ptr::null_mut(),
+        topk_counts: ptr::null_mut(),
+        bins: ptr::null_mut(),
+        invalid: ptr::null_mut(),
+    };
+    let cap = matches.map_or(0, |m| m.1);
+    let kroom = k.unwrap_or(1).clamp(1, ffi::IRIS_TOPK_MAX) as usize;
+    let broom = nbins.unwrap_or(1).clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize;
+    let mut lists = vec![ffi::IrisMatch::default(); nq * cap as usize];
+    let mut totals = vec![0u64; nq];
+    let mut best = vec![ffi::IrisMatch::default(); if k.is_some() { nq * kroom } else { 0 }];
+    let mut listed = vec![0u32; nq];
+    let mut bins = vec![0u64; if nbins.is_some() { nq * broom } else { 0 }];
+    let mut invalid = vec![0u64; nq];
+    if let Some((threshold, _)) = matches {
+        r.parts |= ffi::IRIS_REPORT_MATCHES;
+        r.threshold = threshold;
+        r.matches_cap = cap;
+        r.matches = if cap == 0 { ptr::null_mut() } else { lists.as_mut_ptr() };
+        r.matches_counts = totals.as_mut_ptr();
+    }
+    if let Some(k) = k {
+        r.parts |= ffi::IRIS_REPORT_TOPK;
+        r.k = k;
+        r.topk = best.as_mut_ptr();
+        r.topk_counts = listed.as_mut_ptr();
+    }
+    if let Some(nbins) = nbins {
+        r.parts |= ffi::IRIS_REPORT_HIST;
+        r.nbins = nbins;
+        r.bins = bins.as_mut_ptr();
+        r.invalid = invalid.as_mut_ptr();
+    }
+    check(call(&mut r as *mut ffi::IrisBatchReport as *mut _))?;
+    Ok((0..nq)
+        .map(|q| Report {
+            matches: matches.map(|_| {
+                let list = &lists[q * cap as usize..q * cap as usize + totals[q].min(cap) as usize];
+                (list.iter().map(match_to_pair).collect(), totals[q])
+            }),
+            topk: k.map(|_| best[q * kroom..q * kroom + listed[q] as usize].iter().map(match_to_pair).collect()),
+            histogram: nbins.map(|_| (bins[q * broom..(q + 1) * broom].to_vec(), invalid[q])),
+        })
+        .collect())
 }
 
 /// `distances` (src/lib.rs:82-87).
@@ -1034,69 +1130,9 @@ impl TemplateBatchEngine {
         k: Option<u32>,
         nbins: Option<u32>,
     ) -> Result<Vec<Report>> {
-        let nq = self.nq;
-        let mut r = ffi::IrisBatchReport {
-            parts: 0,
-            k: 0,
-            nbins: 0,
-            reserved: 0,
-            threshold: 0.0,
-            matches: ptr::null_mut(),
-            matches_cap: 0,
-            matches_counts: ptr::null_mut(),
-            topk: ptr::null_mut(),
-            topk_counts: ptr::null_mut(),
-            bins: ptr::null_mut(),
-            invalid: ptr::null_mut(),
-        };
-        let cap = matches.map_or(0, |m| m.1);
-        let kroom = k.unwrap_or(1).clamp(1, ffi::IRIS_TOPK_MAX) as usize;
-        let broom = nbins.unwrap_or(1).clamp(1, ffi::IRIS_HIST_MAX_BINS) as usize;
-        let mut lists = vec![ffi::IrisMatch::default(); nq * cap as usize];
-        let mut totals = vec![0u64; nq];
-        let mut best = vec![ffi::IrisMatch::default(); if k.is_some() { nq * kroom } else { 0 }];
-        let mut listed = vec![0u32; nq];
-        let mut bins = vec![0u64; if nbins.is_some() { nq * broom } else { 0 }];
-        let mut invalid = vec![0u64; nq];
-        if let Some((threshold, _)) = matches {
-            r.parts |= ffi::IRIS_REPORT_MATCHES;
-            r.threshold = threshold;
-            r.matches_cap = cap;
-            r.matches = if cap == 0 { ptr::null_mut() } else { lists.as_mut_ptr() };
-            r.matches_counts = totals.as_mut_ptr();
-        }
-        if let Some(k) = k {
-            r.parts |= ffi::IRIS_REPORT_TOPK;
-            r.k = k;
-            r.topk = best.as_mut_ptr();
-            r.topk_counts = listed.as_mut_ptr();
-        }
-        if let Some(nbins) = nbins {
-            r.parts |= ffi::IRIS_REPORT_HIST;
-            r.nbins = nbins;
-            r.bins = bins.as_mut_ptr();
-            r.invalid = invalid.as_mut_ptr();
-        }
-        check(unsafe {
-            ffi::iris_template_batch_report(
-                self.h.raw,
-                db.raw(),
-                first,
-                n,
-                index_base,
-                &mut r as *mut ffi::IrisBatchReport as *mut _,
-            )
-        })?;
-        Ok((0..nq)
-            .map(|q| Report {
-                matches: matches.map(|_| {
-                    let list = &lists[q * cap as usize..q * cap as usize + totals[q].min(cap) as usize];
-                    (list.iter().map(match_to_pair).collect(), totals[q])
-                }),
-                topk: k.map(|_| best[q * kroom..q * kroom + listed[q] as usize].iter().map(match_to_pair).collect()),
-                histogram: nbins.map(|_| (bins[q * broom..(q + 1) * broom].to_vec(), invalid[q])),
-            })
-            .collect())
+        batch_report_call(self.nq, matches, k, nbins, |r| unsafe {
+            ffi::iris_template_batch_report(self.h.raw, db.raw(), first, n, index_base, r)
+        })
     }
 }
 

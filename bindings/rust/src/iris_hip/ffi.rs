@@ -538,6 +538,18 @@ extern "C" {
         index_base: u64,
         report: *mut c_void,
     ) -> c_int;
+    // masks batch reports: several of the resolver's batch matches / topk / histogram of every probe
+    // from one masks pass; `report` points at an IrisBatchReport (the header declares it void *)
+    pub fn iris_resolver_batch_report_masks(
+        engine: *mut IrisEngine,
+        masks_db: *const IrisDb,
+        first: u64,
+        n: u64,
+        shares_device: *const *const u16,
+        parts: u32,
+        index_base: u64,
+        report: *mut c_void,
+    ) -> c_int;
     // threshold matching: every record below a distance (no reference counterpart for the threshold)
     pub fn iris_template_matches(
         engine: *mut IrisEngine,

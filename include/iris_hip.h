@@ -881,9 +881,9 @@ int iris_resolver_batch_histogram_masks(iris_engine_t *engine, const iris_db_t *
  * pass runs the matches part alone once more (never with matches_cap == 0); on a LANES database
  * that pass reuses the denominators already in the workspace.
  *
- * Out of scope: the masks batch engine (an iris_resolver_batch_report_masks needs per-slot sinks
- * and a per-group overflow rerun, at the register ceiling of the batch kernel's resolving form: the
- * next follow-up; the template batch engine has its report, iris_template_batch_report, section
+ * Out of scope: the batch engines here (the masks batch engine has its report,
+ * iris_resolver_batch_report_masks, section "masks batch reports" below, with per-slot sinks and a
+ * per-group overflow rerun; the template batch engine has iris_template_batch_report, section
  * "template batch reports" below); host-array forms (*_host); pipelined forms; device groups; more than one
  * threshold, k or histogram per call; a search part -- topk[0] at k = 1 is the search's result. */
 /* iris_resolver_search's sibling: denominators given */
@@ -929,7 +929,8 @@ int iris_resolver_report_masks(iris_engine_t *engine, const iris_db_t *masks_db,
  * aligned block of 4 queries run once more as iris_template_batch_matches' pass (never with
  * matches_cap == 0).
  *
- * Out of scope: the masks batch engine (the next follow-up); pipelined, host-array and
+ * Out of scope: the masks batch engine here (its report is iris_resolver_batch_report_masks,
+ * section "masks batch reports" below, which takes this struct); pipelined, host-array and
  * device-group forms; per-query thresholds, k or bin counts; a search part -- topk[q][0] at k = 1
  * is query q's search result. */
 typedef struct iris_batch_report {
@@ -949,6 +950,54 @@ typedef struct iris_batch_report {
 /* report: the caller's iris_batch_report_t; it crosses as void *, as iris_template_report's does */
 int iris_template_batch_report(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                                uint64_t index_base, void *report /* iris_batch_report_t * */);
+
+/* ------------------------------------------------------ masks batch reports
+ * The combined pass of a masks batch engine at the resolver: every probe's match list, k closest
+ * records and score histogram from ONE pass over the masks database and the participants' share
+ * slabs (src/main.rs:597-621, src/lib.rs:97-107).  A resolver that batches its requests asks all
+ * three of every probe, and each sibling batch call is a full pass; all three are functions of the
+ * one value the fused resolver step holds per (query, record), the best rotation as exact integers.
+ *
+ * The call takes iris_batch_report_t and the IRIS_REPORT_* bits unchanged: report->parts selects
+ * the parts (at least one, no others; reserved is 0), and one threshold, cap, k and bin count
+ * serve all nq queries.  Every other input is iris_resolver_batch_search_masks': a masks batch
+ * engine (nq = 1..64), a masks database of either layout, and the participants' query-major share
+ * arrays (shares_device[p]: nq slabs of n rows of 31 u16, 2-byte aligned).  The whole semantics:
+ * EACH SELECTED PART IS BYTE FOR BYTE WHAT ITS SIBLING BATCH CALL WRITES for the same arguments --
+ *   MATCHES  matches [nq][matches_cap] and matches_counts [nq] are iris_resolver_batch_matches_masks'
+ *            out and counts for (threshold, cap, index_base);
+ *   TOPK     topk [nq][k] and topk_counts [nq] are iris_resolver_batch_topk_masks' out and counts
+ *            for (k, index_base);
+ *   HIST     bins [nq][nbins] and invalid [nq] are iris_resolver_batch_histogram_masks' for nbins
+ * -- and so, by those calls' contracts, what the single-query *_masks calls (and
+ * iris_resolver_report_masks) write on slab q.  Indices are index_base + row; a distance above 1
+ * from garbage shares joins the last bin; a record whose 31 denominators are all zero (den == 0)
+ * is in no list and counts in `invalid`.  Entries past a count stay untouched.  The fields and
+ * arrays of a part that is not selected are neither read nor written.
+ *
+ * Refusals: the value arguments are checked before the handles -- report NULL, parts and reserved,
+ * then each selected part's own arguments under its sibling's rules, then the number of share
+ * parts (1..8) -- then the engine, the share pointers and the range as in the siblings: a masks
+ * batch engine (a single-query masks engine is IRIS_E_ARG: iris_resolver_report_masks), a masks
+ * database, and share pointers that are neither NULL nor at an odd address.  A refused or failed call writes nothing: nothing is written before every selected
+ * part of every query has succeeded.  n == 0: the counts and the bins are zero, and
+ * nothing is launched.
+ *
+ * One part selected runs that sibling batch call.  Two or three parts split the queries as the
+ * siblings do: on TILES ranges the batch kernel runs, groups of 2..4 queries take one pass each of
+ * the batch kernel's report form, a single left-over query the single-query report pass on its
+ * slab; smaller TILES ranges and LANES databases run one single-query report pass per query.  Every
+ * pass, each followed by its top-k merge, and one histogram reduce over all queries are enqueued
+ * before the call waits once.  A query whose match list overflows the room of the first pass has
+ * its group alone run once more as iris_resolver_batch_matches_masks' pass (never with
+ * matches_cap == 0); the buffer then grows so that the next identical call is one pass.
+ *
+ * Out of scope: host-array (*_host), pipelined and device-group forms; per-query thresholds, k or
+ * bin counts; a search part -- topk[q][0] at k = 1 is query q's iris_resolver_batch_search_masks
+ * result; the distance batch engine; a K-split batch kernel for small ranges. */
+int iris_resolver_batch_report_masks(iris_engine_t *engine, const iris_db_t *masks_db, uint64_t first, uint64_t n,
+                                     const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                     void *report /* iris_batch_report_t * */);
 
 /* ------------------------------------------------------------ arch plugin
  * The reference's backend plugin point (src/arch/mod.rs:5):

@@ -164,6 +164,59 @@ inline Report collect_report(const ReportRequest &req, F call, G rematch) {
     if (req.nbins) res.histogram->invalid = r.invalid;
     return res;
 }
+// One batch report call (iris_template_batch_report, iris_resolver_batch_report_masks) for nq queries:
+// call(&r) -> rc with r filled from the request, result[q]'s selected parts from its arrays.
+// cap = kAllMatches: the report has room for first_room records a query; when a list is longer,
+// every list comes from rematch(longest), the sibling matches call with that room.
+template <class F, class G>
+inline std::vector<Report> collect_batch_report(uint32_t nq, const ReportRequest &req, uint64_t first_room, F call, G rematch) {
+    iris_batch_report_t r{};
+    const bool all = req.cap == kAllMatches;
+    std::vector<Match> lists, best;
+    std::vector<uint64_t> totals(nq), bins, invalid(nq);
+    std::vector<uint32_t> listed(nq);
+    const uint32_t kroom = req.k && *req.k && *req.k <= IRIS_TOPK_MAX ? *req.k : 1;
+    const uint32_t broom = req.nbins && *req.nbins && *req.nbins <= IRIS_HIST_MAX_BINS ? *req.nbins : 1;
+    if (req.threshold) {
+        r.parts |= IRIS_REPORT_MATCHES;
+        r.threshold = *req.threshold;
+        r.matches_cap = all ? first_room : req.cap;
+        lists.resize((size_t)nq * r.matches_cap);
+        r.matches = r.matches_cap ? lists.data() : nullptr;
+        r.matches_counts = totals.data();
+    }
+    if (req.k) {
+        r.parts |= IRIS_REPORT_TOPK;
+        r.k = *req.k;
+        best.resize((size_t)nq * kroom);
+        r.topk = best.data();
+        r.topk_counts = listed.data();
+    }
+    if (req.nbins) {
+        r.parts |= IRIS_REPORT_HIST;
+        r.nbins = *req.nbins;
+        bins.assign((size_t)nq * broom, 0);
+        r.bins = bins.data();
+        r.invalid = invalid.data();
+    }
+    check(call(&r));
+    std::vector<Report> res(nq);
+    std::vector<Matches> full;
+    if (req.threshold && all && !totals.empty() && *std::max_element(totals.begin(), totals.end()) > r.matches_cap)
+        full = rematch(*std::max_element(totals.begin(), totals.end()));
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (req.threshold) {
+            const Match *src = lists.data() + (size_t)q * r.matches_cap;
+            if (!full.empty()) res[q].matches = std::move(full[q]);
+            else res[q].matches = Matches{std::vector<Match>(src, src + std::min(totals[q], r.matches_cap)), totals[q]};
+        }
+        if (req.k) res[q].topk = std::vector<Match>(best.begin() + (size_t)q * kroom, best.begin() + (size_t)q * kroom + listed[q]);
+        if (req.nbins)
+            res[q].histogram = Histogram{std::vector<uint64_t>(bins.begin() + (size_t)q * broom, bins.begin() + (size_t)(q + 1) * broom),
+                                         invalid[q]};
+    }
+    return res;
+}
 }  // namespace detail
 
 class Device {
@@ -762,6 +815,22 @@ public:
         }
         return res;
     }
+    // Several of matches(), topk() and histogram() for every query from ONE pass over the masks and
+    // the share slabs (iris_resolver_batch_report_masks, an iris_batch_report_t; no reference
+    // counterpart): result[q]'s selected parts are what those methods give for query q, the others
+    // are empty.  One threshold, cap, k and bin count serve all queries; result[q].topk[0] at k = 1
+    // is resolve()'s entry q.  cap = kAllMatches: room for 1024 records a query; when a list is
+    // longer, every list comes from matches() itself.  Give a cap to stay at one call.
+    std::vector<Report> report(const Database &db, const std::vector<const uint16_t *> &shares_device,
+                               const ReportRequest &req, uint64_t first, uint64_t n, uint64_t index_base = 0) const {
+        return detail::collect_batch_report(
+            nq_, req, 1024,
+            [&](iris_batch_report_t *r) {
+                return iris_resolver_batch_report_masks(h_, db.handle(), first, n, shares_device.data(),
+                                                        (uint32_t)shares_device.size(), index_base, r);
+            },
+            [&](uint64_t longest) { return matches(db, shares_device, first, n, *req.threshold, index_base, longest); });
+    }
 
 private:
     uint32_t nq_ = 0;
@@ -1007,52 +1076,10 @@ public:
     // a cap to stay at one call.
     std::vector<Report> report(const Database &db, const ReportRequest &req, uint64_t first, uint64_t n,
                                uint64_t index_base = 0) const {
-        iris_batch_report_t r{};
-        const bool all = req.cap == kAllMatches;
-        std::vector<Match> lists, best;
-        std::vector<uint64_t> totals(nq_), bins, invalid(nq_);
-        std::vector<uint32_t> listed(nq_);
-        const uint32_t kroom = req.k && *req.k && *req.k <= IRIS_TOPK_MAX ? *req.k : 1;
-        const uint32_t broom = req.nbins && *req.nbins && *req.nbins <= IRIS_HIST_MAX_BINS ? *req.nbins : 1;
-        if (req.threshold) {
-            r.parts |= IRIS_REPORT_MATCHES;
-            r.threshold = *req.threshold;
-            r.matches_cap = all ? std::min<uint64_t>(1024, std::max<uint64_t>(16, 65536 / std::max<uint32_t>(nq_, 1))) : req.cap;
-            lists.resize((size_t)nq_ * r.matches_cap);
-            r.matches = r.matches_cap ? lists.data() : nullptr;
-            r.matches_counts = totals.data();
-        }
-        if (req.k) {
-            r.parts |= IRIS_REPORT_TOPK;
-            r.k = *req.k;
-            best.resize((size_t)nq_ * kroom);
-            r.topk = best.data();
-            r.topk_counts = listed.data();
-        }
-        if (req.nbins) {
-            r.parts |= IRIS_REPORT_HIST;
-            r.nbins = *req.nbins;
-            bins.assign((size_t)nq_ * broom, 0);
-            r.bins = bins.data();
-            r.invalid = invalid.data();
-        }
-        check(iris_template_batch_report(h_, db.handle(), first, n, index_base, &r));
-        std::vector<Report> res(nq_);
-        std::vector<Matches> full;
-        if (req.threshold && all && !totals.empty() && *std::max_element(totals.begin(), totals.end()) > r.matches_cap)
-            full = matches(db, *req.threshold, first, n, index_base, *std::max_element(totals.begin(), totals.end()));
-        for (uint32_t q = 0; q < nq_; ++q) {
-            if (req.threshold) {
-                const Match *src = lists.data() + (size_t)q * r.matches_cap;
-                if (!full.empty()) res[q].matches = std::move(full[q]);
-                else res[q].matches = Matches{std::vector<Match>(src, src + std::min(totals[q], r.matches_cap)), totals[q]};
-            }
-            if (req.k) res[q].topk = std::vector<Match>(best.begin() + (size_t)q * kroom, best.begin() + (size_t)q * kroom + listed[q]);
-            if (req.nbins)
-                res[q].histogram = Histogram{std::vector<uint64_t>(bins.begin() + (size_t)q * broom, bins.begin() + (size_t)(q + 1) * broom),
-                                             invalid[q]};
-        }
-        return res;
+        return detail::collect_batch_report(
+            nq_, req, std::min<uint64_t>(1024, std::max<uint64_t>(16, 65536 / std::max<uint32_t>(nq_, 1))),
+            [&](iris_batch_report_t *r) { return iris_template_batch_report(h_, db.handle(), first, n, index_base, r); },
+            [&](uint64_t longest) { return matches(db, *req.threshold, first, n, index_base, longest); });
     }
 
 private:

@@ -1279,7 +1279,7 @@ int iris_resolver_report_masks(iris_engine_t *e, const iris_db_t *db, uint64_t f
     iris_report_t *const rep = (iris_report_t *)report;
     CHK(report_args(rep));  // the value arguments first: refused whatever the handles
     ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
-    CHK(single_masks_args(e, db, "iris_resolver_batch_matches_masks, _topk_masks and _histogram_masks (there is no batched report)"));
+    CHK(single_masks_args(e, db, "iris_resolver_batch_report_masks"));
     CHK(share_args(shares_device, parts, n));
     iris_device *d = e->dev;
     std::lock_guard<std::recursive_mutex> g(d->mu);
@@ -1450,6 +1450,195 @@ int iris_template_batch_report(iris_engine_t *e, const iris_db_t *db, uint64_t f
         if (want_hist) rep->invalid[q] = ones[q].invalid;
     }
     return 0;
+}
+
+// ------------------------------------------------------------------ masks batch reports
+
+// Two or three parts for the nq queries of a masks batch engine over w.r (not empty), every launch
+// unit of the walk (MasksWalk, as the sibling calls split) from ONE pass: a group of 2..4 queries
+// masks_batch_kernel<BATCH_REPORT> ("masks_batch_report"), a single query the single-query report
+// pass on its slab ("masks_report"; LANES "masks" + "resolver_report").  The device's buffers are
+// shared by region, as batch_report_run shares them: d->matches holds ONE lists region -- per query
+// of a unit its lists and the merge's spare lists, sized for the largest unit -- and behind it the
+// queries' match regions; d->match_count the nq match counters and behind them every query's
+// histogram copies; d->match_sinks the ReportSinks[nq], staged through the pinned result and copied
+// once; the pinned result the nq counts, the staged sinks, the merged lists [nq][k] and the nq rows,
+// each at a 64-byte boundary.  A unit's pass is followed by its merge levels, so the region serves
+// every unit in stream order (topk_run_units' argument: a unit's merge has consumed the region
+// before the next unit's pass writes it; the match regions and counters are per query and never
+// shared).  One hist_reduce over all nq rows (copies = 1: a copy) follows the last unit, and the
+// call waits once.  With a matches part the call is a threshold-match call (matches_run_units) whose
+// first pass is all units' report passes: room, overflow and rerun are
+// iris_resolver_batch_matches_masks', the rerun that call's plain match pass of the one unit.  On
+// LANES a rerun reuses the denominators where the workspace still holds that query's (the last
+// query enqueued).  Nothing reaches the caller's arrays before every part has succeeded.
+static int masks_batch_report_run(iris_device *d, const iris_engine *e, const iris_db *db, const MasksWalk &w,
+                                  const uint16_t *const *shares, uint32_t parts, uint64_t base,
+                                  const iris_batch_report_t *rep) {
+    const bool want_match = rep->parts & IRIS_REPORT_MATCHES, want_topk = rep->parts & IRIS_REPORT_TOPK,
+               want_hist = rep->parts & IRIS_REPORT_HIST;
+    const uint32_t nq = e->nq;
+    const uint64_t n = w.r.n;
+    const uint32_t k = want_topk ? rep->k : 0, nbins = want_hist ? rep->nbins : 0;
+    const uint32_t copies = !want_hist ? 0 : d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
+    const size_t words = (size_t)nbins + 1, row = (size_t)copies * words;
+    const size_t rows_bytes = want_hist ? nq * row * sizeof(uint64_t) : 0;
+    // the lists a unit's pass writes per query, and the region the largest unit takes
+    const auto unit_lists = [&](const MasksUnit &u) -> uint64_t {
+        if (!want_topk) return 0;
+        return u.m > 1 ? masks_batch_topk_units(d->hooks, w.r, u.m) : w.tiles ? masks_topk_units(d->hooks, w.r) : resolver_topk_units(n);
+    };
+    uint64_t region = 0;
+    for (MasksUnit u = w.unit(0); u.m; u = w.unit(u.q0 + u.m)) {
+        const uint64_t lists = unit_lists(u);
+        region = std::max(region, (uint64_t)u.m * (lists + topk_spare_lists(lists)) * k);
+    }
+    const size_t lists_bytes = region * sizeof(Partial);
+    const auto line = [](size_t b) { return (b + 63) / 64 * 64; };
+    const size_t stage_off = line(nq * sizeof(uint64_t));
+    const size_t topk_off = line(stage_off + nq * sizeof(ReportSinks));
+    const size_t hist_off = line(topk_off + (size_t)nq * k * sizeof(Partial));
+    CHK(ensure_host_result(d, hist_off + (want_hist ? nq * words * sizeof(uint64_t) : 0)));
+    CHK(ensure(d, d->match_sinks, nq * sizeof(ReportSinks)));
+    // the buffers' addresses are read when a step is enqueued: matches_run_units ensures them first
+    const auto rows_dev = [=] { return (uint64_t *)d->match_count.p + nq; };
+    struct {  // LANES: the query whose denominators the workspace holds
+        const uint16_t *den = nullptr;
+        uint32_t q = 0;
+    } held;
+    // one unit's pass of mode p: Report on the unit's device sinks, Match (the rerun) into ms
+    const auto unit_pass = [&](const MasksUnit &u, Pass p, const MatchSink *ms, const ReportSinks *stage) -> int {
+        const ReportSinks *dsinks = (const ReportSinks *)d->match_sinks.p + u.q0;
+        if (u.m > 1) {
+            if (p == Pass::Report)
+                return timed(d, "masks_batch_report", n * u.m, [&] {
+                    return launch_masks_batch(Pass::Report, d->hooks, d->stream, db->data, u.frags, u.m, w.r,
+                                              {shares, parts, u.q0, dsinks, stage + u.q0});
+                });
+            return timed(d, "masks_batch_match", n * u.m, [&] {
+                return launch_masks_batch(Pass::Match, d->hooks, d->stream, db->data, u.frags, u.m, w.r, {shares, parts, u.q0, ms});
+            });
+        }
+        // one query through the single-query forms, on its slab of every part
+        const uint16_t *sl[8];
+        w.slabs(u.q0, shares, parts, sl);
+        const uint16_t *den = !w.tiles && held.den && held.q == u.q0 ? held.den : nullptr;
+        CHK(masks_single_launch(d, u.one, db, w.r, sl, parts, p, p == Pass::Report ? report_sink(dsinks) : ms[0], &den));
+        held.den = den;
+        held.q = u.q0;
+        return 0;
+    };
+    // every unit's report pass and merge: ms = the nq match sinks, null without a matches part
+    const auto report_passes = [&](const MatchSink *ms) -> int {
+        char *res = (char *)d->host_result;
+        ReportSinks *stage = (ReportSinks *)(res + stage_off);
+        for (MasksUnit u = w.unit(0); u.m; u = w.unit(u.q0 + u.m)) {
+            const uint64_t lists = unit_lists(u), stride = (lists + topk_spare_lists(lists)) * k;
+            for (uint32_t s = 0; s < u.m; ++s) {
+                ReportSinks &x = stage[u.q0 + s];
+                x = ReportSinks{};
+                if (ms) x.match = ms[u.q0 + s];
+                if (want_topk) x.topk = topk_sink((Partial *)d->matches.p + s * stride, k);
+                if (want_hist) x.hist = hist_sink(rows_dev() + (u.q0 + s) * row, nbins, copies);
+            }
+        }
+        // the sinks cross to the device from pinned memory, as a template batch match pass's do
+        HIPCHK(hipMemcpyAsync(d->match_sinks.p, stage, nq * sizeof(ReportSinks), hipMemcpyHostToDevice, d->stream));
+        for (MasksUnit u = w.unit(0); u.m; u = w.unit(u.q0 + u.m)) {
+            CHK(unit_pass(u, Pass::Report, nullptr, stage));
+            if (!want_topk) continue;
+            const uint64_t lists = unit_lists(u), stride = (lists + topk_spare_lists(lists)) * k;
+            CHK(topk_merge_enqueue(d, (Partial *)d->matches.p, lists, stride, k, u.m, (Partial *)(res + topk_off) + (size_t)u.q0 * k));
+        }
+        return 0;
+    };
+    const auto enqueue = [&]() -> int {  // behind the last unit: the rows
+        if (!want_hist) return 0;
+        char *res = (char *)d->host_result;
+        if (copies > 1)
+            return timed(d, "hist_reduce", nq * row, [&] {
+                return launch_hist_reduce(d->stream, rows_dev(), (uint32_t)words, copies, nq, (uint64_t *)(res + hist_off));
+            });
+        HIPCHK(hipMemcpyAsync(res + hist_off, rows_dev(), nq * words * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+        return 0;
+    };
+    std::vector<Partial> best;
+    std::vector<uint64_t> rows, mcounts;
+    const auto taken = [&]() -> int {
+        const char *res = (const char *)d->host_result;
+        try {
+            if (want_topk) best.assign((const Partial *)(res + topk_off), (const Partial *)(res + topk_off) + (size_t)nq * k);
+            if (want_hist) rows.assign((const uint64_t *)(res + hist_off), (const uint64_t *)(res + hist_off) + nq * words);
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        return want_hist ? hist_rows_check(rows.data(), n, nbins, nq) : 0;
+    };
+    if (want_match) {
+        std::vector<MatchUnit> units;
+        try {
+            mcounts.resize(nq);
+            for (MasksUnit u = w.unit(0); u.m; u = w.unit(u.q0 + u.m))
+                units.push_back(MatchUnit{u.q0, u.m, [&unit_pass, u](const MatchSink *ms) { return unit_pass(u, Pass::Match, ms, nullptr); }});
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        const MatchWhole whole{nq, report_passes};
+        const MatchRider ride{lists_bytes, rows_bytes, enqueue, taken};
+        CHK(matches_run_units(d, n, base, rep->threshold, rep->matches, rep->matches_cap, mcounts.data(), nq, false, units, &whole,
+                              0, &ride));
+        memcpy(rep->matches_counts, mcounts.data(), nq * sizeof(uint64_t));
+    } else {
+        const size_t count_bytes = nq * sizeof(uint64_t) + rows_bytes;
+        CHK(ensure(d, d->matches, lists_bytes));
+        CHK(ensure(d, d->match_count, count_bytes));
+        HIPCHK(hipMemsetAsync(d->match_count.p, 0, count_bytes, d->stream));
+        CHK(report_passes(nullptr));
+        CHK(enqueue());
+        CHK(sync(d));
+        CHK(taken());
+    }
+    if (want_topk)
+        for (uint32_t q = 0; q < nq; ++q)
+            rep->topk_counts[q] = topk_list(best.data() + (size_t)q * k, k, base, rep->topk + (size_t)q * k);
+    if (want_hist) hist_rows_write(rows.data(), nbins, nq, rep->bins, rep->invalid);  // checked in taken()
+    return 0;
+}
+
+// Several of iris_resolver_batch_matches_masks, iris_resolver_batch_topk_masks and
+// iris_resolver_batch_histogram_masks for every probe of a masks batch engine from one pass over the
+// masks and the share slabs (header: "masks batch reports").  One part: the sibling call itself.
+// Otherwise masks_batch_report_run.
+int iris_resolver_batch_report_masks(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n,
+                                     const uint16_t *const *shares_device, uint32_t parts, uint64_t index_base,
+                                     void *report) {
+    IRIS_KEEP_DEVICE();
+    const iris_batch_report_t *const rep = (const iris_batch_report_t *)report;
+    CHK(batch_report_args(rep));  // the value arguments first: refused whatever the handles
+    ARG(parts >= 1 && parts <= 8, "parts must be 1..8");
+    CHK(masks_batch_args(e, db));
+    CHK(share_args(shares_device, parts, n));
+    for (uint32_t p = 0; n && p < parts; ++p) ARG(((uintptr_t)shares_device[p] & 1) == 0, "share array is not 2-byte aligned");
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (rep->parts == IRIS_REPORT_MATCHES)
+        return iris_resolver_batch_matches_masks(e, db, first, n, shares_device, parts, index_base, rep->threshold, rep->matches,
+                                                 rep->matches_cap, rep->matches_counts);
+    if (rep->parts == IRIS_REPORT_TOPK)
+        return iris_resolver_batch_topk_masks(e, db, first, n, shares_device, parts, index_base, rep->k, rep->topk,
+                                              rep->topk_counts);
+    if (rep->parts == IRIS_REPORT_HIST)
+        return iris_resolver_batch_histogram_masks(e, db, first, n, shares_device, parts, rep->nbins, rep->bins, rep->invalid);
+    if (n == 0) {  // nothing is launched
+        if (rep->parts & IRIS_REPORT_MATCHES) memset(rep->matches_counts, 0, e->nq * sizeof(uint64_t));
+        if (rep->parts & IRIS_REPORT_TOPK) memset(rep->topk_counts, 0, e->nq * sizeof(uint32_t));
+        if (rep->parts & IRIS_REPORT_HIST) CHK(hist_empty(e->nq, rep->nbins, rep->bins, rep->invalid));
+        return 0;
+    }
+    const MasksWalk w(e, db, first, n);
+    return masks_batch_report_run(d, e, db, w, shares_device, parts, index_base, rep);
 }
 
 }  // extern "C"

@@ -539,6 +539,12 @@ struct MasksBatchOut {
         : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, lists(l), stride(s), k(kk) {}
     MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, const MatchSink *hist_sinks, HistTag)
         : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, hists(hist_sinks) {}
+    // Report: reports[s] is query s's ReportSinks on the DEVICE (two or three parts, the same for every query, with one k,
+    // nbins and copies), staged[s] the host copy they were staged from, which the launcher checks
+    const ReportSinks *reports = nullptr, *staged = nullptr;
+    MasksBatchOut(const uint16_t *const *shares, uint32_t parts, uint32_t q0, const ReportSinks *device_sinks,
+                  const ReportSinks *host_copy)
+        : resolve(true), rs{shares, parts, q0, nullptr, nullptr, 0}, reports(device_sinks), staged(host_copy) {}
 };
 int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
                        LaunchRange r, const MasksBatchOut &o);

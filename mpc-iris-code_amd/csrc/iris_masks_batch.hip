@@ -14,6 +14,8 @@
 // The top-k form keeps, in place of the running best, each query's k best records of the wave as
 // a wave-resident sorted list (topk_insert, iris_device.hpp) and stores one list per wave and
 // query for launch_topk_merge to fold (iris_resolver_batch_topk_masks).
+// The report form feeds two or three of those sinks -- the match list, the wave's top-k list, the
+// LDS histogram -- from the one best rotation per (query, record) (iris_resolver_batch_report_masks).
 //
 // The query side: each wave reads the G queries' compact words (16 B per lane, step and query)
 // from L2, as masks_mfma_kernel<MASKS_RESOLVE> does for its one query; a query's fragments are
@@ -32,7 +34,7 @@ namespace {
 
 constexpr uint32_t kSteps = kMaskChunks / 4;  // 50 steps of 4 chunks
 
-enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2, BATCH_TOPK = 3, BATCH_HIST = 4 };
+enum { BATCH_OUT = 0, BATCH_RESOLVE = 1, BATCH_MATCH = 2, BATCH_TOPK = 3, BATCH_HIST = 4, BATCH_REPORT = 5 };
 
 __device__ __forceinline__ uint32_t dword_of(const uint4 &v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
@@ -55,6 +57,8 @@ struct MaskBatchArgs {
     MatchSink match[G];     // BATCH_MATCH: the slot's own records, room, counter and threshold
                             // BATCH_TOPK: topk_sink -- buf = the slot's lists [gridDim.x * 4][k], cap = k
                             // BATCH_HIST: hist_sink -- the slot's counter copies; every slot the same nbins and copies
+                            // BATCH_REPORT: report_sink -- the slot's ReportSinks of the device array; every slot
+                            // the same parts, k, nbins and copies
 };
 
 }  // namespace
@@ -75,6 +79,13 @@ struct MaskBatchArgs {
 // four slots), resident while the wave walks its tile groups.  The histograms are zeroed ahead of a
 // barrier before the walk and, behind a barrier after it, each valid slot's non-zero words are added
 // once to the workgroup's copy of a.match[g]'s counters (hist_flush).
+// BATCH_REPORT: BATCH_MATCH, BATCH_TOPK and BATCH_HIST from one walk.  a.match[g] points at slot g's
+// ReportSinks; they are scalar-loaded (report_sinks_load: a wave-uniform address) where they are used
+// -- per valid slot at the end of a tile group, and once more after the walk -- never held across the
+// K loop.  Whether a part is present is read from slot 0's struct (every slot selects the same parts),
+// so the test is the same for every wave of the grid: with a histogram part every wave of the
+// workgroup reaches the zeroing barrier and the flush barrier, both outside `if (total)`; with a
+// top-k part every wave of the grid stores each valid slot's list at BATCH_TOPK's unit numbers.
 template <int G, int T, int MODE>
 __global__ void __launch_bounds__(256, 2)
     masks_batch_kernel(const uint4 *__restrict__ db, MaskBatchArgs<G> a, uint64_t tile0, uint64_t ntiles, uint64_t first,
@@ -85,8 +96,8 @@ __global__ void __launch_bounds__(256, 2)
     const uint64_t nwaves = (uint64_t)gridDim.x * kWaveSlots;
     const uint64_t ngroups = (ntiles + T - 1) / T;
     // BATCH_RESOLVE and BATCH_TOPK: every wave of the grid writes after the walk; BATCH_HIST: every
-    // wave of the workgroup reaches the two histogram barriers
-    if (MODE != BATCH_RESOLVE && MODE != BATCH_TOPK && MODE != BATCH_HIST && wave >= ngroups) return;
+    // wave of the workgroup reaches the two histogram barriers; BATCH_REPORT: both
+    if (MODE != BATCH_RESOLVE && MODE != BATCH_TOPK && MODE != BATCH_HIST && MODE != BATCH_REPORT && wave >= ngroups) return;
     const uint32_t total = wave < ngroups ? (uint32_t)((ngroups - wave + nwaves - 1) / nwaves) * kSteps : 0;
     uint16_t *lds = sh_out[threadIdx.x >> 6];
     Partial best[G];
@@ -100,6 +111,18 @@ __global__ void __launch_bounds__(256, 2)
         for (int g = 0; g < G; ++g) hist_zero(hist + g * (kHistMaxBins + 1), hist_sink_bins(a.match[0]));
         __syncthreads();
     }
+    if constexpr (MODE == BATCH_REPORT) {
+        hist = hist_lds<G>();
+        const ReportSinks up = report_sinks_load(a.match[0]);
+        if (report_has_hist(up)) {  // workgroup-uniform
+#pragma unroll
+            for (int g = 0; g < G; ++g) hist_zero(hist + g * (kHistMaxBins + 1), hist_sink_bins(up.hist));
+            __syncthreads();
+        }
+    }
+    // BATCH_REPORT alone: a slot's sinks, loaded at the end of each tile group for the slot's tiles; every
+    // other mode neither writes nor reads it (resolve_tile's report path is the one reader)
+    ReportSinks group{};
 
     v16f acc[G][T];
     auto zero = [&] {
@@ -159,6 +182,7 @@ __global__ void __launch_bounds__(256, 2)
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     if (g < a.valid) {  // wave-uniform
+                        if constexpr (MODE == BATCH_REPORT) group = report_sinks_load(a.match[g]);
 #pragma unroll
                         for (int t = 0; t < T; ++t) {
                             if constexpr (MODE == BATCH_OUT) {
@@ -169,8 +193,9 @@ __global__ void __launch_bounds__(256, 2)
                                 // slot g's slab of every share array; alignment is the slab's own
                                 const ResolveView view{a.shares, a.parts, a.slab[g], ((a.aligned >> g) & 1u) != 0, a.match[g],
                                                        MODE == BATCH_RESOLVE ? a.dist[g] : nullptr, best[g],
-                                                       MODE == BATCH_HIST ? hist + g * (kHistMaxBins + 1) : nullptr};
-                                resolve_tile<MODE == BATCH_MATCH, MODE == BATCH_TOPK, MODE == BATCH_HIST>(
+                                                       MODE == BATCH_HIST || MODE == BATCH_REPORT ? hist + g * (kHistMaxBins + 1) : nullptr,
+                                                       MODE == BATCH_REPORT ? &group : nullptr};
+                                resolve_tile<MODE == BATCH_MATCH, MODE == BATCH_TOPK, MODE == BATCH_HIST, MODE == BATCH_REPORT>(
                                     view, lds, lane, (tile0 + tw + t) * kTile, tw + t < ntiles, acc[g][t], first, end);
                             }
                         }
@@ -213,6 +238,23 @@ __global__ void __launch_bounds__(256, 2)
             if (g < a.valid)
                 hist_flush(hist + g * (kHistMaxBins + 1), hist_sink_bins(a.match[g]), hist_sink_copy(a.match[g]));
     }
+    if constexpr (MODE == BATCH_REPORT) {  // each part as its own mode above, under the same grid-uniform tests
+        const ReportSinks done = report_sinks_load(a.match[0]);
+        if (report_has_topk(done)) {  // every wave of the grid: one list per slot
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g < a.valid) topk_store(report_sinks_load(a.match[g]).topk, wave, lane, best[g]);
+        }
+        if (report_has_hist(done)) {  // every wave of the workgroup
+            __syncthreads();
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g < a.valid) {
+                    const ReportSinks slot = report_sinks_load(a.match[g]);
+                    hist_flush(hist + g * (kHistMaxBins + 1), hist_sink_bins(slot.hist), hist_sink_copy(slot.hist));
+                }
+        }
+    }
     if constexpr (MODE == BATCH_RESOLVE) {
         __shared__ Partial sh_best[G][kWaveSlots];
 #pragma unroll
@@ -245,7 +287,9 @@ namespace {
 // 164 / 234 for four at 1 / 2; resolve form 122 / 256 and 192 / 256; match form 110 / 245 and
 // 169 / 233 (it keeps no running best: profiles/r10_masks_batch_matches.txt); top-k form 120 / 254
 // and 188 / 252 (the lists live in the running bests' registers, topk_insert's broadcasts in SGPRs:
-// profiles/r14_masks_batch_topk.txt), so this mode takes the resolve form's choice unchanged.
+// profiles/r14_masks_batch_topk.txt), so this mode takes the resolve form's choice unchanged;
+// report form 122 / 256 and 193 / 256, BATCH_HIST's LDS (the sinks are scalar-loaded per tile group,
+// not held across the walk: profiles/r28_resources.txt), the top-k form's choice too.
 template <int G>
 constexpr int batch_big_tiles() { return G == 2 ? 4 : 2; }
 
@@ -275,7 +319,7 @@ int launch_group(void *stream, const void *db, const MaskBatchArgs<G> &a, const 
     return check_launch();
 }
 
-template <int G>  // mode = BATCH_*: BATCH_OUT writes `out`, the others read rs, BATCH_MATCH, BATCH_TOPK and BATCH_HIST fill sinks
+template <int G>  // mode = BATCH_*: BATCH_OUT writes `out`, the others read rs, BATCH_MATCH, BATCH_TOPK, BATCH_HIST and BATCH_REPORT fill sinks
 int launch_slots(int mode, const Hooks &h, void *stream, const void *db, const void *const *qfrags, uint32_t m,
                  LaunchRange r, uint16_t *out, const MasksBatchResolve *rs, uint32_t *np, const MatchSink *sinks) {
     const BatchTiles t = batch_tiles(h, r, batch_big_tiles<G>());
@@ -306,6 +350,7 @@ int launch_slots(int mode, const Hooks &h, void *stream, const void *db, const v
     for (uint32_t p = 0; p < rs->parts; ++p) a.shares[p] = rs->shares[p];
     if (mode == BATCH_TOPK) return launch_group<G, BATCH_TOPK>(stream, db, a, t, r);
     if (mode == BATCH_HIST) return launch_group<G, BATCH_HIST>(stream, db, a, t, r);
+    if (mode == BATCH_REPORT) return launch_group<G, BATCH_REPORT>(stream, db, a, t, r);
     if (mode == BATCH_MATCH) return launch_group<G, BATCH_MATCH>(stream, db, a, t, r);
     return launch_group<G, BATCH_RESOLVE>(stream, db, a, t, r);
 }
@@ -328,7 +373,8 @@ bool masks_batch_runs(const Hooks &h, LaunchRange r) {
 // the most partials per query a pass over r writes (the grid at one tile per wave)
 uint32_t masks_batch_partials(const Hooks &h, LaunchRange r) { return r.n ? batch_tiles(h, r, 1).grid : 0; }
 
-// the lists each query of a top-k pass over r writes: one per wave of the grid (launch_slots')
+// the lists each query of a top-k pass, or of a report pass with a top-k part, over r writes: one per
+// wave of the grid (launch_slots')
 uint64_t masks_batch_topk_units(const Hooks &h, LaunchRange r, uint32_t m) {
     if (r.n == 0) return 0;
     return (uint64_t)batch_tiles(h, r, m == 2 ? batch_big_tiles<2>() : batch_big_tiles<kMasksBatchG>()).grid * kWaveSlots;
@@ -350,7 +396,7 @@ int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, con
         if (o.sinks || o.lists || o.hists || (!rs && !o.rows)) return -1;
         return launch_mode(rs ? BATCH_RESOLVE : BATCH_OUT, h, stream, db, qfrags, m, r, o.rows, rs, o.np, nullptr);
     case Pass::Match:
-        if (!rs || !o.sinks || o.hists) return -1;
+        if (!rs || !o.sinks || o.hists || o.reports) return -1;
         return launch_mode(BATCH_MATCH, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, o.sinks);
     case Pass::Topk:
         if (!rs || !o.lists || o.hists || o.k == 0 || o.k > kTopkMax) return -1;
@@ -361,6 +407,18 @@ int launch_masks_batch(Pass p, const Hooks &h, void *stream, const void *db, con
         for (uint32_t s = 0; s < m; ++s)
             if (!hist_sink_ok(o.hists[s]) || o.hists[s].cap != o.hists[0].cap) return -1;
         return launch_mode(BATCH_HIST, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, o.hists);
+    case Pass::Report:  // two or three parts, and the same parts, k, nbins and copies for all slots: the kernel tests slot 0's
+        if (!rs || !o.reports || !o.staged || o.sinks || o.lists || o.hists || o.rows) return -1;
+        for (uint32_t s = 0; s < m; ++s) {
+            const ReportSinks &x = o.staged[s], &x0 = o.staged[0];
+            const bool has_match = x.match.count, has_topk = x.topk.cap != 0, has_hist = x.hist.count;
+            if (has_match + has_topk + has_hist < 2) return -1;
+            if (has_match != (x0.match.count != nullptr) || x.topk.cap != x0.topk.cap) return -1;
+            if (has_topk && (x.topk.cap > kTopkMax || !x.topk.buf)) return -1;
+            if (has_hist != (x0.hist.count != nullptr) || (has_hist && (!hist_sink_ok(x.hist) || x.hist.cap != x0.hist.cap))) return -1;
+            ts[s] = report_sink(o.reports + s);
+        }
+        return launch_mode(BATCH_REPORT, h, stream, db, qfrags, m, r, nullptr, rs, nullptr, ts);
     default: return -1;
     }
 }

@@ -310,6 +310,7 @@ def load_library(path=None):
             "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_report": ([P, P, u64, u64, u64, ctypes.POINTER(Report)], ctypes.c_int),
             "iris_template_batch_report": ([P, P, u64, u64, u64, ctypes.POINTER(BatchReport)], ctypes.c_int),
+            "iris_resolver_batch_report_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.POINTER(BatchReport)], ctypes.c_int),
             "iris_resolver_report": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.POINTER(Report)],
                                      ctypes.c_int),
             "iris_resolver_report_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.POINTER(Report)], ctypes.c_int),
@@ -394,7 +395,7 @@ def exported_symbols():
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
         "iris_template_histogram", "iris_template_batch_histogram",
         "iris_resolver_histogram", "iris_resolver_histogram_masks", "iris_resolver_batch_histogram_masks",
-        "iris_template_report", "iris_resolver_report", "iris_resolver_report_masks", "iris_template_batch_report",
+        "iris_template_report", "iris_resolver_report", "iris_resolver_report_masks", "iris_template_batch_report", "iris_resolver_batch_report_masks",
     ]
 
 
@@ -1501,43 +1502,51 @@ class TemplateBatchEngine(_Engine):
         lowest indices, matches_counts[q] the exact total, topk[q] best first, bins[q] and
         invalid[q] query q's histogram.  The records are views of the arrays the call filled."""
         n = (len(db) - first) if n is None else n
-        parts = int(parts)
-        r = BatchReport()
-        res = BatchReportResult()
-        r.parts = parts
-        marr = mcounts = tarr = tcounts = None
-        room = 1
-        if parts & REPORT_MATCHES:
-            r.threshold = float(threshold)
-            r.matches_cap = int(cap)
-            if int(cap):
-                marr = (Match * (self.nq * int(cap)))()
-                r.matches = marr
-            mcounts = (ctypes.c_uint64 * self.nq)()
-            r.matches_counts = mcounts
-        if parts & REPORT_TOPK:
-            r.k = int(k)
-            room = max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1
-            tarr = (Match * (self.nq * room))()
-            tcounts = (ctypes.c_uint32 * self.nq)()
-            r.topk = tarr
-            r.topk_counts = tcounts
-        if parts & REPORT_HIST:
-            nb = int(nbins)
-            r.nbins = nb
-            res.bins = np.zeros((self.nq, nb if 0 < nb <= HIST_MAX_BINS else 1), np.uint64)
-            res.invalid = np.zeros(self.nq, np.uint64)
-            r.bins = res.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-            r.invalid = res.invalid.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-        _check(load_library().iris_template_batch_report(self.handle, db.handle, int(first), int(n), int(index_base),
-                                                         ctypes.byref(r)))
-        if parts & REPORT_MATCHES:
-            c = int(cap)
-            res.matches_counts = [int(x) for x in mcounts]
-            res.matches = [[marr[q * c + j] for j in range(min(c, res.matches_counts[q]))] for q in range(self.nq)]
-        if parts & REPORT_TOPK:
-            res.topk = [[tarr[q * room + j] for j in range(tcounts[q])] for q in range(self.nq)]
-        return res
+        f = load_library().iris_template_batch_report
+        return _batch_report(self.nq, parts, threshold, cap, k, nbins, lambda r: f(
+            self.handle, db.handle, int(first), int(n), int(index_base), ctypes.byref(r)))
+
+
+def _batch_report(nq, parts, threshold, cap, k, nbins, call):
+    """One batch report call (iris_template_batch_report, iris_resolver_batch_report_masks): the
+    iris_batch_report_t and the arrays of the selected parts for nq queries, call(struct) -> rc,
+    then the BatchReportResult whose records are views of the arrays the call filled."""
+    parts = int(parts)
+    r = BatchReport()
+    res = BatchReportResult()
+    r.parts = parts
+    marr = mcounts = tarr = tcounts = None
+    room = 1
+    if parts & REPORT_MATCHES:
+        r.threshold = float(threshold)
+        r.matches_cap = int(cap)
+        if int(cap):
+            marr = (Match * (nq * int(cap)))()
+            r.matches = marr
+        mcounts = (ctypes.c_uint64 * nq)()
+        r.matches_counts = mcounts
+    if parts & REPORT_TOPK:
+        r.k = int(k)
+        room = max(1, min(int(k), TOPK_MAX)) if int(k) > 0 else 1
+        tarr = (Match * (nq * room))()
+        tcounts = (ctypes.c_uint32 * nq)()
+        r.topk = tarr
+        r.topk_counts = tcounts
+    if parts & REPORT_HIST:
+        nb = int(nbins)
+        r.nbins = nb
+        res.bins = np.zeros((nq, nb if 0 < nb <= HIST_MAX_BINS else 1), np.uint64)
+        res.invalid = np.zeros(nq, np.uint64)
+        r.bins = res.bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        r.invalid = res.invalid.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    _check(call(r))
+    if parts & REPORT_MATCHES:
+        c = int(cap)
+        res.matches_counts = [int(x) for x in mcounts]
+        res.matches = [[marr[q * c + j] for j in range(min(c, res.matches_counts[q]))] for q in range(nq)]
+    if parts & REPORT_TOPK:
+        res.topk = [[tarr[q * room + j] for j in range(tcounts[q])] for q in range(nq)]
+    return res
 
 
 class DistanceBatchEngine(_Engine):
@@ -1695,6 +1704,21 @@ class MasksBatchEngine(_Engine):
         _check(load_library().iris_resolver_batch_histogram_masks(self.handle, db.handle, int(first), int(n), arr, len(ptrs),
                                                                   nb, _ptr(bins), _ptr(invalid)))
         return bins, invalid
+
+    def report(self, db, shares_device_ptrs, parts, threshold=0.0, cap=0, k=0, nbins=0, first=0, n=None, index_base=0):
+        """Several of matches(), topk() and histogram() for every query from ONE pass over the
+        masks and the share slabs (iris_resolver_batch_report_masks; no reference counterpart)
+        -> BatchReportResult, as TemplateBatchEngine.report returns it.  shares_device_ptrs as in
+        resolve(); parts: REPORT_MATCHES | REPORT_TOPK | REPORT_HIST; threshold and cap (records
+        per query; 0 only counts) serve the matches part, k the top-k part, nbins the histogram
+        part.  Each part is byte for byte what the sibling method's call writes; topk[q][0] at
+        k = 1 is resolve()'s entry q."""
+        n = (len(db) - first) if n is None else n
+        ptrs = [int(p) for p in shares_device_ptrs]
+        arr = (ctypes.c_void_p * max(len(ptrs), 1))(*ptrs)
+        f = load_library().iris_resolver_batch_report_masks
+        return _batch_report(self.nq, parts, threshold, cap, k, nbins, lambda r: f(
+            self.handle, db.handle, int(first), int(n), arr, len(ptrs), int(index_base), ctypes.byref(r)))
 
 
 # ====================================================================== device groups
