@@ -845,6 +845,36 @@ impl Drop for PendingTopk {
     }
 }
 
+/// An enqueued report pass (`iris_template_report_async`); `wait` blocks for it alone and returns
+/// what `TemplateEngine::report` returns for the same parts.
+pub struct PendingReport {
+    raw: *mut ffi::IrisPendingReport,
+    matches: Option<(f64, u64)>,
+    k: Option<u32>,
+    nbins: Option<u32>,
+}
+
+unsafe impl Send for PendingReport {}
+
+impl PendingReport {
+    pub fn wait(mut self) -> Result<Report> {
+        let raw = std::mem::replace(&mut self.raw, ptr::null_mut());
+        collect_report(self.matches, self.k, self.nbins, |r| unsafe {
+            ffi::iris_pending_report_wait(raw, r as *mut ffi::IrisReport as *mut _)
+        })
+    }
+}
+
+impl Drop for PendingReport {
+    fn drop(&mut self) {
+        if !self.raw.is_null() {
+            unsafe {
+                ffi::iris_pending_report_wait(self.raw, ptr::null_mut()); // refused, and the handle freed
+            }
+        }
+    }
+}
+
 impl TemplateEngine {
     pub fn new(query: &Template) -> Self {
         Self::new_on(default_device(), query).unwrap_or_else(|e| panic!("TemplateEngine::new: {e}"))
@@ -952,6 +982,58 @@ impl TemplateEngine {
         collect_report(matches, k, nbins, |r| unsafe {
             ffi::iris_template_report(self.h.raw, db.raw(), first, n, index_base, r as *mut ffi::IrisReport as *mut _)
         })
+    }
+
+    /// Enqueues `report` and returns at once (iris_template_report_async): a report pass still
+    /// running may compute the next one submitted, whatever parts and arguments the two ask for;
+    /// `nbins` alone is the pipelined histogram.  The engine may be dropped before the wait; the
+    /// database must outlive it, unmodified.
+    pub fn report_async(
+        &self,
+        db: &Database,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        matches: Option<(f64, u64)>,
+        k: Option<u32>,
+        nbins: Option<u32>,
+    ) -> Result<PendingReport> {
+        // the in scalars only: the submission reads no pointer
+        let mut r = ffi::IrisReport {
+            parts: 0,
+            k: k.unwrap_or(0),
+            nbins: nbins.unwrap_or(0),
+            topk_count: 0,
+            threshold: matches.map_or(0.0, |m| m.0),
+            matches: ptr::null_mut(),
+            matches_cap: matches.map_or(0, |m| m.1),
+            matches_count: 0,
+            topk: ptr::null_mut(),
+            bins: ptr::null_mut(),
+            invalid: 0,
+        };
+        if matches.is_some() {
+            r.parts |= ffi::IRIS_REPORT_MATCHES;
+        }
+        if k.is_some() {
+            r.parts |= ffi::IRIS_REPORT_TOPK;
+        }
+        if nbins.is_some() {
+            r.parts |= ffi::IRIS_REPORT_HIST;
+        }
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            ffi::iris_template_report_async(
+                self.h.raw,
+                db.raw(),
+                first,
+                n,
+                index_base,
+                &r as *const ffi::IrisReport as *const _,
+                &mut raw,
+            )
+        })?;
+        Ok(PendingReport { raw, matches, k, nbins })
     }
 
     /// Enqueues `topk` and returns at once (iris_template_topk_async): a pass still running may

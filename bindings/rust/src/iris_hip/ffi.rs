@@ -70,6 +70,8 @@ pub struct IrisPending {
 pub type IrisPendingMatches = IrisPending;
 /// `iris_pending_topk_t`: the same opaque struct again.
 pub type IrisPendingTopk = IrisPending;
+/// `iris_pending_report_t`: and again.
+pub type IrisPendingReport = IrisPending;
 /// Device groups (`iris_group_t`, `iris_group_db_t`, `iris_group_pending_t`).
 #[repr(C)]
 pub struct IrisGroup {
@@ -473,6 +475,18 @@ extern "C" {
         index_base: u64,
         report: *mut c_void,
     ) -> c_int;
+    // pipelined reports: the submission reads the in scalars of an IrisReport only; the wait takes
+    // the caller's IrisReport with the same parts, matches_cap, k and nbins
+    pub fn iris_template_report_async(
+        engine: *mut IrisEngine,
+        db: *const IrisDb,
+        first: u64,
+        n: u64,
+        index_base: u64,
+        report: *const c_void,
+        out: *mut *mut IrisPending,
+    ) -> c_int;
+    pub fn iris_pending_report_wait(pending: *mut IrisPending, report: *mut c_void) -> c_int;
     // resolver histograms: the same distribution from the participants' share rows (a distance can
     // exceed 1 on garbage shares: the last bin takes it)
     pub fn iris_resolver_histogram(

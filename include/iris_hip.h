@@ -86,11 +86,12 @@ typedef struct iris_device iris_device_t;
 typedef struct iris_db iris_db_t;
 typedef struct iris_engine iris_engine_t;
 typedef struct iris_pending iris_pending_t;
-/* The handles of iris_template_matches_async and iris_template_topk_async: the same opaque struct
- * under names of their own.  Each of the three waits refuses (IRIS_E_ARG) and leaves alone a handle
- * another submission made. */
+/* The handles of iris_template_matches_async, iris_template_topk_async and
+ * iris_template_report_async: the same opaque struct under names of their own.  Each of the four
+ * waits refuses (IRIS_E_ARG) and leaves alone a handle another submission made. */
 typedef iris_pending_t iris_pending_matches_t;
 typedef iris_pending_t iris_pending_topk_t;
+typedef iris_pending_t iris_pending_report_t;
 
 /* ---------------------------------------------------------------- errors */
 const char *iris_last_error(void);
@@ -726,8 +727,11 @@ int iris_pending_topk_wait(iris_pending_t *pending /* an iris_pending_topk_t */,
  * queries need a TILES database).  The bytes copied back per call are 8 (nbins + 1) per query,
  * whatever n is.
  *
- * Out of scope: the pipelined and device-group forms (histograms add: a caller sums its
- * shards); host-array forms; bin counts that are not a power of two and caller-given edges;
+ * The pipelined form of the single-query template call is iris_template_report_async with
+ * parts = IRIS_REPORT_HIST (section "pipelined reports" below).
+ *
+ * Out of scope: pipelined resolver and batch-engine forms and the device-group forms (histograms
+ * add: a caller sums its shards); host-array forms; bin counts that are not a power of two and caller-given edges;
  * weighted counts; more than 1024 bins (the batched kernel keeps four queries' histograms in LDS
  * beside its 128-KiB fragment ring: 16 KiB at 1024 bins fit the CU's 160 KiB, 64 KiB at 4096 do
  * not). */
@@ -778,7 +782,10 @@ int iris_template_batch_histogram(iris_engine_t *engine, const iris_db_t *db, ui
  * overflows the room of the first pass runs the matches part alone once more, as
  * iris_template_matches does (never with matches_cap == 0).
  *
- * Out of scope: the pipelined forms (a report pass neither hosts nor is hosted in the sharing ring);
+ * The pipelined template report is iris_template_report_async (section "pipelined reports" below):
+ * there a running report pass serves the next one; this blocking call neither hosts nor is hosted.
+ *
+ * Out of scope: pipelined resolver and batch-engine reports;
  * template batch engines here (iris_template_batch_report, section "template batch reports" below,
  * is their call) and masks batch engines; host-array forms and
  * device groups; more than one threshold, k or histogram per call; a search part -- topk[0] at
@@ -805,6 +812,59 @@ typedef struct iris_report {
  * every binding mirrors, and a struct of arguments is memory the caller lays out as above. */
 int iris_template_report(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
                          uint64_t index_base, void *report /* iris_report_t * */);
+
+/* -------------------------------------------------------- pipelined reports
+ * Pipelined form of iris_template_report, as iris_template_topk_async is of iris_template_topk (no
+ * reference counterpart: the reference's calls block, src/lib.rs:42-53; the loops generalised are
+ * src/template.rs:43-47 + src/main.rs:616-621).  A service that runs a query stream gets the match
+ * list, the k closest records and the histogram of every probe from one shared pass: a report pass
+ * that is still streaming the database also computes the report pass submitted after it.
+ *
+ * Submission: reads only the in scalars of *report -- parts, threshold, matches_cap, k, nbins --
+ * and copies them; it does not read the array pointers and writes nothing to the struct.  It
+ * enqueues the pass and returns at once.  The value arguments are refused before the handles under
+ * iris_template_report's rules: report NULL, parts, then each selected part's scalars (a NaN
+ * threshold, k outside 1..IRIS_TOPK_MAX, nbins not a power of two in 1..IRIS_HIST_MAX_BINS); the
+ * pointer checks move to the wait.  Then out == NULL, then the engine, database, layout and range
+ * as iris_template_report checks them; a batch engine is refused, and so is an engine that keeps
+ * no host copy of its query.  A refused submission leaves *out alone.
+ *
+ * Wait: iris_pending_report_wait takes the caller's iris_report_t.  Its parts must equal the
+ * submission's, and so must matches_cap, k and nbins of the selected parts (IRIS_E_ARG naming the
+ * field otherwise: the arrays' sizes follow from them); threshold is not read.  The pointers of
+ * the selected parts are checked under the sibling rules (matches may be NULL only with a cap of
+ * 0; topk and bins are required).  It blocks for THAT pass only, writes the out fields and arrays
+ * of the selected parts, and frees the handle whatever it returns -- a failed check included --
+ * but a handle of another kind of submission is refused with both names and left alone.
+ *
+ * Contract: each selected part is byte for byte what iris_template_report would have written at the
+ * submission for the same arguments, and so what iris_template_matches, iris_template_topk and
+ * iris_template_histogram write; entries past the counts are untouched; fields and arrays of
+ * unselected parts are neither read nor written; nothing is written before every selected part has
+ * succeeded (the histogram's "sums to n" check and a match list's second pass included).  n == 0
+ * gives zero counts and zero bins, launches nothing, and the handle owns no event or buffers.  A
+ * match list longer than the pass's room (max(matches_cap, 1024) records; never with a cap of 0)
+ * runs the matches part alone once more at the wait, blocking.
+ *
+ * Sharing: a report pass hosts only a report pass and is hosted only by one (same records of the
+ * same database, unwritten since; one guest per pass); the two may differ in parts, threshold, cap,
+ * k and nbins, and the result does not depend on it.  A handle of this call is a report pass
+ * whatever parts holds: parts = IRIS_REPORT_HIST is the pipelined histogram.  Kernel stat
+ * "report_shared": registrations and tile groups carried.
+ *
+ * The engine may be destroyed before the wait; the database must stay alive and unmodified until
+ * it.  Until its wait a pending holds one device buffer: the three sinks (128 bytes), the
+ * histogram's 64 copies of nbins + 1 counters (525 KB at 1024 bins), 24 bytes per record of the
+ * match list's room (24 KB at caps up to 1024) and one list of k records per wave of its pass
+ * (120 MB at k = 64 over 10M templates, 1.9 MB at k = 1), and 10 KB of pinned host memory.
+ *
+ * Out of scope: resolver, batch-engine and device-group pipelines; a report pass hosting a search,
+ * match or top-k pass, or the reverse; more than one guest per pass; k > 64. */
+int iris_template_report_async(iris_engine_t *engine, const iris_db_t *db, uint64_t first, uint64_t n,
+                               uint64_t index_base, const void *report /* const iris_report_t * */,
+                               iris_pending_t **out /* an iris_pending_report_t */);
+int iris_pending_report_wait(iris_pending_t *pending /* an iris_pending_report_t */,
+                             void *report /* iris_report_t * */);
 
 /* ----------------------------------------------------- resolver histograms
  * The same distribution where the MPC deployment first has distances: at the resolver, after the

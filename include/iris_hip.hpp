@@ -920,6 +920,31 @@ private:
     uint32_t k_;
 };
 
+// An enqueued report pass (TemplateEngine::report_async): wait() once for what report() with the same
+// request returns; destroying it unwaited waits and discards the result.
+class PendingReport {
+public:
+    PendingReport(iris_pending_report_t *p, const ReportRequest &req) : p_(p), req_(req) {}
+    PendingReport(PendingReport &&o) noexcept : p_(o.p_), req_(o.req_) { o.p_ = nullptr; }
+    PendingReport(const PendingReport &) = delete;
+    PendingReport &operator=(const PendingReport &) = delete;
+    ~PendingReport() {
+        if (p_) (void)iris_pending_report_wait(p_, nullptr);  // refused, and the handle freed
+    }
+    Report wait() {
+        if (!p_) throw Error(IRIS_E_ARG, "PendingReport::wait called twice");
+        iris_pending_report_t *p = p_;
+        p_ = nullptr;
+        return detail::collect_report(
+            req_, [&](iris_report_t *r) { return iris_pending_report_wait(p, r); },
+            [](uint64_t) -> Matches { throw Error(IRIS_E_ARG, "PendingReport: the cap is explicit"); });
+    }
+
+private:
+    iris_pending_report_t *p_;
+    ReportRequest req_;
+};
+
 // Template vs Template database (src/template.rs:43-64) with the resolver's argmin.
 class TemplateEngine : public detail::Engine {
 public:
@@ -976,6 +1001,30 @@ public:
         iris_pending_topk_t *p = nullptr;
         check(iris_template_topk_async(h_, db.handle(), first, n, index_base, k, &p));
         return PendingTopk(p, k);
+    }
+    // pipelined form of report() with an explicit cap, as matches_async(): returns once the pass is
+    // enqueued; a report pass still running may compute the next one submitted, whatever parts and
+    // arguments the two ask for -- nbins alone is the pipelined histogram (iris_template_report_async)
+    PendingReport report_async(const Database &db, const ReportRequest &req, uint64_t first, uint64_t n,
+                               uint64_t index_base = 0) const {
+        if (req.threshold && req.cap == kAllMatches) throw Error(IRIS_E_ARG, "report_async takes an explicit cap");
+        iris_report_t r{};  // the in scalars only: the submission reads no pointer
+        if (req.threshold) {
+            r.parts |= IRIS_REPORT_MATCHES;
+            r.threshold = *req.threshold;
+            r.matches_cap = req.cap;
+        }
+        if (req.k) {
+            r.parts |= IRIS_REPORT_TOPK;
+            r.k = *req.k;
+        }
+        if (req.nbins) {
+            r.parts |= IRIS_REPORT_HIST;
+            r.nbins = *req.nbins;
+        }
+        iris_pending_report_t *p = nullptr;
+        check(iris_template_report_async(h_, db.handle(), first, n, index_base, &r, &p));
+        return PendingReport(p, req);
     }
     // pipelined form of matches() with an explicit cap (the list holds the min(count, cap) lowest
     // indices, count is the total): returns once the pass is enqueued; a pass still running may

@@ -196,6 +196,8 @@ void device_teardown(iris_device *d) {
             if (m.dev.p) (void)hipFree(m.dev.p);
         for (MatchBufs &m : d->topk_free)
             if (m.dev.p) (void)hipFree(m.dev.p);
+        for (MatchBufs &m : d->report_free)
+            if (m.dev.p) (void)hipFree(m.dev.p);
         for (int b = 0; b < 2; ++b) {
             if (d->apart[b].p) (void)hipFree(d->apart[b].p);
             if (d->apart_read[b]) (void)hipEventDestroy(d->apart_read[b]);
@@ -396,6 +398,7 @@ int iris_device_kernel_stats(iris_device_t *d, const char *kernel, uint64_t *lau
     const int shared = !strcmp(kernel, "search_shared")  ? kShareSearch
                        : !strcmp(kernel, "match_shared") ? kShareMatch
                        : !strcmp(kernel, "topk_shared")  ? kShareTopk
+                       : !strcmp(kernel, "report_shared") ? kShareReport
                                                          : -1;
     if (shared >= 0) {
         // shared passes: launches = searches (match, top-k passes) registered as guests, items = tile groups

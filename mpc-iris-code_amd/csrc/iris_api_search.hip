@@ -79,7 +79,7 @@ int share_take(iris_device *d, uint32_t np, SharePass **out) {
 
 int iris_api::share_join(iris_device *d, int share_host, const iris_db *db, uint64_t first, uint64_t n, uint32_t np,
                          const iris_template_t *query, hipEvent_t after, ShareKind kind, Partial *partials,
-                         const MatchSink *sink, ShareJoin *out) {
+                         const MatchSink *sink, ShareJoin *out, const ReportPrep *prep) {
     *out = ShareJoin{};
     SharePass *sp = nullptr;
     if (d->hooks.search_share) CHK(share_take(d, np, &sp));
@@ -106,6 +106,11 @@ int iris_api::share_join(iris_device *d, int share_host, const iris_db *db, uint
     if (launch_share_prepare(d->share, sp->slot, guest ? (uint32_t *)sp->done.p : nullptr, np) != 0)
         return fail(IRIS_E_HIP, "kernel launch failed: share_prepare");
     if (match) HIPCHK(hipMemsetAsync(sink->count, 0, sizeof(uint64_t), d->share));
+    // a report pass's sinks and counters, for the same reason: the hosting pass reads the struct
+    // once `ready` is published and adds into the counters from then on
+    if (kind == kShareReport &&
+        launch_report_prepare(d->share, (ReportSinks *)sink->buf, prep->sinks, prep->zero, prep->words) != 0)
+        return fail(IRIS_E_HIP, "kernel launch failed: report_prepare");
     if (guest) {
         uint32_t *tab = (uint32_t *)sp->qbuf;
         uint32_t *frag = (uint32_t *)((char *)sp->qbuf + qalign(kTemplateTabBytes));

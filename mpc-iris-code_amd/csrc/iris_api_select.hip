@@ -3,7 +3,8 @@
 // the single-query template match and top-k (their handles live by iris_pending.hpp; here is only
 // what a match or a top-k handle adds), the distance histograms of the template engines and of
 // the resolver forms, and the combined pass that answers a match, a top-k and a histogram call of
-// one probe from one read (iris_template_report, iris_resolver_report, iris_resolver_report_masks),
+// one probe from one read (iris_template_report, iris_resolver_report, iris_resolver_report_masks;
+// pipelined: iris_template_report_async, whose running pass also serves the next submission),
 // and of every probe of a template batch engine from one GEMM pass (iris_template_batch_report).
 // Calls, locking and errors: see iris_api.hip.
 #include <string.h>
@@ -67,18 +68,28 @@ static int masks_single_launch(iris_device *d, const iris_engine *c, const iris_
 // hooks included -- runs the sharing form (§4.1) and takes a place in the ring; every other pass
 // (the rerun of an overflowing match list among them) runs the blocking call's kernel and neither
 // hosts nor is hosted.  query: the host copy a guest's fragments are built from.
+// A report call (kShareReport): ms is report_sink of the pending's device ReportSinks and prep what
+// that struct holds and the counters to clear -- on the sharing stream with a ring entry (share_join),
+// else on the device stream; under IRIS_SEARCH_SHARE=0 a report runs the blocking call's kernel.
 static int select_pass_enqueue(iris_device *d, const iris_db *db, LaunchRange r, const void *qtab, const void *qfrag,
-                               const iris_template_t *query, ShareKind kind, const MatchSink &ms, bool shared) {
-    const bool match = kind == kShareMatch;
-    const Pass p = match ? Pass::Match : Pass::Topk;
-    if (shared && db->k.layout == IRIS_LAYOUT_TILES && share_search_ok(d->hooks, r)) {
+                               const iris_template_t *query, ShareKind kind, const MatchSink &ms, bool shared,
+                               const ReportPrep *prep = nullptr) {
+    const bool match = kind == kShareMatch, report = kind == kShareReport;
+    const Pass p = match ? Pass::Match : report ? Pass::Report : Pass::Topk;
+    auto report_prepare = [&]() -> int {
+        if (launch_report_prepare(d->stream, (ReportSinks *)ms.buf, prep->sinks, prep->zero, prep->words) != 0)
+            return fail(IRIS_E_HIP, "kernel launch failed: report_prepare");
+        return 0;
+    };
+    if (shared && db->k.layout == IRIS_LAYOUT_TILES && share_search_ok(d->hooks, r) && (!report || d->hooks.search_share)) {
         ShareJoin j;
         CHK(share_join(d, d->share_last, db, r.first, r.n, mfma_search_partials(d->hooks, r), query, nullptr, kind, nullptr,
-                       &ms, &j));
+                       &ms, &j, prep));
         d->share_last = -1;
         // a match pass's counter: share_join zeroes it on the sharing stream, but only with a ring entry
         if (match && !j.sp) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
-        CHK(timed(d, match ? "template_match" : "template_topk", r.n, [&] {
+        if (report && !j.sp) CHK(report_prepare());  // a report pass's struct and counters, likewise
+        CHK(timed(d, pass_name(p, "template_match", "template_topk", nullptr, "template_report"), r.n, [&] {
             return launch_template_share(p, d->hooks, d->stream, db->data, qfrag, r, ms, nullptr,
                                          j.sp ? j.sp->slot : nullptr, j.own_done, j.count);
         }));
@@ -86,6 +97,7 @@ static int select_pass_enqueue(iris_device *d, const iris_db *db, LaunchRange r,
     }
     d->share_last = -1;  // only the device's latest pass can host
     if (match) HIPCHK(hipMemsetAsync(ms.count, 0, sizeof(uint64_t), d->stream));
+    if (report) CHK(report_prepare());
     return launch_template_select(d, db, qtab, qfrag, r, p, ms);
 }
 
@@ -1248,6 +1260,206 @@ int iris_template_report(iris_engine_t *e, const iris_db_t *db, uint64_t first, 
     return report_dispatch(d, n, index_base + first, rep, {n ? template_topk_lists(d, db, r) : 0, [&](Pass p, const MatchSink &s) {
         return launch_template_select(d, db, e->qtab, e->qfrag, r, p, s);
     }});
+}
+
+// ------------------------------------------------------------------ pipelined reports
+
+// iris_template_report_async .. iris_pending_report_wait (the handle's life:
+// iris_pending.hpp).  One device buffer per pending, from kReportPool (the "fit" pick: k and nbins
+// change from call to call):
+//   [0, kReportSinksBytes)   the ReportSinks the pass (and the pass that hosts it) reads
+//   hist copies              copies x (nbins + 1) u64 (no histogram part: none)
+//   the match counter        8 bytes, straight behind them: one region to clear
+//   the match records        room = min(n, max(cap, kMatchFirstRoom)) of them (cap 0: none)
+//   the top-k lists          units lists of k and the merge's spare lists
+// and one pinned slot (kReportSlotBytes): the counter and the first kMatchInline records, the merged
+// k records at kReportSlotTopkOff, the histogram row at kReportSlotHistOff.  Behind the pass, on the
+// side stream: the merge (its last level into the slot), the histogram's reduce (copies = 1: a copy)
+// into the slot, the copy of the counter and the inline records.
+constexpr size_t kReportSinksBytes = 128;
+static_assert(sizeof(ReportSinks) <= kReportSinksBytes, "report buffer layout");
+struct iris_pending_report : iris_pending {
+    const iris_db *db = nullptr;  // the caller keeps it alive and unmodified until the wait
+    uint64_t first = 0, cap = 0, room = 0;
+    double threshold = 0;
+    uint32_t parts = 0, k = 0, nbins = 0, copies = 0;
+    size_t cnt_off = 0, rec_off = 0;  // of the device buffer: the match counter, the records
+    iris_template_t query;  // an overflowing match list runs its pass again after the engine may be gone
+};
+
+int iris_template_report_async(iris_engine_t *e, const iris_db_t *db, uint64_t first, uint64_t n, uint64_t index_base,
+                               const void *report, iris_pending_t **out) {
+    IRIS_KEEP_DEVICE();
+    // the in scalars only, under iris_template_report's rules and in its order; the pointers wait for the wait
+    const iris_report_t *const rep = (const iris_report_t *)report;
+    ARG(rep, "report is NULL");
+    const uint32_t parts = rep->parts, all = IRIS_REPORT_MATCHES | IRIS_REPORT_TOPK | IRIS_REPORT_HIST;
+    ARG(parts != 0 && (parts & ~all) == 0, "parts must be one or more of IRIS_REPORT_MATCHES, _TOPK, _HIST");
+    const bool want_match = parts & IRIS_REPORT_MATCHES, want_topk = parts & IRIS_REPORT_TOPK,
+               want_hist = parts & IRIS_REPORT_HIST;
+    const double threshold = rep->threshold;
+    const uint64_t cap = want_match ? rep->matches_cap : 0;
+    const uint32_t k = want_topk ? rep->k : 0, nbins = want_hist ? rep->nbins : 0;
+    if (want_match) ARG(threshold == threshold, "threshold is NaN");
+    if (want_topk) ARG(k >= 1 && k <= IRIS_TOPK_MAX, "k must be 1..IRIS_TOPK_MAX (64)");
+    if (want_hist)
+        ARG(nbins >= 1 && nbins <= IRIS_HIST_MAX_BINS && (nbins & (nbins - 1)) == 0,
+            "nbins must be a power of two in 1..IRIS_HIST_MAX_BINS (1024)");
+    ARG(out, "out is NULL");
+    CHK(template_args(e, db));
+    iris_device *d = e->dev;
+    std::lock_guard<std::recursive_mutex> g(d->mu);
+    CHK(set_device(d));
+    CHK(range_ok(db, first, n));
+    if (!e->host_query) return fail(IRIS_E_ARG, "engine keeps no host copy of its query");
+    iris_pending_report *p = nullptr;
+    CHK(pending_new(d, kShareReport, n, index_base + first, &p));
+    p->db = db;
+    p->first = first;
+    p->cap = cap;
+    p->threshold = threshold;
+    p->parts = parts;
+    p->k = k;
+    p->nbins = nbins;
+    p->query = *e->host_query;
+    if (n == 0) return pending_publish(p, out);
+    const LaunchRange r{first, n};
+    const uint64_t units = want_topk ? template_topk_lists(d, db, r) : 0;
+    const uint32_t words = nbins + 1;
+    p->copies = !want_hist ? 0 : d->hooks.hist_copies ? d->hooks.hist_copies : kHistCopies;
+    p->room = cap ? std::min<uint64_t>(n, std::max<uint64_t>(cap, kMatchFirstRoom)) : 0;
+    const size_t hist_bytes = (size_t)p->copies * words * sizeof(uint64_t);
+    p->cnt_off = kReportSinksBytes + hist_bytes;
+    p->rec_off = p->cnt_off + sizeof(uint64_t);
+    const size_t lists_off = p->rec_off + p->room * sizeof(Partial);
+    int rc = bufs_take(d, kReportPool, lists_off + (units + topk_spare_lists(units)) * k * sizeof(Partial), p);
+    if (rc == 0) rc = pending_arm(p);
+    if (rc != 0) return pending_abandon(p, rc);
+    char *dev = (char *)p->bufs.dev.p, *slot = (char *)p->bufs.host;
+    uint64_t *hist = (uint64_t *)(dev + kReportSinksBytes), *cnt = (uint64_t *)(dev + p->cnt_off);
+    Partial *records = (Partial *)(dev + p->rec_off), *lists = (Partial *)(dev + lists_off), *spare = lists + units * k;
+    ReportPrep prep{ReportSinks{}, hist, (uint64_t)p->copies * words + 1};
+    if (want_match) prep.sinks.match = MatchSink{records, p->room, cnt, threshold};
+    if (want_topk) prep.sinks.topk = topk_sink(lists, k);
+    if (want_hist) prep.sinks.hist = hist_sink(hist, nbins, p->copies);
+    rc = select_pass_enqueue(d, db, r, e->qtab, e->qfrag, e->host_query, kShareReport, report_sink((const ReportSinks *)dev),
+                             true, &prep);
+    if (rc == 0) rc = pending_side_begin(p);
+    if (rc == 0 && want_topk)  // the merge, whose last level writes the pinned slot
+        rc = timed(d, "topk_merge", units, [&] {
+            return launch_topk_merge(d->aux, lists, spare, units, k, (Partial *)(slot + kReportSlotTopkOff));
+        }, d->aux);
+    if (rc == 0 && want_hist) {
+        if (p->copies > 1)
+            rc = timed(d, "hist_reduce", (uint64_t)p->copies * words, [&] {
+                return launch_hist_reduce(d->aux, hist, words, p->copies, 1, (uint64_t *)(slot + kReportSlotHistOff));
+            }, d->aux);
+        else
+            rc = pending_side_chk(p, hipMemcpyAsync(slot + kReportSlotHistOff, hist, words * sizeof(uint64_t),
+                                                    hipMemcpyDeviceToHost, d->aux));
+    }
+    if (rc == 0 && want_match) {  // the counter and the first records
+        const size_t bytes = sizeof(uint64_t) + std::min<uint64_t>(p->room, kMatchInline) * sizeof(Partial);
+        rc = pending_side_chk(p, hipMemcpyAsync(slot, cnt, bytes, hipMemcpyDeviceToHost, d->aux));
+    }
+    if (rc == 0) rc = pending_side_end(p);
+    if (rc != 0) return pending_abandon(p, rc);
+    return pending_publish(p, out);
+}
+
+// The `total` match records of a pending whose pass has ended -> recs (caller holds the device lock).
+// A list longer than its room: the matches part alone once more, blocking and unshared, as a plain
+// match pass into the buffer grown to the reported count (the top-k list and the histogram row are
+// off the slot by then), the query's tables built again from the host copy.
+static int pending_report_records(iris_pending_report *p, uint64_t total, Partial *recs) {
+    iris_device *d = p->dev;
+    if (total <= std::min<uint64_t>(p->room, kMatchInline)) {
+        memcpy(recs, (const char *)p->bufs.host + kMatchRecOff, total * sizeof(Partial));
+        return 0;
+    }
+    CHK(set_device(d));
+    if (total > p->room) {
+        void *q = nullptr;
+        CHK(dev_malloc(d, &q, qalign(kTemplateTabBytes) + kTemplateFragDwords * 4, "match rerun query"));
+        uint32_t *tab = (uint32_t *)q, *frag = (uint32_t *)((char *)q + qalign(kTemplateTabBytes));
+        p->room = total;
+        p->cnt_off = 0;
+        p->rec_off = kMatchRecOff;
+        int rc = ensure(d, p->bufs.dev, kMatchRecOff + total * sizeof(Partial));
+        uint64_t *cnt = (uint64_t *)p->bufs.dev.p;
+        if (rc == 0 && launch_query_template(d->stream, &p->query, tab, frag) != 0)
+            rc = fail(IRIS_E_HIP, "kernel launch failed: query tables");
+        if (rc == 0)
+            rc = select_pass_enqueue(d, p->db, LaunchRange{p->first, p->n}, tab, frag, &p->query, kShareMatch,
+                                     MatchSink{(Partial *)((char *)p->bufs.dev.p + kMatchRecOff), total, cnt, p->threshold},
+                                     false);
+        uint64_t again = 0;
+        if (rc == 0 && hipMemcpyAsync(&again, cnt, sizeof(again), hipMemcpyDeviceToHost, d->stream) != hipSuccess)
+            rc = fail(IRIS_E_HIP, "hipMemcpyAsync failed");
+        const int rs = sync(d);
+        (void)hipFree(q);
+        CHK(rc);
+        CHK(rs);
+        if (again != total) return fail(IRIS_E_HIP, "match pass counts differ between two runs");
+    }
+    // on the second side stream, which carries nothing of a template pipeline (iris_pending_matches_wait)
+    HIPCHK(hipMemcpyAsync(recs, (const char *)p->bufs.dev.p + p->rec_off, total * sizeof(Partial), hipMemcpyDeviceToHost,
+                          d->aux2));
+    HIPCHK(hipStreamSynchronize(d->aux2));
+    return 0;
+}
+
+int iris_pending_report_wait(iris_pending_t *pending, void *report) {
+    IRIS_KEEP_DEVICE();
+    iris_pending_report *p = nullptr;
+    CHK(pending_claim(pending, kShareReport, &p));
+    iris_report_t *const rep = (iris_report_t *)report;
+    const bool want_match = p->parts & IRIS_REPORT_MATCHES, want_topk = p->parts & IRIS_REPORT_TOPK,
+               want_hist = p->parts & IRIS_REPORT_HIST;
+    // the struct must be the submission's: the arrays' sizes follow from these fields
+    int rc = 0;
+    if (!rep) rc = fail(IRIS_E_ARG, "report is NULL");
+    else if (rep->parts != p->parts) rc = fail(IRIS_E_ARG, "parts differs from the submission's");
+    else if (want_match && rep->matches_cap != p->cap) rc = fail(IRIS_E_ARG, "matches_cap differs from the submission's");
+    else if (want_topk && rep->k != p->k) rc = fail(IRIS_E_ARG, "k differs from the submission's");
+    else if (want_hist && rep->nbins != p->nbins) rc = fail(IRIS_E_ARG, "nbins differs from the submission's");
+    else if (want_match && p->cap && !rep->matches) rc = fail(IRIS_E_ARG, "out is NULL with cap > 0");
+    else if (want_topk && !rep->topk) rc = fail(IRIS_E_ARG, "out is NULL");
+    else if (want_hist && !rep->bins) rc = fail(IRIS_E_ARG, "bins is NULL");
+    return pending_retire(p, pending_await(p), rc, [&]() -> int {
+        const uint64_t n = p->n;
+        const uint32_t k = p->k, nbins = p->nbins;
+        // every part's result off the slot and checked before anything reaches *rep: a rerun replaces the buffers
+        uint64_t total = 0;
+        Partial best[kTopkMax];
+        std::vector<uint64_t> row;
+        std::vector<Partial> recs;
+        const char *slot = (const char *)p->bufs.host;
+        if (n > 0) {
+            if (want_match) memcpy(&total, slot, sizeof(total));
+            if (total > n) return fail(IRIS_E_HIP, "match pass counted more records than the range holds");
+            if (want_topk) memcpy(best, slot + kReportSlotTopkOff, k * sizeof(Partial));
+        }
+        const uint64_t take = std::min(total, p->cap);
+        try {
+            if (want_hist && n > 0)
+                row.assign((const uint64_t *)(slot + kReportSlotHistOff), (const uint64_t *)(slot + kReportSlotHistOff) + nbins + 1);
+            else if (want_hist)
+                row.assign((size_t)nbins + 1, 0);
+            if (take) recs.resize(total);
+        } catch (const std::bad_alloc &) {
+            return fail(IRIS_E_NOMEM, "out of host memory");
+        }
+        if (want_hist) CHK(hist_rows_check(row.data(), n, nbins, 1));
+        if (take) CHK(pending_report_records(p, total, recs.data()));
+        if (want_match) {
+            if (take) match_list(recs.data(), total, take, p->base, rep->matches);
+            rep->matches_count = total;
+        }
+        if (want_topk) rep->topk_count = n > 0 ? topk_list(best, k, p->base, rep->topk) : 0;
+        if (want_hist) hist_rows_write(row.data(), nbins, 1, rep->bins, &rep->invalid);
+        return 0;
+    });
 }
 
 // ------------------------------------------------------------------ resolver reports

@@ -399,8 +399,10 @@ __device__ __forceinline__ void hist_count(uint32_t *lds, uint32_t nbins, int la
     if (inv != 0 && lane == 0) atomicAdd(&lds[nbins], (uint32_t)__popcll(inv));
 }
 // the workgroup's non-zero words -> dst (agent-scope relaxed u64 adds, as append_matches adds its
-// counter; neighbouring lanes add to neighbouring words)
-__device__ __forceinline__ void hist_flush(const uint32_t *lds, uint32_t nbins, uint64_t *dst) {
+// counter; neighbouring lanes add to neighbouring words).  Counters: uint64_t *, or the same pointer
+// global by type (the sharing pass, iris_mfma.hip)
+template <class Counters>
+__device__ __forceinline__ void hist_flush(const uint32_t *lds, uint32_t nbins, Counters dst) {
     for (uint32_t i = threadIdx.x; i <= nbins; i += blockDim.x) {
         const uint32_t v = lds[i];
         if (v != 0) __hip_atomic_fetch_add(dst + i, (uint64_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

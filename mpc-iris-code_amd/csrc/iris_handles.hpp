@@ -99,8 +99,9 @@ struct UploadTune {
 constexpr int kShareRing = 8;
 // The entry point a sharing pass came from: a pass hosts only a pass of its own kind.  The value
 // indexes the registrations and the device counters of tile groups carried (kernel stats
-// "search_shared", "match_shared", "topk_shared").
-enum ShareKind { kShareSearch = 0, kShareMatch = 1, kShareTopk = 2, kShareKinds = 3 };
+// "search_shared", "match_shared", "topk_shared", "report_shared").  A report pending is of kind
+// report whatever its parts: a single part too (the pipelined histogram is parts = HIST).
+enum ShareKind { kShareSearch = 0, kShareMatch = 1, kShareTopk = 2, kShareReport = 3, kShareKinds = 4 };
 struct SharePass {
     iris::GuestSlot *slot = nullptr;  // this pass's guest slot, read by its kernel
     DevBuf done;                      // as a guest: the words the hosting pass sets, read by this pass's kernel
@@ -129,6 +130,12 @@ struct MatchBufs {
 // pass's lists and behind them the merge's spare lists ((units + topk_spare_lists(units)) * k
 // records), host is a pinned slot of kTopkSlotBytes that takes the merged k records.
 constexpr size_t kTopkSlotBytes = iris::kTopkMax * sizeof(iris::Partial);
+// A pending iris_template_report_async owns one such pair as well (iris_api_select.hip has the
+// device buffer's layout): the pinned slot takes the match counter and the first kMatchInline
+// records, the merged k records and the histogram row.
+constexpr size_t kReportSlotTopkOff = 512, kReportSlotHistOff = kReportSlotTopkOff + kTopkSlotBytes;
+constexpr size_t kReportSlotBytes = kReportSlotHistOff + (IRIS_HIST_MAX_BINS + 1 + 7) / 8 * 8 * sizeof(uint64_t);
+static_assert(kMatchSlotBytes <= kReportSlotTopkOff && kReportSlotHistOff % 64 == 0, "report slot layout");
 
 struct iris_device {
     int ordinal = 0;
@@ -152,6 +159,8 @@ struct iris_device {
     std::vector<MatchBufs> match_free;
     // asynchronous top-k: the same for its pendings
     std::vector<MatchBufs> topk_free;
+    // asynchronous reports: the same for theirs
+    std::vector<MatchBufs> report_free;
     // zeroed device word of the fused (last-workgroup) search reduce; searches on the stream
     // are serialised, and each launch leaves it zeroed
     DevBuf ticket;
@@ -180,13 +189,14 @@ struct iris_device {
     // registrations run on (the side stream waits behind the running pass, so it cannot carry them),
     // the event that orders a pass behind its registration, and the device counter of tile groups
     // carried for guests (kernel stats "search_shared", with the registrations as its launches;
-    // word and entry [1]: the match passes', "match_shared"; [2]: the top-k passes', "topk_shared")
+    // word and entry [1]: the match passes', "match_shared"; [2]: the top-k passes', "topk_shared";
+    // [3]: the report passes', "report_shared")
     SharePass share_ring[kShareRing];
     int share_next = 0, share_last = -1;
     hipStream_t share = nullptr;
     hipEvent_t share_reg = nullptr;
     unsigned long long *share_count = nullptr;
-    uint64_t share_regs[kShareKinds] = {0, 0, 0};
+    uint64_t share_regs[kShareKinds] = {};
     // handles alive on this device (1 for the device handle itself + 1 per database
     // and engine handle): the device is torn down when the last one is released,
     // so handles may be destroyed in any order
@@ -547,8 +557,15 @@ int search_enqueue(iris_engine *e, const iris_db *db, uint64_t first, uint64_t n
 // share_last as the call found it) if that pass can host it, and orders the device stream behind
 // the registration.  query: the host copy the guest's fragments are built from; after: an event the
 // sharing stream waits for first (or null).  A search gives its partials buffer, a match pass its
-// sink (whose counter is zeroed here, on the sharing stream), a top-k pass its topk_sink.  The
+// sink (whose counter is zeroed here, on the sharing stream), a top-k pass its topk_sink, a report
+// pass report_sink of its device ReportSinks and `prep`: the struct is stored and its counters are
+// cleared here, on the sharing stream ahead of the publish (launch_report_prepare).  The
 // kernel takes sp->slot, own_done and count; share_launched, behind the launch, makes the pass the one that can host next.
+struct ReportPrep {
+    iris::ReportSinks sinks;  // what the device struct holds
+    uint64_t *zero;           // the histogram's copies and behind them the match counter: `words` u64
+    uint64_t words;
+};
 struct ShareJoin {
     SharePass *sp = nullptr;
     const uint32_t *own_done = nullptr;  // a guest's done words
@@ -556,7 +573,7 @@ struct ShareJoin {
 };
 int share_join(iris_device *d, int share_host, const iris_db *db, uint64_t first, uint64_t n, uint32_t np,
                const iris_template_t *query, hipEvent_t after, ShareKind kind, iris::Partial *partials,
-               const iris::MatchSink *sink, ShareJoin *out);
+               const iris::MatchSink *sink, ShareJoin *out, const ReportPrep *prep = nullptr);
 int share_launched(iris_device *d, const ShareJoin &j);
 // Fills dst with the source bytes [off, off + bytes) of a write; false on a read error (errno set).
 using SlotFill = std::function<bool(void *dst, size_t off, size_t bytes)>;

@@ -367,7 +367,9 @@ int launch_template_mfma(Pass p, const Hooks &h, void *stream, const void *db, c
 // own launch skips the groups marked there.  A search's results are partials, a match pass's the
 // hits appended to each query's sink, a top-k pass's each wave's list at unit blockIdx.x * 4 + wave
 // of each query's topk_sink (mfma_topk_units(h, r) units; k may differ).  A pass hosts passes of
-// its own mode only: the caller keeps them apart.
+// its own mode only: the caller keeps them apart.  A report pass (iris_template_report_async) feeds,
+// per query, the parts that query's ReportSinks hold -- the two queries' may differ in every field
+// -- and each query's lists and histogram copies are written as its own launch would write them.
 // The slot is device memory, zeroed before the hosting pass's launch and written once by
 // launch_share_publish* (the fields, then ready with agent-scope release).  Nothing else is read
 // while its writer runs: done words and what a pass wrote for its guest reach their readers (the
@@ -378,11 +380,12 @@ struct GuestSlot {
     const void *frag;   // the guest's query fragments (a buffer of the sharing ring, not the engine's)
     Partial *partials;  // the guest's partials buffer (a search)
     uint32_t *done;     // the guest's done array, one word per workgroup
-    MatchSink sink;     // the guest's sink (a match pass: its counter is zeroed ahead of the publish; a top-k pass: topk_sink)
+    MatchSink sink;     // the guest's sink (a match pass: its counter is zeroed ahead of the publish; a top-k pass: topk_sink;
+                        // a report pass: report_sink of its device ReportSinks, complete ahead of the publish)
 };
 // whether a range runs the form that can share: 4 tiles per wave, no K-split, separate reduce
 bool share_search_ok(const Hooks &h, LaunchRange r);
-// Search, Match or Topk where share_search_ok() (else -1): slot = this pass's guest slot (NULL:
+// Search, Match, Topk or Report where share_search_ok() (else -1): slot = this pass's guest slot (NULL:
 // never hosts), own_done = NULL or the words an earlier pass set for the tile groups it computed
 // for this query, count = NULL or a device counter of tile groups carried for guests.
 int launch_template_share(Pass p, const Hooks &h, void *stream, const void *db, const void *qfrag, LaunchRange r,
@@ -393,6 +396,10 @@ int launch_share_prepare(void *stream, GuestSlot *slot, uint32_t *done, uint32_t
 // a search's registration; a match pass's, and a top-k pass's (sink = topk_sink(lists, k))
 int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partial *partials, uint32_t *done);
 int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done);
+// a report pass's registration is launch_share_publish_match with report_sink(device ReportSinks).
+// What precedes it, and the pass's own launch: `sinks` stored at dst (device memory) and the
+// `words` u64 counters at `zero` cleared (the histogram's copies and the match counter), one launch
+int launch_report_prepare(void *stream, ReportSinks *dst, const ReportSinks &sinks, uint64_t *zero, uint64_t words);
 // test hook IRIS_SEARCH_SHARE_DELAY_US: a one-thread kernel that spins for `ticks` of the wall clock
 int launch_share_delay(void *stream, uint64_t ticks);
 

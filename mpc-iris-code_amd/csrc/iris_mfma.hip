@@ -551,6 +551,88 @@ __device__ __forceinline__ void round_topk(const v16f (&den)[NQ][T], const v16f 
     }
 }
 
+// The report form's epilogue of a round (iris_template_report_async): per query and tile the best
+// rotation once, and from it every part that query's sinks hold, each as its own form above feeds
+// it -- the histogram's count into the query's LDS histogram `hist` (hist_count), the hits appended
+// to its match sink (round_matches), the candidates into its wave-resident list (round_topk; list:
+// this lane's entry).  A part's presence is a scalar test, the same for every wave of the workgroup;
+// the pointers are global by type, as every sink's of a sharing pass.
+typedef __attribute__((address_space(1))) uint64_t *GlobalCounter;
+struct GlobalReport {
+    GlobalSink match;    // count null: no matches part
+    GlobalLists topk;    // k 0: no top-k part
+    GlobalCounter hist;  // counters[copy_mask + 1][nbins + 1]; null: no histogram part
+    uint32_t nbins, copy_mask;
+};
+__device__ __forceinline__ bool report_has_match(const GlobalReport &r) { return (uint64_t)r.match.count != 0; }
+__device__ __forceinline__ bool report_has_topk(const GlobalReport &r) { return r.topk.k != 0; }
+__device__ __forceinline__ bool report_has_hist(const GlobalReport &r) { return (uint64_t)r.hist != 0; }
+// the words a workgroup's thread 0 keeps of a query's ReportSinks in LDS (kReportWords u64 a query)
+// and a wave's copy of them, made uniform: SGPRs, read where a round's epilogue uses them, so that
+// nothing of them is carried across the streaming loop
+constexpr int kReportWords = 8;
+__device__ __forceinline__ uint64_t (*report_words_lds())[kReportWords] {  // of the kernel that calls it only
+    __shared__ uint64_t w[2][kReportWords];
+    return w;
+}
+__device__ __forceinline__ void report_words_store(uint64_t *w, const ReportSinks *sinks) {
+    const __attribute__((address_space(1))) ReportSinks *const p = (const __attribute__((address_space(1))) ReportSinks *)sinks;
+    w[0] = (uint64_t)p->match.buf;
+    w[1] = p->match.cap;
+    w[2] = (uint64_t)p->match.count;
+    w[3] = (uint64_t)__double_as_longlong(p->match.threshold);
+    w[4] = (uint64_t)p->topk.buf;
+    w[5] = p->topk.cap;
+    w[6] = p->hist.cap;
+    w[7] = (uint64_t)p->hist.count;
+}
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {  // as template_share_kernel's uniform64
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ GlobalReport report_words_load(const uint64_t *w) {
+    GlobalReport r;
+    r.match = GlobalSink{(GlobalPartial)uniform_u64(w[0]), uniform_u64(w[1]), (GlobalCounter)uniform_u64(w[2]),
+                         __longlong_as_double((long long)uniform_u64(w[3]))};
+    r.topk = GlobalLists{(GlobalPartial)uniform_u64(w[4]), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w[5])};
+    const uint64_t hc = uniform_u64(w[6]);
+    r.hist = (GlobalCounter)uniform_u64(w[7]);
+    r.nbins = (uint32_t)hc;
+    r.copy_mask = (uint32_t)(hc >> 32);
+    return r;
+}
+// One query's T tiles from tw.  Tiles past the range and records outside it are neither counted nor
+// candidates (the histogram counts EVERY record of the range once, so a clamped duplicate would show
+// in its sum); half 0 of the wave votes, as in every form above.
+template <int T>
+__device__ __forceinline__ void round_report(const GlobalReport &r, uint32_t *hist, const v16f (&den)[T],
+                                             const v16f (&s)[T], uint64_t tile0, uint64_t ntiles, uint64_t tw,
+                                             uint64_t first, uint64_t end, int lane, Partial &list) {
+    bool hit[T];
+    uint32_t hn[T], hd[T];
+    int hr[T];
+    uint64_t hi[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const uint64_t tg = (tile0 + tw + t) * kTile + (lane & 31);
+        const bool counted = (tw + t < ntiles) && tg >= first && tg < end && (lane >> 5) == 0;
+        best_rotation(lane, [&](int rr, uint32_t &nn, uint32_t &dd) {
+            dd = (uint32_t)den[t][rr];
+            nn = (uint32_t)(((int)dd - (int)s[t][rr]) >> 1);  // num = (den - S) / 2
+        }, hn[t], hd[t], hr[t]);
+        if (report_has_hist(r)) hist_count(hist, r.nbins, lane, counted, hn[t], hd[t]);
+        hit[t] = report_has_match(r) && match_hit(r.match, counted, hn[t], hd[t]);
+        if (!counted) hd[t] = 0;  // no candidate (a hit is a counted lane: its record keeps its den)
+        hi[t] = tg - first;
+    }
+    if (report_has_match(r)) append_matches<T>(r.match, lane, hit, hn, hd, hr, hi);
+    if (report_has_topk(r)) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) topk_insert(list, r.topk.k, lane, partial_of(hn[t], hd[t], hr[t], hi[t]), true);
+    }
+}
+
 template <int NQ, int T, class Epi>
 __device__ __forceinline__ void share_round(const uint4 *__restrict__ db, const GlobalFrag (&qf)[NQ], uint64_t tile0,
                                             uint64_t ntiles, uint64_t tw, int lane, Epi &&epi) {
@@ -748,8 +830,8 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
     }
 }
 
-// The pass of iris_template_search_async, iris_template_matches_async and iris_template_topk_async
-// over large TILES ranges (4 tiles per wave; the search with its separate reduce).  Each workgroup
+// The pass of iris_template_search_async, iris_template_matches_async, iris_template_topk_async and
+// iris_template_report_async over large TILES ranges (4 tiles per wave; the search with its separate reduce).  Each workgroup
 // decides at its start, from words another stream may write while the pass runs: its tile group was
 // computed for this query by the pass that hosted it (own_done) -> nothing to do; a guest has been
 // published in the slot -> both queries for the workgroup's 16 tiles in the two-query shape (2
@@ -764,8 +846,16 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
 // over its 4 tiles (round_topk) and stores it, empty or not, at unit blockIdx.x * kWaveSlots +
 // wslot of that query's lists -- the unit template_mfma_kernel<MF_TOPK> numbers -- so each unit of
 // a query's lists is written exactly once, by the hosting pass or by the query's own launch.
+// SH_REPORT: `out` is report_sink of the query's device ReportSinks and so is slot->sink for the
+// guest's; thread 0 reads both structs into LDS (the guest's behind the acquire: it was complete
+// before `ready` was published), and a round's epilogue feeds, per query, the parts that query's
+// struct holds (round_report): hits as SH_MATCH, the wave's list as SH_TOPK -- parked in LDS between
+// the rounds, stored at the same unit, empty lists included -- and every record's bin in the query's
+// own LDS histogram, which covers both rounds and is flushed once, behind a barrier under a
+// workgroup-uniform test, into copy blockIdx.x % copies of that query's counters.  A tile group feeds
+// a query's sinks in exactly one workgroup, so the histogram's sum is the range.
 //   Memory order: only the slot is written while the pass runs.  The done words and whatever a
-// pass writes for its guest (partials; records and counter adds, the adds agent-scope relaxed; lists) are
+// pass writes for its guest (partials; records, counter and histogram adds, the adds agent-scope relaxed; lists) are
 // read by the guest's own launch and what follows it on the device stream, so the end of the
 // kernel publishes them: they are plain stores, and own_done is read relaxed.  (An agent-scope
 // release store per tile group wrote the XCD's L2 back 19 532 times a pass, 0.43 ms of a 7.8-ms
@@ -775,7 +865,7 @@ __device__ __forceinline__ void share_finish(const Partial *sh, const GlobalPart
 // even_only (test hook): the guest counts as not visible in odd tile groups.
 // (ints, not an unnamed enum: MODE == SH_SEARCH is part of the kernel's mangled name, and host and
 // device passes number unnamed types differently)
-constexpr int SH_SEARCH = 0, SH_MATCH = 1, SH_TOPK = 2;
+constexpr int SH_SEARCH = 0, SH_MATCH = 1, SH_TOPK = 2, SH_REPORT = 3;
 template <int MODE>
 __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     template_share_kernel(const uint4 *__restrict__ db, const uint4 *__restrict__ qfrag, uint64_t tile0, uint64_t ntiles,
@@ -787,6 +877,13 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     // cache) and the slot's fields behind them; LDS makes the decision the same for every wave
     __shared__ uint32_t sh_flag[2];
     __shared__ uint64_t sh_guest[MODE == SH_MATCH ? 6 : MODE == SH_TOPK ? 4 : 3];
+    // SH_REPORT: the words of both queries' sinks ([0] this pass's, [1] the guest's), and the two LDS
+    // histograms zeroed by every wave ahead of the barrier below, which every wave reaches
+    uint64_t (*sh_report)[kReportWords] = nullptr;
+    if constexpr (MODE == SH_REPORT) {
+        sh_report = report_words_lds();
+        hist_zero(hist_lds<2>(), 2 * (kHistMaxBins + 1) - 1);
+    }
     if (threadIdx.x == 0) {
         const uint32_t dn =
             own_done ? __hip_atomic_load(own_done + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -805,9 +902,16 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
                 sh_guest[3] = slot->sink.cap;
                 sh_guest[4] = (uint64_t)slot->sink.count;
                 sh_guest[5] = (uint64_t)__double_as_longlong(slot->sink.threshold);
+            } else if constexpr (MODE == SH_REPORT) {
+                // the guest's struct was complete in device memory before `ready` was published
+                sh_guest[1] = 0;
+                report_words_store(sh_report[1], (const ReportSinks *)slot->sink.buf);
             } else {
                 sh_guest[1] = (uint64_t)slot->partials;
             }
+        }
+        if constexpr (MODE == SH_REPORT) {  // this pass's own: complete before its launch
+            if (!dn) report_words_store(sh_report[0], (const ReportSinks *)out.buf);
         }
         sh_flag[0] = dn;
         sh_flag[1] = rdy;
@@ -826,7 +930,61 @@ __global__ void __launch_bounds__(64 * kWaveSlots, kMfmaWgs)
     constexpr int kRounds = kMfmaTiles / 2;
     __shared__ FragRing sh_ring;  // the two-query rounds' operands (static: a solo workgroup holds it too)
     typedef __attribute__((address_space(1))) uint32_t *GlobalWord;
-    if constexpr (MODE == SH_TOPK) {
+    if constexpr (MODE == SH_REPORT) {
+        const uint64_t unit = (uint64_t)blockIdx.x * kWaveSlots + wslot;
+        uint32_t *const hist = hist_lds<2>();  // query qi's: hist + qi * (kHistMaxBins + 1), over both rounds
+        if (!shared) {
+            const GlobalFrag qf[1] = {(GlobalFrag)qfrag};
+            share_round<1, kMfmaTiles>(db, qf, tile0, ntiles, tw, lane, [&](const auto &den, const auto &s) {
+                const GlobalReport r = report_words_load(sh_report[0]);
+                Partial list = partial_none();
+                round_report<kMfmaTiles>(r, hist, den[0], s[0], tile0, ntiles, tw, first, end, lane, list);
+                if (report_has_topk(r)) topk_store_lists(r.topk, unit, lane, list);
+            });
+        } else {
+            const GlobalFrag qf[2] = {(GlobalFrag)qfrag, (GlobalFrag)uniform64(sh_guest[0])};
+            // a query's list waits in LDS while the next round streams, as SH_TOPK parks it; only one
+            // of the two is in registers at a time, and each lane reads back the entry it wrote
+            __shared__ Partial sh_list[kWaveSlots][2][64];
+#pragma unroll
+            for (int rd = 0; rd < kRounds; ++rd)
+                staged_round<kStagedDepth>(db, qf, tile0, ntiles, tw + 2 * rd, lane, wslot, sh_ring,
+                                           [&](const auto &den, const auto &s) {
+#pragma unroll
+                                               for (int qi = 0; qi < 2; ++qi) {
+                                                   const GlobalReport r = report_words_load(sh_report[qi]);
+                                                   Partial list = partial_none();
+                                                   if (rd > 0 && report_has_topk(r)) list = sh_list[wslot][qi][lane];
+                                                   round_report<2>(r, hist + qi * (kHistMaxBins + 1), den[qi], s[qi], tile0,
+                                                                   ntiles, tw + 2 * rd, first, end, lane, list);
+                                                   if (report_has_topk(r)) {
+                                                       if (rd + 1 < kRounds) sh_list[wslot][qi][lane] = list;
+                                                       else topk_store_lists(r.topk, unit, lane, list);
+                                                   }
+                                               }
+                                           });
+        }
+        // the histograms, once, after the last round: behind a barrier under a workgroup-uniform test
+        const GlobalReport own = report_words_load(sh_report[0]);
+        GlobalReport guest = own;
+        if (shared) guest = report_words_load(sh_report[1]);
+        const bool own_hist = report_has_hist(own), guest_hist = shared && report_has_hist(guest);
+        if (own_hist || guest_hist) {
+            __syncthreads();
+            if (own_hist) hist_flush(hist, own.nbins, own.hist + (uint64_t)(blockIdx.x & own.copy_mask) * (own.nbins + 1));
+            if (guest_hist)
+                hist_flush(hist + (kHistMaxBins + 1), guest.nbins,
+                           guest.hist + (uint64_t)(blockIdx.x & guest.copy_mask) * (guest.nbins + 1));
+        }
+        if (shared) {
+            const GlobalWord guest_done = (GlobalWord)uniform64(sh_guest[2]);
+            __syncthreads();  // every wave has fed the guest's sinks: only then is its tile group done
+            if (threadIdx.x == 1) {
+                __hip_atomic_store(guest_done + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (count) atomicAdd(count, 1ull);
+            }
+        }
+    } else if constexpr (MODE == SH_TOPK) {
         const uint64_t unit = (uint64_t)blockIdx.x * kWaveSlots + wslot;
         const GlobalLists own{(GlobalPartial)out.buf, (uint32_t)out.cap};
         if (!shared) {
@@ -950,6 +1108,15 @@ __global__ void share_publish_match_kernel(GuestSlot *slot, const void *frag, Ma
     slot->sink = sink;
     slot->done = done;
     __hip_atomic_store(&slot->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a report pass's own preparation: its ReportSinks stored in device memory (thread 0) and the
+// `words` counters behind `zero` cleared -- the histogram's copies and the match counter
+__global__ void __launch_bounds__(256) report_prepare_kernel(ReportSinks *dst, ReportSinks sinks, uint64_t *zero,
+                                                             uint64_t words) {
+    const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i0 == 0) *dst = sinks;
+    for (uint64_t i = i0; i < words; i += (uint64_t)gridDim.x * blockDim.x) zero[i] = 0;
 }
 
 __global__ void share_delay_kernel(uint64_t ticks) {
@@ -1152,7 +1319,8 @@ int launch_template_share(Pass p, const Hooks &h, void *stream, const void *db, 
     case Pass::Search: return share_pass<SH_SEARCH>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
     case Pass::Match: return share_pass<SH_MATCH>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
     case Pass::Topk: return share_pass<SH_TOPK>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
-    default: return -1;  // counts and histograms have no sharing form
+    case Pass::Report: return share_pass<SH_REPORT>(h, stream, db, qfrag, r, o, n_partials, slot, own_done, count);
+    default: return -1;  // counts have no sharing form; a histogram's is a report pass of that part alone
     }
 }
 
@@ -1169,6 +1337,12 @@ int launch_share_publish(void *stream, GuestSlot *slot, const void *frag, Partia
 
 int launch_share_publish_match(void *stream, GuestSlot *slot, const void *frag, const MatchSink &sink, uint32_t *done) {
     hipLaunchKernelGGL(share_publish_match_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, slot, frag, sink, done);
+    return check_launch();
+}
+
+int launch_report_prepare(void *stream, ReportSinks *dst, const ReportSinks &sinks, uint64_t *zero, uint64_t words) {
+    hipLaunchKernelGGL(report_prepare_kernel, dim3((uint32_t)grid_stride_blocks(words ? words : 1)), dim3(256), 0,
+                       (hipStream_t)stream, dst, sinks, zero, words);
     return check_launch();
 }
 

@@ -1,6 +1,7 @@
 // iris_pending.hpp — the life of a pending handle, from the submission of
-// iris_template_search_async, iris_template_matches_async or iris_template_topk_async to its wait:
-// what a handle owns, and the one copy of every step the three submit / wait pairs share.
+// iris_template_search_async, iris_template_matches_async, iris_template_topk_async or
+// iris_template_report_async to its wait: what a handle owns, and the one copy of every step the
+// four submit / wait pairs share.
 //
 // A submission runs, under the device lock: pending_new; for an empty range pending_publish at once
 // (such a handle owns no event and no buffers); else its slot or buffers (take_result_slot,
@@ -15,7 +16,8 @@
 #include "iris_handles.hpp"
 
 // iris_template_matches_async's handle extends it (iris_pending_matches, iris_api_select.hip), as does
-// iris_template_topk_async's (iris_pending_topk), and `kind` tells each wait which one it was given
+// iris_template_topk_async's (iris_pending_topk) and iris_template_report_async's
+// (iris_pending_report), and `kind` tells each wait which one it was given
 struct iris_pending {
     ShareKind kind = kShareSearch;
     iris_device *dev = nullptr;
@@ -35,7 +37,8 @@ struct PendingCalls {
 inline constexpr PendingCalls kPendingCalls[kShareKinds] = {
     {"iris_template_search_async", "iris_pending_wait", nullptr},
     {"iris_template_matches_async", "iris_pending_matches_wait", "enqueue match copy: "},
-    {"iris_template_topk_async", "iris_pending_topk_wait", "enqueue top-k merge: "}};
+    {"iris_template_topk_async", "iris_pending_topk_wait", "enqueue top-k merge: "},
+    {"iris_template_report_async", "iris_pending_report_wait", "enqueue report results: "}};
 
 // A free list of (device buffer, pinned slot) pairs: its pinned slots come in blocks of `slots`
 // (d->slot_blocks, as take_result_slot's), the device buffers on first use.
@@ -48,6 +51,7 @@ struct BufPool {
 };
 inline constexpr BufPool kMatchPool{&iris_device::match_free, kMatchSlotBytes, 64, "match slots", false};
 inline constexpr BufPool kTopkPool{&iris_device::topk_free, kTopkSlotBytes, 32, "top-k slots", true};
+inline constexpr BufPool kReportPool{&iris_device::report_free, kReportSlotBytes, 16, "report slots", true};
 
 // A pair for p whose device buffer holds dev_bytes (caller holds the device lock)
 inline int bufs_take(iris_device *d, const BufPool &pool, size_t dev_bytes, iris_pending *p) {

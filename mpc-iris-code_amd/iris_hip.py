@@ -309,6 +309,8 @@ def load_library(path=None):
             "iris_template_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_batch_histogram": ([P, P, u64, u64, ctypes.c_uint32, P, P], ctypes.c_int),
             "iris_template_report": ([P, P, u64, u64, u64, ctypes.POINTER(Report)], ctypes.c_int),
+            "iris_template_report_async": ([P, P, u64, u64, u64, ctypes.POINTER(Report), PP], ctypes.c_int),
+            "iris_pending_report_wait": ([P, ctypes.POINTER(Report)], ctypes.c_int),
             "iris_template_batch_report": ([P, P, u64, u64, u64, ctypes.POINTER(BatchReport)], ctypes.c_int),
             "iris_resolver_batch_report_masks": ([P, P, u64, u64, P, ctypes.c_uint32, u64, ctypes.POINTER(BatchReport)], ctypes.c_int),
             "iris_resolver_report": ([P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, P, u64, u64, ctypes.POINTER(Report)],
@@ -395,6 +397,7 @@ def exported_symbols():
         "iris_resolver_batch_topk_masks", "iris_template_batch_topk",
         "iris_template_histogram", "iris_template_batch_histogram",
         "iris_resolver_histogram", "iris_resolver_histogram_masks", "iris_resolver_batch_histogram_masks",
+        "iris_template_report_async", "iris_pending_report_wait",
         "iris_template_report", "iris_resolver_report", "iris_resolver_report_masks", "iris_template_batch_report", "iris_resolver_batch_report_masks",
     ]
 
@@ -1330,6 +1333,37 @@ class TemplateEngine(_Engine):
         return _report(lambda r: f(self.handle, db.handle, int(first), int(n), int(index_base), r), self, threshold, cap, k, nbins,
                        lambda count: self.matches(db, threshold, first, n, index_base, cap=count)[0])
 
+    def report_async(self, db, threshold=None, cap=None, k=None, nbins=None, first=0, n=None, index_base=0):
+        """Enqueue report() and return at once (iris_template_report_async) -> PendingReport, whose
+        wait() returns the ReportResult that report() with the same arguments returns.  A report
+        pass that is still streaming the database also computes the one submitted after it,
+        whatever parts and arguments the two ask for; `nbins` alone is the pipelined histogram.
+        The engine may be closed before the wait; the database stays alive and unmodified until it.
+        cap None returns every match: the pass has room for 1024 records (or what the engine
+        remembers of its last list), and a longer list comes from matches() at the wait -- the
+        one case in which the engine must still be open then."""
+        n = (len(db) - first) if n is None else n
+        r = Report()  # the in scalars only: the submission reads no pointer
+        room = None
+        if threshold is not None:
+            r.parts |= REPORT_MATCHES
+            r.threshold = float(threshold)
+            room = max(1024, getattr(self, "_match_room", 0)) if cap is None else int(cap)
+            r.matches_cap = room
+        if k is not None:
+            r.parts |= REPORT_TOPK
+            r.k = int(k)
+        if nbins is not None:
+            r.parts |= REPORT_HIST
+            r.nbins = int(nbins)
+        h = ctypes.c_void_p()
+        _check(load_library().iris_template_report_async(self.handle, db.handle, int(first), int(n), int(index_base),
+                                                         ctypes.byref(r), ctypes.byref(h)))
+        rematch = None
+        if threshold is not None and cap is None:
+            rematch = lambda count: self.matches(db, threshold, first, n, index_base, cap=count)[0]
+        return PendingReport(h, self, threshold, room, k, nbins, rematch)
+
     def topk_async(self, db, k, first=0, n=None, index_base=0):
         """Enqueue topk() and return at once (iris_template_topk_async) -> PendingTopk, whose
         wait() returns what topk() with the same arguments returns.  The engine may be closed
@@ -1339,6 +1373,34 @@ class TemplateEngine(_Engine):
         _check(load_library().iris_template_topk_async(self.handle, db.handle, int(first), int(n), int(index_base),
                                                        int(k), ctypes.byref(h)))
         return PendingTopk(h, int(k))
+
+
+class PendingReport:
+    """An enqueued report pass (TemplateEngine.report_async); wait() -> ReportResult, once."""
+
+    def __init__(self, handle, owner, threshold, room, k, nbins, rematch):
+        self.handle = handle
+        self._args = (owner, threshold, room, k, nbins, rematch)
+
+    def wait(self):
+        if self.handle is None:
+            raise IrisError(-1, "PendingReport.wait called twice")
+        h, self.handle = self.handle, None
+        owner, threshold, room, k, nbins, rematch = self._args
+        f = load_library().iris_pending_report_wait
+        res = _report(lambda r: f(h, r), owner, threshold, room, k, nbins, rematch)
+        if rematch is not None:  # cap None: every match, as report() returns them
+            if res.matches_count > room:
+                res.matches = rematch(res.matches_count)
+            owner._match_room = min(res.matches_count + res.matches_count // 4, 1 << 22)
+        return res
+
+    def __del__(self):
+        if getattr(self, "handle", None) is not None:
+            try:
+                load_library().iris_pending_report_wait(self.handle, None)  # refused, and the handle freed
+            except Exception:
+                pass
 
 
 class PendingTopk:
@@ -2053,7 +2115,7 @@ def f64_bits(x):
 __all__ = [
     "Bits", "EncodedBits", "Template", "encode", "decode_distance", "resolver_search", "resolver_search_device", "distances", "denominators", "MasksEngine",
     "DistanceEngine", "TemplateEngine", "TemplateBatchEngine", "Device", "Database", "Match", "merge_matches", "merge_topk", "resolver_topk", "resolver_histogram", "resolver_report", "TOPK_MAX", "HIST_MAX_BINS", "Report", "ReportResult", "BatchReport", "BatchReportResult", "REPORT_MATCHES", "REPORT_TOPK", "REPORT_HIST", "dot_bool", "dot_u16",
-    "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingTopk",
+    "Group", "GroupDatabase", "GroupPendingSearch", "PendingMatches", "PendingReport", "PendingTopk",
     "dot_bool_batch", "dot_u16_batch", "IrisError", "load_library", "KIND_MASKS", "KIND_SHARES", "KIND_TEMPLATES",
     "LAYOUT_DEFAULT", "LAYOUT_LANES", "LAYOUT_TILES", "config",
     "ROTATIONS", "BITS", "LIMBS", "COLS", "ROWS",
